@@ -27,9 +27,24 @@ VALU lane-ops (rocprofv3 SQ_INSTS_VALU x 64, profiles/pmc_kernels.json, measured
 on the same workload) / mean launch time, against 256 CU x 4 SIMD x 32 lanes x
 2.4 GHz.  `traffic` = HBM bytes per launch from the same PMC record (FETCH_SIZE x
 2 + WRITE_SIZE, MI355X_MICROARCH.md's gfx950 correction), null when no record
-matches.  cpu_baseline: the C oracle (oracle/tmh_oracle.c, "port") on a bounded
-sample of the same workload on this host, rank 0, N = 1: all threads of the
-box's share (<= 16) and one thread.
+matches.
+
+A plain run sets up, warms up, times the K steps, writes its outputs if
+`--dump-outputs DIR` is given, and prints the line.  `--full` adds what takes runs of
+its own: the `alone` batch of the roofline (the dominant kernel with nothing beside
+it, one more batch after the timed region), cpu_baseline (the C oracle,
+oracle/tmh_oracle.c, "port", on a bounded sample of the same workload on this host,
+rank 0, N = 1: all threads of the box's share (<= 16) and one thread) and the
+`secondary` lines (the other configurations, each in a child process).
+
+`--dump-outputs DIR`: what the last timed step computed, as DIR/<name>.npy (float32,
+float64 for fp64 traces and the statistics), at most 64 MB in all.  Trace mode: pv,
+meter and residual of the last batch at a fixed, seeded sample of its seconds
+(`sample_seconds`) and chains (`sample_chains`), and the chains' `status`.  Stats
+mode: the reduced totals of the timed region (hist, energy_*, peak_residual) and the
+last batch's per-chain accumulators (`chain_acc`).  The chains of every step are
+fixed by the arguments (global chain ids, keyed Philox), so two builds run with the
+same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -82,6 +97,49 @@ def valu_busy(rec, ms):
 # C3 1 M chains, C4 16,384 sites, C5 65,536 sites for the node (strong scaling)
 DEFAULT_CHAINS = {"c2": 4096, "c3": 1048576, "c4": 16384, "c5": 65536}
 STRONG = ("c3", "c4", "c5")
+
+# --dump-outputs: at most 64 MB in all.  The sampled arrays share 48 MiB; the chains are
+# sampled above DUMP_MAX_CHAINS, so the index files stay small beside them
+DUMP_SAMPLE_BYTES = 48 << 20
+DUMP_MAX_CHAINS = 65536
+
+
+def sample_index(total, keep, seed):
+    """Sorted indices into range(total): all of them, or a fixed, seeded sample of `keep`."""
+    import numpy as np
+    if keep >= total:
+        return np.arange(total)
+    return np.sort(np.random.default_rng(seed).choice(total, int(keep), replace=False))
+
+
+def dump_outputs(path, pipe, sim, k_last, tot, precision):
+    """--dump-outputs: the arrays a caller of the timed path holds after its last step
+    (batch `k_last`, in its context), as path/<name>.npy.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    cx = pipe.ctx_of(k_last)
+    chains = sample_index(pipe.n, DUMP_MAX_CHAINS, 1)
+    ci = torch.as_tensor(chains, device=pipe.dev)
+    sim.state = cx.state
+    arrays = {"sample_chains": chains.astype(np.float64), "status": sim.status()[chains].astype(np.float32)}
+    if cx.trace:
+        real = np.float64 if precision == "fp64" else np.float32
+        s0 = (pipe.nwin - 1) * pipe.win                    # the trace holds the batch's last window
+        per_array = DUMP_SAMPLE_BYTES // (len(cx.trace) * np.dtype(real).itemsize)
+        seconds = sample_index(pipe.secs - s0, max(1, per_array // len(chains)), 2)
+        si = torch.as_tensor(seconds, device=pipe.dev)
+        arrays["sample_seconds"] = (s0 + seconds).astype(np.float64)
+        for f, t in cx.trace.items():
+            arrays[f] = t.index_select(0, si).index_select(1, ci).cpu().numpy().astype(real, copy=False)
+    else:
+        for k in ("energy_pv", "energy_meter", "energy_residual", "peak_residual"):
+            arrays[k] = np.array([float(tot[k])], dtype=np.float64)
+        arrays["hist"] = tot["hist"].cpu().numpy().astype(np.float64)
+        arrays["chain_acc"] = cx.acc.index_select(1, ci).cpu().numpy().astype(np.float64, copy=False)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def rank_chains(workload, chains, rank, world):
@@ -170,8 +228,16 @@ def parse():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp64"])
     ap.add_argument("--mode", default=None, choices=["trace", "stats"], help="c2: trace, c5: stats")
     ap.add_argument("--start", default=None, help="c2/c5: 2019-09-05 00:00:00, c4: 2019-01-01 00:00:00")
+    ap.add_argument("--full", action="store_true",
+                    help="the full report: beside the headline measurement, the roofline's `alone` batch, the CPU "
+                         "baseline (unless --no-cpu-baseline) and the --secondary configurations; a plain run "
+                         "only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all: a fixed, seeded sample of larger outputs); with N > 1 "
+                         "GPUs rank r writes DIR/rank<r>/")
     ap.add_argument("--cpu-sample-chains", type=int, default=8192)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--path", default="auto", choices=["auto", "sequential", "time_parallel"])
     ap.add_argument("--build-on", default=None, choices=["expand", "walk"],
                     help="stream of each batch's construction, plan and draws: in order on the expansion "
@@ -205,7 +271,7 @@ def parse():
                     help="pipeline streams on hardware queues of their own (dedicated: CU-masked over every CU, "
                          "independent of GPU_MAX_HW_QUEUES) or plain streams sharing HIP's queue pool (shared)")
     ap.add_argument("--secondary", default=None,
-                    help="after the headline measurement (one GPU only), run the other configurations in child "
+                    help="with --full: after the headline measurement (one GPU only), run the other configurations in child "
                          "processes and add their lines under 'secondary': all | none | a comma list of "
                          "c2_fp64,c3,c4,c5 (default: all for the C2 fp32 run with its CPU baseline, else none)")
     ap.add_argument("--timeline", action="store_true",
@@ -252,6 +318,8 @@ def parse():
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 (the timed steps) and --warmup >= 0")
     if a.proxy_world > 1 and (a.gpus > 1 or a.workload not in STRONG):
         ap.error("--proxy-world: a one-GPU proxy of a strong-scaled workload (c3 / c4 / c5)")
     from tmhpvsim_amd.pipeline import pipeline_defaults
@@ -284,7 +352,7 @@ def parse():
     # smaller shards keep the default 16 (the C4 N = 8 shard: 2.50 against 2.46e11 with 8)
     a.walk_lanes = a.walk_lanes or (16 if c5 else (8 if a.workload in ("c3", "c4") and per_gpu > 8192 else 0))
     if a.secondary is None:
-        # the full report (the default C2 run with its CPU baseline) carries them; quick runs do not
+        # the full report (--full: the default C2 run with its CPU baseline) carries them; quick runs do not
         a.secondary = "all" if (a.workload == "c2" and a.precision == "fp32" and not a.no_cpu_baseline) else "none"
     a.cc = a.cc or ("markov" if c5 else "faithful")
     a.hw_queues_given = a.hw_queues is not None   # secondaries pick their own default otherwise
@@ -324,7 +392,7 @@ def secondary_lines(args):
     for name, extra in SECONDARY.items():
         if args.secondary != "all" and name not in args.secondary.split(","):
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--secondary", "none"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--secondary", "none"] + extra
         if getattr(args, "hw_queues_given", False) and "--hw-queues" not in extra:
             cmd += ["--hw-queues", str(args.hw_queues)]
         try:
@@ -512,6 +580,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:   # before anything else runs on the contexts
+        dumped = dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                              pipe, sim, args.warmup + args.steps - 1, tot, args.precision)
     phases = {}
     for name, kk in (("expand", _lib.K_EXPAND), ("segments", _lib.K_SEGMENTS),
                      ("candidates", _lib.K_CANDIDATES), ("tmh_step", _lib.K_STEP)):
@@ -519,15 +591,17 @@ def main():
         # per launch, below made per batch (x windows).  One-window batches: the total over
         # the batches, since the gated schedule's first batch runs as first_split windows
         phases[name] = (ms / cnt if nwin > 1 else ms / args.steps) if cnt else None
-    # the dominant kernel alone: one more batch with nothing beside it (after the timed
+    # --full, the dominant kernel alone: one more batch with nothing beside it (after the timed
     # region, not part of `value`): its duration without the pipelined walks sharing the CUs
-    one_step(args.warmup + args.steps)
-    torch.cuda.synchronize()
-    alone_ms, alone_n = _lib.profile_read(sim._eng, _lib.K_EXPAND)
-    alone_ms = alone_ms / alone_n if alone_n else float("nan")
-    alone_ms *= 1 if nwin == 1 else nwin
-    for kk in (_lib.K_SEGMENTS, _lib.K_CANDIDATES, _lib.K_STEP):
-        _lib.profile_read(sim._eng, kk)
+    alone_ms = None
+    if args.full:
+        one_step(args.warmup + args.steps)
+        torch.cuda.synchronize()
+        alone_ms, alone_n = _lib.profile_read(sim._eng, _lib.K_EXPAND)
+        alone_ms = alone_ms / alone_n if alone_n else float("nan")
+        alone_ms *= 1 if nwin == 1 else nwin
+        for kk in (_lib.K_SEGMENTS, _lib.K_CANDIDATES, _lib.K_STEP):
+            _lib.profile_read(sim._eng, kk)
     bad = pipe.faulted()
     for name in phases:                                    # per batch (all windows)
         if phases[name] is not None:
@@ -566,13 +640,13 @@ def main():
                 "frac": achieved / HBM_PEAK_GBS, "traffic": rec["traffic_bytes_per_launch"] if rec else None,
                 "kernel": "expand_kernel (P2, " + sim.path + ")", "kernel_ms": kmean,
                 "bytes_per_launch": TB * n * secs,
-                # the same launch with no other batch in flight (one extra batch after the timed region)
+                # --full: the same launch with no other batch in flight (one extra batch after the timed region)
                 "alone": {"kernel_ms": alone_ms, "achieved": TB * n * secs / (alone_ms / 1e3) / 1e9,
-                          "frac": TB * n * secs / (alone_ms / 1e3) / 1e9 / HBM_PEAK_GBS},
+                          "frac": TB * n * secs / (alone_ms / 1e3) / 1e9 / HBM_PEAK_GBS} if args.full else None,
                 "valu": valu(kms_launch)}
     else:
         v = valu(kms_launch) or {}
-        va = valu(alone_ms / nwin) or {}   # the same launch with no other batch in flight
+        va = valu(alone_ms / nwin if args.full else None) or {}   # --full: the same launch with no other batch in flight
         agg = rec["valu_insts_per_launch"] * 64 * nwin * args.steps / elapsed / 1e12 if rec else None
         agg_w = valu_busy(rec, elapsed * 1e3 / (args.steps * nwin)).get("busy_frac_weighted") if rec else None
         # `achieved` / `frac`: the expansion lane-ops of the whole timed region over its wall
@@ -586,7 +660,7 @@ def main():
                 "per_launch": {"kernel_ms": kms_launch, "achieved": v.get("achieved"), "frac": v.get("frac"),
                                "busy_frac_weighted": v.get("busy_frac_weighted")},
                 "alone": {"kernel_ms": alone_ms / nwin, "achieved": va.get("achieved"), "frac": va.get("frac"),
-                          "busy_frac_weighted": va.get("busy_frac_weighted")},
+                          "busy_frac_weighted": va.get("busy_frac_weighted")} if args.full else None,
                 "aggregate": ({"achieved": agg, "frac": agg / VALU_PEAK_TLANE, "busy_frac_weighted": agg_w}
                               if rec else None),
                 "kernel": "expand_kernel (P2, " + sim.path + ")", "kernel_ms": kms_launch,
@@ -600,6 +674,7 @@ def main():
         "metric": "simulated chain-seconds/sec (node) at 1/2/4/8 GPUs + % HBM roofline",
         "value": value, "unit": "chain-seconds/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "prewarm_batches": prewarm, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "full": args.full, "dumped_outputs": dumped,
         "scaling": scaling, "vs_baseline": None, "dtype": args.precision, "data": "synthetic (keyed Philox)",
         "config": {"workload": (f"{args.workload.upper()}: {n_node} chains"
                                 + (f" ({n} per GPU)" if scaling == "weak" else f" on {world} GPU(s)")
@@ -656,10 +731,10 @@ def main():
                             "marks_ms": {key: [round(t0ev.elapsed_time(ev[k]), 4) if k in ev else None
                                                for k in range(k0, k0 + args.steps)]
                                          for key, ev in tl.items()}}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args, kw)
     pipe.close()   # drain and release the pipeline's dedicated streams
-    if rank == 0 and world == 1 and args.secondary != "none":
+    if rank == 0 and world == 1 and args.full and args.secondary != "none":
         del pipe, run_batches, one_step   # the children need the memory
         torch.cuda.empty_cache()
         line["secondary"] = secondary_lines(args)

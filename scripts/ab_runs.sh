@@ -9,7 +9,7 @@ TAG=$1; shift
 for spec in "$@"; do
   IFS='|' read -r name lib args <<< "$spec"
   l=$PWD/tmhpvsim_amd/libtmhpvsim.so; [ "$lib" = cur ] || l=$PWD/tmhpvsim_amd/libtmh_$lib.so
-  TMHPVSIM_LIB=$l timeout -k 10 300 python bench.py --no-cpu-baseline --secondary none $args \
+  TMHPVSIM_LIB=$l timeout -k 10 300 python bench.py --full --no-cpu-baseline --secondary none $args \
       > gpurun_out/ab_${TAG}_$name.json 2> gpurun_out/ab_${TAG}_$name.err || { echo "$name failed rc=$?"; tail -3 gpurun_out/ab_${TAG}_$name.err; exit 1; }
   python3 -c "
 import json; d=json.loads(open('gpurun_out/ab_${TAG}_$name.json').read().strip().splitlines()[-1]); r=d['roofline']

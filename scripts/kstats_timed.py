@@ -1,6 +1,6 @@
-"""Mean duration of the dominant kernel over the timed steps of one bench run, from a
-rocprofv3 kernel trace: the launches of KERNEL in start order, the last one being bench.py's
-`alone` batch, the STEPS before it the timed region's (pre-warm and warm-up launches come first).
+"""Mean duration of the dominant kernel over the timed steps of one `bench.py --full` run, from
+a rocprofv3 kernel trace: the launches of KERNEL in start order, the last one being the full
+report's `alone` batch, the STEPS before it the timed region's (pre-warm and warm-up launches come first).
 usage: python scripts/kstats_timed.py kernel_trace.csv STEPS [KERNEL]"""
 import csv
 import sys

@@ -29,7 +29,7 @@ for spec in "$@"; do
   IFS='|' read -r name lib args <<< "$spec"
   l=$PWD/tmhpvsim_amd/libtmhpvsim.so; [ "$lib" = cur ] || l=$PWD/tmhpvsim_amd/libtmh_$lib.so
   out=gpurun_out/ab_${TAG}_$name
-  TMHPVSIM_LIB=$l timeout -k 10 300 python bench.py --no-cpu-baseline --secondary none $args > $out.json 2> $out.err \
+  TMHPVSIM_LIB=$l timeout -k 10 300 python bench.py --full --no-cpu-baseline --secondary none $args > $out.json 2> $out.err \
     || { echo "$name failed rc=$?"; tail -3 $out.err; exit 1; }
   python3 - $out.json $name <<'EOF'
 import json, sys

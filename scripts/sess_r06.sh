@@ -5,27 +5,28 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+RES="${TMH_RESULTS:-bench_out}"   # where the runs' lines and logs go
+mkdir -p "$RES"
 TAG=$1; shift
 for step in "$@"; do
   case "$step" in
     smoke)
-      timeout -k 10 300 python __graft_entry__.py smoke > gpurun_out/smoke_$TAG.log 2>&1 || { echo "smoke failed rc=$?"; tail -5 gpurun_out/smoke_$TAG.log; exit 1; }
-      tail -1 gpurun_out/smoke_$TAG.log ;;
+      timeout -k 10 300 python __graft_entry__.py smoke > $RES/smoke_$TAG.log 2>&1 || { echo "smoke failed rc=$?"; tail -5 $RES/smoke_$TAG.log; exit 1; }
+      tail -1 $RES/smoke_$TAG.log ;;
     tests:*)
       K="${step#tests:}"
-      timeout -k 10 900 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider -rf --durations=10 --timeout 300 --timeout-method thread -k "$K" > gpurun_out/pyt_$TAG.log 2>&1; rc=$?
-      grep -E "PASSED|FAILED|ERROR|passed|failed" gpurun_out/pyt_$TAG.log | tail -25
+      timeout -k 10 900 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider -rf --durations=10 --timeout 300 --timeout-method thread -k "$K" > $RES/pyt_$TAG.log 2>&1; rc=$?
+      grep -E "PASSED|FAILED|ERROR|passed|failed" $RES/pyt_$TAG.log | tail -25
       [ $rc -eq 0 ] || exit $rc ;;
     alltests)
-      timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider -rf --durations=15 --timeout 300 --timeout-method thread > gpurun_out/pytest_all_$TAG.log 2>&1; rc=$?
-      grep -E "FAILED|ERROR|passed|failed" gpurun_out/pytest_all_$TAG.log | tail -15
+      timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider -rf --durations=15 --timeout 300 --timeout-method thread > $RES/pytest_all_$TAG.log 2>&1; rc=$?
+      grep -E "FAILED|ERROR|passed|failed" $RES/pytest_all_$TAG.log | tail -15
       [ $rc -eq 0 ] || exit $rc ;;
     bench:*)
       rest="${step#bench:}"; reps="${rest%%:*}"; extra=""; [ "$rest" != "$reps" ] && extra="${rest#*:}"
       for i in $(seq 1 $reps); do
-        timeout -k 10 400 python bench.py --secondary none --no-cpu-baseline $extra > gpurun_out/bench_${TAG}_$i.json 2> gpurun_out/bench_${TAG}_$i.err || { echo "bench failed"; tail -5 gpurun_out/bench_${TAG}_$i.err; exit 1; }
-        python - "gpurun_out/bench_${TAG}_$i.json" <<'PY'
+        timeout -k 10 400 python bench.py --full --secondary none --no-cpu-baseline $extra > $RES/bench_${TAG}_$i.json 2> $RES/bench_${TAG}_$i.err || { echo "bench failed"; tail -5 $RES/bench_${TAG}_$i.err; exit 1; }
+        python - "$RES/bench_${TAG}_$i.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]
@@ -37,8 +38,8 @@ PY
       rest="${step#ab:}"; reps="${rest%%:*}"; var="${rest#*:}"
       for i in $(seq 1 $reps); do
         for v in 1 0; do
-          env $var=$v timeout -k 10 400 python bench.py --secondary none --no-cpu-baseline > gpurun_out/ab_${TAG}_${v}_$i.json 2> gpurun_out/ab_${TAG}_${v}_$i.err || { echo "bench failed"; tail -5 gpurun_out/ab_${TAG}_${v}_$i.err; exit 1; }
-          python - "gpurun_out/ab_${TAG}_${v}_$i.json" "$var=$v" <<'PY'
+          env $var=$v timeout -k 10 400 python bench.py --full --secondary none --no-cpu-baseline > $RES/ab_${TAG}_${v}_$i.json 2> $RES/ab_${TAG}_${v}_$i.err || { echo "bench failed"; tail -5 $RES/ab_${TAG}_${v}_$i.err; exit 1; }
+          python - "$RES/ab_${TAG}_${v}_$i.json" "$var=$v" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]
@@ -47,9 +48,9 @@ PY
         done
       done ;;
     prof)
-      ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/gpurun_out/prof_$TAG" -o run -- \
-          python3 "$OLDPWD/bench.py" --secondary none --no-cpu-baseline > "$OLDPWD/gpurun_out/prof_$TAG.log" 2>&1 ) || { echo "rocprof failed"; exit 1; }
-      python3 scripts/kstats.py "$(find gpurun_out/prof_$TAG -name "*kernel_stats.csv" -print -quit)" > gpurun_out/kstats_$TAG.txt 2>&1; cat gpurun_out/kstats_$TAG.txt ;;
+      ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$RES/prof_$TAG" -o run -- \
+          python3 "$OLDPWD/bench.py" --full --secondary none --no-cpu-baseline > "$OLDPWD/$RES/prof_$TAG.log" 2>&1 ) || { echo "rocprof failed"; exit 1; }
+      python3 scripts/kstats.py "$(find $RES/prof_$TAG -name "*kernel_stats.csv" -print -quit)" > $RES/kstats_$TAG.txt 2>&1; cat $RES/kstats_$TAG.txt ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done

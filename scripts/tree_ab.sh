@@ -12,7 +12,7 @@ for rep in $(seq 1 "$REPS"); do
   for spec in "$@"; do
     IFS='|' read -r name dir args <<< "$spec"
     out=$ROOT/gpurun_out/tab_${TAG}_${name}_$rep
-    (cd "$dir" && timeout -k 10 300 python bench.py --no-cpu-baseline --secondary none $args > "$out.json" 2> "$out.err") \
+    (cd "$dir" && timeout -k 10 300 python bench.py --full --no-cpu-baseline --secondary none $args > "$out.json" 2> "$out.err") \
       || { echo "$name failed rc=$?"; tail -3 "$out.err"; exit 1; }
     python3 - "$out.json" "$name" <<'EOF'
 import json, sys

@@ -211,3 +211,126 @@ def test_walk_lanes_defaults(monkeypatch):
                        (["--workload", "c3", "--proxy-world", "8"], 8), (["--workload", "c4", "--walk-lanes", "4"], 4)):
         monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
         assert bench.parse().walk_lanes == want, argv
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """`--full` (off by default) carries the roofline's `alone` batch, the CPU baseline and
+    the secondary lines; the secondary children are full runs of their own configuration
+    (their `alone` figure is part of the report) without a CPU baseline or children."""
+    for argv, want in (([], False), (["--full"], True), (["--steps", "3", "--warmup", "1"], False)):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        a = bench.parse()
+        assert a.full is want and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", "somewhere"])
+    assert bench.parse().dump_outputs == "somewhere"
+    import argparse
+    cmds = []
+
+    class R:
+        stdout = "not json"
+
+    monkeypatch.setattr(subprocess, "run", lambda cmd, **k: cmds.append(cmd) or R())
+    bench.secondary_lines(argparse.Namespace(secondary="all", hw_queues=16, hw_queues_given=False))
+    assert len(cmds) == len(bench.SECONDARY)
+    for cmd in cmds:
+        assert "--full" in cmd and "--no-cpu-baseline" in cmd and cmd[cmd.index("--secondary") + 1] == "none"
+
+
+def test_sample_index_is_fixed_by_its_seed():
+    import numpy as np
+    assert np.array_equal(bench.sample_index(7, 7, 1), np.arange(7))
+    assert np.array_equal(bench.sample_index(7, 100, 1), np.arange(7))
+    a, b = bench.sample_index(86400, 1024, 2), bench.sample_index(86400, 1024, 2)
+    assert np.array_equal(a, b) and len(np.unique(a)) == 1024 and np.all(np.diff(a) > 0)
+    assert a.min() >= 0 and a.max() < 86400
+    assert not np.array_equal(a, bench.sample_index(86400, 1024, 3))
+
+
+class _FakePipe:
+    """What dump_outputs reads of a BatchPipeline, on the CPU."""
+
+    def __init__(self, n, secs, win, trace, acc=None):
+        import types
+        self.n, self.secs, self.win, self.nwin, self.dev = n, secs, win, (secs + win - 1) // win, "cpu"
+        self.cx = types.SimpleNamespace(trace=trace, acc=acc, state="state of the last batch")
+        self.asked = []
+
+    def ctx_of(self, k):
+        self.asked.append(k)
+        return self.cx
+
+
+class _FakeSim:
+    def __init__(self, status):
+        self._status, self.state = status, None
+
+    def status(self):
+        assert self.state == "state of the last batch"
+        return self._status
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp64"])
+def test_dump_outputs_trace_sample(tmp_path, monkeypatch, prec):
+    """Trace mode: pv, meter, residual of the last batch at the sampled seconds and chains
+    (a fixed sample: two dumps are identical), in the run's precision, within the budget."""
+    import numpy as np
+    import torch
+    n, secs, win = 37, 250, 100            # three windows: the trace holds the last one (50 s)
+    real = torch.float64 if prec == "fp64" else torch.float32
+    g = torch.Generator().manual_seed(5)
+    trace = {f: torch.rand(win, n, generator=g, dtype=torch.float64).to(real) for f in ("pv", "meter", "residual")}
+    trace["pv"][3, 5] = float("nan")
+    status = np.arange(n, dtype=np.uint32) % 3
+    monkeypatch.setattr(bench, "DUMP_MAX_CHAINS", 16)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 3 * 16 * 20 * (8 if prec == "fp64" else 4))   # 20 of the 50 seconds
+    pipe = _FakePipe(n, secs, win, trace)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), pipe, _FakeSim(status), 9, None, prec)
+    bench.dump_outputs(str(tmp_path / "b"), _FakePipe(n, secs, win, trace), _FakeSim(status), 9, None, prec)
+    assert pipe.asked == [9]
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(got) == {"pv", "meter", "residual", "status", "sample_seconds", "sample_chains"} == set(shapes)
+    assert all(p.suffix == ".npy" for p in (tmp_path / "a").iterdir())
+    chains, seconds = got["sample_chains"].astype(int), got["sample_seconds"].astype(int)
+    assert len(chains) == 16 and len(seconds) == 20 and seconds.min() >= 200 and seconds.max() < 250
+    assert np.array_equal(got["status"], status[chains].astype(np.float32))
+    for f in ("pv", "meter", "residual"):
+        assert got[f].dtype == (np.float64 if prec == "fp64" else np.float32) and list(got[f].shape) == shapes[f] == [20, 16]
+        np.testing.assert_array_equal(got[f], trace[f].numpy()[seconds - 200][:, chains])
+    assert sum(a.nbytes for f, a in got.items() if f in trace) <= bench.DUMP_SAMPLE_BYTES
+    for name, a in got.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a, np.load(tmp_path / "b" / (name + ".npy")))
+
+
+def test_dump_outputs_budget_of_the_benchmarked_sizes():
+    """The sampled arrays of every default workload, and the index files beside them,
+    stay under 64 MB in all."""
+    for n, secs, win, item, arrays in ((4096, 86400, 86400, 4, 3), (4096, 86400, 86400, 8, 3),
+                                       (1048576, 86400, 86400, 8, 4), (65536, 604800, 86400, 8, 4)):
+        chains = min(n, bench.DUMP_MAX_CHAINS)
+        if arrays == 3:
+            rows = min(win, max(1, bench.DUMP_SAMPLE_BYTES // (arrays * item) // chains))
+            total = arrays * rows * chains * item + rows * 8
+        else:
+            total = arrays * chains * 8 + 4096 * 8 + 4 * 8
+        assert total + chains * (8 + 4) <= 64_000_000
+
+
+def test_dump_outputs_stats(tmp_path):
+    """Stats mode: the reduced totals of the timed region and the last batch's per-chain
+    accumulators, as float64."""
+    import numpy as np
+    import torch
+    n = 11
+    acc = torch.arange(4 * n, dtype=torch.float64).reshape(4, n)
+    tot = {"energy_pv": torch.tensor(1.5, dtype=torch.float64), "energy_meter": torch.tensor(2.5, dtype=torch.float64),
+           "energy_residual": torch.tensor(1.0, dtype=torch.float64), "peak_residual": torch.tensor(7.25, dtype=torch.float64),
+           "hist": torch.arange(8, dtype=torch.int64), "energy_fx": torch.zeros(2, 3, dtype=torch.int64)}
+    bench.dump_outputs(str(tmp_path), _FakePipe(n, 300, 100, {}, acc=acc), _FakeSim(np.zeros(n, np.uint32)), 4, tot, "fp32")
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert set(got) == {"energy_pv", "energy_meter", "energy_residual", "peak_residual", "hist", "chain_acc",
+                        "status", "sample_chains"}
+    assert got["peak_residual"].tolist() == [7.25] and got["energy_meter"].tolist() == [2.5]
+    assert got["hist"].dtype == np.float64 and got["hist"].tolist() == list(range(8))
+    np.testing.assert_array_equal(got["chain_acc"], acc.numpy())
+    assert np.array_equal(got["sample_chains"], np.arange(n))
