@@ -140,8 +140,30 @@ typedef struct tmh_stats {
     double* chain_acc;  /* [4][n_chains] sum pv, sum meter, sum residual (W*s), max residual */
 } tmh_stats;
 
+/* Fleet series: exact per-second sums over the chains of a group, accumulated over
+ * calls (caller zero-initialises).  sum: device int64 [n_groups][n_steps][4]; row s of a
+ * group holds, for step step0 + s, over the group's chains that are ok at that step
+ * (live and before their fault):
+ *   [0] sum of q(pv)   [1] sum of q(meter)   [2] n_ok   [3] ok chains with the covered bit
+ * with q(v) = v * 2^TMH_SERIES_FRAC_BITS rounded half to even to an integer, v the engine's
+ * final value (fp32 engines: the fp32 value a trace would hold after the guard-band fixup;
+ * fp64 engines: the fp64 value).  Residual = [1] - [0].  Integer sums: the bits do not
+ * depend on block, wave, window, batch or shard order.  Chain i of a call belongs to
+ * group i / group_chains (0: one group; else a multiple of 512).  A faulted chain's
+ * seconds before its fault count; a chain faulted at construction adds nothing. */
+#define TMH_SERIES_FRAC_BITS 12        /* q in units of 2^-12 W */
+#define TMH_SERIES_MAX_W 16384.0       /* |pv|, |meter| < 2^14 W: 32 lanes x 2^26 fit an int32 partial */
+typedef struct tmh_series {
+    int64_t* sum;
+    int64_t step0;
+    uint32_t n_steps, group_chains, n_groups, reserved;
+} tmh_series;
+
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
+/* TMH_SERIES_FRAC_BITS and TMH_SERIES_MAX_W as the library was built with them */
+int tmh_series_frac_bits(void);
+double tmh_series_max_w(void);
 /* Provenance: "TMHSTAMP:" + the 16-hex-digit hash of the sources and compile flags
  * this library was built from (tmhpvsim_amd/build.py build_stamp; "unstamped" for a
  * build outside it).  The Python loader refuses an in-tree library whose stamp differs
@@ -261,6 +283,25 @@ int tmh_set_shape_tables(struct tmh_engine* eng, const double* shapes, const int
  * launches; sites == NULL restores the engine's single site. */
 int tmh_set_sites(struct tmh_engine* eng, const double* sites, const double* linke, uint32_t n_chains);
 
+/* Fleet series (tmh_series above): every later expansion of this engine adds its
+ * window's rows to series->sum; NULL switches it off.  A setter like the two above;
+ * the struct is copied, the buffer must outlive the launches.  The series is final
+ * after the TMH_EXPAND_COMMIT half (it carries the fixup's corrections), as the
+ * statistics are.  With a series set, a step / expansion call is refused
+ * (TMH_E_INVAL, before any launch) when: a trace pointer is non-NULL (a caller with
+ * traces can sum them); the engine runs the sequential path or injected uniforms;
+ * chain ids are set (compaction: a tile would mix groups); the window is not inside
+ * [step0, step0 + n_steps); n_groups * group_chains < n_chains; group_chains is not
+ * 0 or a multiple of 512 (with 0, n_groups must be 1); inverter Paco or |Pnt| is not
+ * below TMH_SERIES_MAX_W.  Per-chain statistics and the histogram are accumulated
+ * beside the series when tmh_stats gives them. */
+int tmh_set_series(struct tmh_engine* eng, const tmh_series* series);
+/* Tests only: the fp32 guard-band records (chain, block) the last expansion on
+ * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
+ * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
+int64_t tmh_test_guard_records(const struct tmh_engine* eng, const void* scratch, uint32_t n_chains,
+                               uint32_t n_steps);
+
 /* ClearskyindexModel.__init__ for chains [chain0, chain0 + n_chains): the 14+
  * constructor draws and CloudCoverBinary's first cloud.  `inj` may be NULL
  * (keyed mode). */
@@ -355,12 +396,13 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * (tests and measurement: which kernel instantiation produced a line or a trace):
  * TMH_OUT_ANY (any trace fields and/or statistics), TMH_OUT_TRACE3 (exactly pv,
  * meter, residual, no statistics: the trace-mode hot path), TMH_OUT_STATS
- * (statistics only), plus TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in
- * fp64; -1 before the first expansion (and on the sequential path, whose one
+ * (statistics only), TMH_OUT_SERIES (a fleet series, with or without statistics), plus
+ * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
 #define TMH_OUT_TRACE3 1
 #define TMH_OUT_STATS 2
+#define TMH_OUT_SERIES 3
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

@@ -1,0 +1,77 @@
+#!/usr/bin/env python
+"""Cost of the fleet series: TMH_K_EXPAND (tmh_profile_*: HIP events around the expansion
+kernel) of the statistics-only expansion without and with a series, same chains, same
+window, same process, the two alternating.
+
+    python scripts/series_cost.py [--chains 65536] [--steps 86400] [--pairs 5] [--precision fp32]
+                                  [--start "2019-09-05 00:00:00"] [--out FILE.json]
+
+Without a series the run launches the statistics-only instantiation (OUT_STATS), with
+one the series instantiation (OUT_SERIES) with the same statistics beside it; the script
+checks both variants and that the statistics of the two agree bit for bit.  Prints one
+JSON line: the per-run milliseconds, their medians, the ratio and the device's name.
+Needs a GPU (no fallback)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--chains", type=int, default=65536)
+    ap.add_argument("--steps", type=int, default=86400)
+    ap.add_argument("--pairs", type=int, default=5)
+    ap.add_argument("--precision", default="fp32")
+    ap.add_argument("--start", default="2019-09-05 00:00:00")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    from tmhpvsim_amd import _lib
+    from tmhpvsim_amd.engine import BatchedSim
+    from tmhpvsim_amd.params import ModelParams
+    if not torch.cuda.is_available():
+        sys.exit("series_cost.py needs a GPU")
+
+    def one(series):
+        sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=ModelParams(), precision=a.precision,
+                         device="cuda:0", horizon=a.steps)
+        sim.enable_stats()
+        if series:
+            sim.enable_series(a.steps)
+        _lib.check(sim.L.tmh_profile_enable(sim._eng, 1))
+        sim.run(a.steps, trace=(), window=a.steps)
+        torch.cuda.synchronize()
+        ms, launches = _lib.profile_read(sim._eng, _lib.K_EXPAND)
+        want = (_lib.OUT_SERIES if series else _lib.OUT_STATS) | (_lib.OUT_FP64 if a.precision == "fp64" else 0)
+        assert launches == 1 and sim.L.tmh_engine_last_expand(sim._eng) == want, (launches, want)
+        return ms, sim.hist.clone(), sim.chain_acc.clone()
+
+    one(False), one(True)   # warm-up: code objects, allocator
+    t = {False: [], True: []}
+    ref = None
+    for _ in range(a.pairs):
+        for s in (False, True):
+            ms, hist, acc = one(s)
+            t[s].append(ms)
+            if ref is None:
+                ref = (hist, acc)
+            assert torch.equal(hist, ref[0]) and torch.equal(acc.view(torch.int64), ref[1].view(torch.int64))
+    m0, m1 = statistics.median(t[False]), statistics.median(t[True])
+    res = dict(device=torch.cuda.get_device_name(0), chains=a.chains, steps=a.steps, precision=a.precision,
+               start=a.start, stats_only_ms=t[False], with_series_ms=t[True], stats_only_median_ms=m0,
+               with_series_median_ms=m1, ratio=m1 / m0,
+               ns_per_chain_second=[1e6 * m0 / (a.chains * a.steps), 1e6 * m1 / (a.chains * a.steps)],
+               build_stamp=_lib.loaded_stamp())
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

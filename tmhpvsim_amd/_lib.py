@@ -60,17 +60,25 @@ class Stats(C.Structure):
                 ("hi", C.c_double), ("chain_acc", C.c_void_p)]
 
 
+class Series(C.Structure):
+    """tmh_series: int64 [n_groups][n_steps][4] fleet sums from step0 on (tmh_set_series)."""
+    _fields_ = [("sum", C.c_void_p), ("step0", C.c_int64), ("n_steps", C.c_uint32), ("group_chains", C.c_uint32),
+                ("n_groups", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_bytes", "tmh_state_offsets", "tmh_plan_bytes",
            "tmh_scratch_bytes", "tmh_engine_scratch_bytes", "tmh_workspace_bytes", "tmh_engine_create", "tmh_engine_destroy", "tmh_engine_path",
            "tmh_init", "tmh_run", "tmh_plan", "tmh_step", "tmh_probe", "tmh_profile_enable", "tmh_profile_read",
            "tmh_set_shape_tables", "tmh_set_sites", "tmh_walk", "tmh_expand",
            "tmh_walk_part", "tmh_expand_part", "tmh_set_clock", "tmh_test_set_segment_capacity",
            "tmh_set_walk_chains_per_row", "tmh_set_walk_lanes", "tmh_set_chain_ids", "tmh_live_chains", "tmh_state_move",
-           "tmh_stream_create_cus", "tmh_stream_destroy", "tmh_set_walk_order", "tmh_engine_last_expand"]
+           "tmh_stream_create_cus", "tmh_stream_destroy", "tmh_set_walk_order", "tmh_engine_last_expand",
+           "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
 EXPAND_KERNEL, EXPAND_COMMIT, EXPAND_MINUTES, EXPAND_NO_MINUTES = 1, 2, 4, 8
 OUT_ANY, OUT_TRACE3, OUT_STATS, OUT_SITES, OUT_FP64 = 0, 1, 2, 16, 32   # tmh_engine_last_expand
+OUT_SERIES = 3
 
 _lib = None
 
@@ -160,6 +168,12 @@ def load():
     if hasattr(L, "tmh_engine_last_expand"):
         L.tmh_engine_last_expand.argtypes = [p]
         L.tmh_engine_last_expand.restype = C.c_int
+    L.tmh_set_series.argtypes = [p, C.POINTER(Series)]
+    L.tmh_set_series.restype = C.c_int
+    L.tmh_series_frac_bits.restype = C.c_int
+    L.tmh_series_max_w.restype = C.c_double
+    L.tmh_test_guard_records.argtypes = [p, p, u32, u32]
+    L.tmh_test_guard_records.restype = i64
     L.tmh_engine_create.argtypes = [C.POINTER(Params), C.POINTER(Clock), C.c_int, C.POINTER(p)]
     L.tmh_engine_destroy.argtypes = [p]
     if hasattr(L, "tmh_set_clock"):

@@ -9,6 +9,8 @@ tmhpvsim/metersim.py:79-95).
     python -m tmhpvsim_amd.cli metersim [--amqp-url URL] [--exchange NAME] [-v]
                                         [--realtime/--no-realtime]
                                         [--batch N --start T --seconds S --seed K --out FILE]
+    python -m tmhpvsim_amd.cli fleet FILE --batch N --no-realtime [--bin S] [--precision fp32|fp64]
+                                          [--start T --seconds S --seed K]
 
 Without --batch the commands are the reference's AMQP pipelines (a fanout
 exchange carrying one JSON float per second, pvsim.py:43-84, metersim.py:13-62):
@@ -22,6 +24,11 @@ write_file (pvsim.py:72-84: header `time,meter,pv,residual load`, one row per
 second, residual = meter - pv) for chain 0, and optionally every chain's traces
 to an .npz.  `metersim` writes the messages it would publish, one JSON object per
 line: {"timestamp": ..., "body": <json.dumps(meter)>} (metersim.py:38-42).
+`fleet` runs N chains series-only (no per-chain trace leaves the GPU, so N may be
+large) and writes the fleet's means per bin of --bin seconds: header
+`time,n_ok,meter,pv,residual load,covered` -- the bin's start, its ok chain-seconds,
+the mean meter, pv and residual load per ok chain-second (W) and the share of them
+under cloud (tmhpvsim_amd.series).
 There is no CPU fallback: the batch mode fails if the engine cannot run.
 """
 from __future__ import annotations
@@ -52,6 +59,24 @@ def _batch_run(n, start, seconds, seed, precision, fields):
     if bad:
         logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their values are NaN")
     return {k: v.double().cpu().numpy() if v.dtype != torch.uint8 else v.cpu().numpy() for k, v in out.items()}
+
+
+def _fleet_run(n, start, seconds, seed, precision, bin_s):
+    from .engine import BatchedSim
+    from .params import ModelParams
+    import torch
+    if not torch.cuda.is_available():
+        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
+    params = ModelParams(seed=int(seed))
+    sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
+                     horizon=int(seconds))
+    sim.enable_series(int(seconds))
+    sim.run(int(seconds), trace=())
+    out = sim.series(bin_s=int(bin_s), mean=True)
+    bad = int((sim.status() != 0).sum())
+    if bad:
+        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); the means are over the ok chains")
+    return {k: v[0] for k, v in out.items()}
 
 
 def _times(start, seconds):
@@ -134,6 +159,26 @@ def metersim(amqp_url, exchange, verbose, realtime, batch, start, seconds, seed,
                 if m.shape[1] > 1:
                     rec["chain"] = c
                 fh.write(json.dumps(rec) + "\n")
+
+
+@main.command()
+@click.argument("file")
+@common
+@click.option("--precision", type=click.Choice(["fp64", "fp32"]), default="fp32", help="batch mode arithmetic")
+@click.option("--bin", "bin_s", type=click.IntRange(min=1), default=1, help="seconds per output row (a last partial bin is kept)")
+def fleet(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, bin_s):
+    """Fleet means per bin over --batch chains to FILE (CSV; series-only engine run)."""
+    logging.basicConfig(level=logging.WARN - 10 * verbose)
+    _need_batch(realtime, batch, "fleet")
+    out = _fleet_run(batch, start, seconds, seed, precision, bin_s)
+    t0 = dt.datetime.fromisoformat(str(start))
+    with open(file, mode="w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(["time", "n_ok", "meter", "pv", "residual load", "covered"])
+        for i in range(len(out["n_ok"])):
+            w.writerow([t0 + dt.timedelta(seconds=i * bin_s), int(out["n_ok"][i]), float(out["meter"][i]),
+                        float(out["pv"][i]), float(out["residual"][i]), float(out["covered"][i])])
+    click.echo(f"wrote {len(out['n_ok'])} rows to {file}")
 
 
 if __name__ == "__main__":

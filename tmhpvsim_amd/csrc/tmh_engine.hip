@@ -53,7 +53,8 @@
 #include "tmhpvsim.h"
 
 using namespace tmh;
-static_assert(OUT_ANY == TMH_OUT_ANY && OUT_TRACE3 == TMH_OUT_TRACE3 && OUT_STATS == TMH_OUT_STATS,
+static_assert(OUT_ANY == TMH_OUT_ANY && OUT_TRACE3 == TMH_OUT_TRACE3 && OUT_STATS == TMH_OUT_STATS &&
+                  OUT_SERIES == TMH_OUT_SERIES,
               "expansion variants: tmh_model.h and include/tmhpvsim.h agree");
 
 namespace {
@@ -2032,7 +2033,7 @@ constexpr int exp_tile_order()
 template <typename R, int OUT, bool SITES>
 constexpr int exp_wg()
 {
-    return out_base(OUT) == OUT_STATS && !SITES ? TMH_EXP_WG_STATS : 256;
+    return out_no_trace(OUT) && !SITES ? TMH_EXP_WG_STATS : 256;
 }
 // the LDS histogram as 16-bit bin pairs when one tile (WG chains x 128 s) cannot fill a
 // 16-bit bin, else one 32-bit word per bin
@@ -2044,7 +2045,7 @@ constexpr int exp_wg()
 template <typename R, int OUT, bool SITES>
 constexpr int exp_tpw()
 {
-    return out_base(OUT) == OUT_STATS && !SITES ? TMH_STATS_TPW : 1;
+    return out_no_trace(OUT) && !SITES ? TMH_STATS_TPW : 1;
 }
 template <typename R, int OUT, bool SITES>
 constexpr bool exp_hist_pack()
@@ -2080,6 +2081,68 @@ constexpr int exp_waves()
 #endif
     return SITES ? TMH_EXP_WAVES_SITES : (sizeof(R) == 8 ? TMH_EXP_WAVES_F64 : (out_base(OUT) == OUT_TRACE3 ? (TMH_ROW_LDS ? TMH_ROW_LDS_WAVES : TMH_EXP_WAVES_TRACE) : TMH_EXP_WAVES_STATS));
 }
+// The fleet series' workgroup accumulator (OUT_SERIES only; a function-local LDS array,
+// so the other instantiations allocate none): per second of the tile the 64-bit sums of
+// q(pv) and q(meter) and one word holding n_ok (low half) and the covered count (high
+// half; a workgroup has at most 512 chains).  The waves add their half-wave partials
+// with LDS atomics; the tile flushes the rows to the device series (series_flush).
+struct SeriesLds {
+    unsigned long long sum[BLOCK_STEPS][2];
+    uint32_t cnt[BLOCK_STEPS];
+};
+template <bool ON>
+__device__ __forceinline__ SeriesLds* series_lds()
+{
+    if constexpr (ON) {
+        __shared__ SeriesLds s;
+        return &s;
+    } else {
+        return nullptr;
+    }
+}
+// One second's contribution of a wave: pv and meter (q units, 0 on lanes that are not ok)
+// reduced to half-wave sums, which lanes 31 and 63 add to the workgroup's row jb;
+// nok, ncov: the wave's counts (scalars).  PV = false: pv is the literal 0 (night).
+template <bool PV>
+__device__ __forceinline__ void series_add(SeriesLds* sl, uint32_t jb, int qpv, int qm, uint32_t nok, uint32_t ncov)
+{
+    const int sm = half_wave_sum(qm);
+    int sp = 0;
+    if constexpr (PV) sp = half_wave_sum(qpv);
+    if ((threadIdx.x & 31u) == 31u) {
+        if constexpr (PV)
+            __hip_atomic_fetch_add(&sl->sum[jb][0], (unsigned long long)(long long)sp, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&sl->sum[jb][1], (unsigned long long)(long long)sm, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&sl->cnt[jb], (threadIdx.x & 32u) ? (nok | ncov << 16) : 0u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+// The tile's rows [j0, j1) of group g into the device series: rows of 4 int64, consecutive
+// steps contiguous, so the workgroup's atomics cover contiguous bytes.  Leaves the
+// accumulator zeroed for the workgroup's next tile.  Every thread of the workgroup calls it.
+template <int WGT>
+__device__ __forceinline__ void series_flush(SeriesLds* sl, const SeriesView& se, uint32_t g, uint32_t j0, uint32_t j1)
+{
+    __syncthreads();   // the waves' last adds
+    unsigned long long* dst = se.sum + (size_t)g * se.gstride + (size_t)j0 * 4;
+    const uint32_t nv = (j1 - j0) * 4;
+    for (uint32_t i = threadIdx.x; i < nv; i += WGT) {
+        const uint32_t row = i >> 2, col = i & 3u;
+        const uint32_t w = sl->cnt[row];
+        const unsigned long long v = col < 2 ? sl->sum[row][col] : (unsigned long long)(col == 2 ? (w & 0xFFFFu) : (w >> 16));
+        if (v) atomicAdd(dst + i, v);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < BLOCK_STEPS; i += WGT) {
+        sl->sum[i][0] = 0;
+        sl->sum[i][1] = 0;
+        sl->cnt[i] = 0;
+    }
+    __syncthreads();
+}
+
 // One (128-second block b, chain block cblk) tile of the expansion: one work-item per
 // chain of the block (the expansion's unit of work, below).  The LDS staging areas are
 // the kernel's (one column per thread, so consecutive tiles need no barrier between them).
@@ -2093,8 +2156,9 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                             const TraceView& tr, const StatsView& sv, uint32_t* lds_hist,
                                             uint32_t (*cov_lds)[WGT], R (*min_lds)[WGT], uint4* held_lds,
                                             const PV64* pv_lds, const double* pv_lds_tab, float* row_lds,
-                                            const float4* nd_lds)
+                                            const float4* nd_lds, const SeriesView& se, SeriesLds* ser_lds)
 {
+    constexpr bool SER = out_base(OUT) == OUT_SERIES;
     // TMH_ROW_LDS: the tile's fp32 geometry rows copied to LDS once (coalesced vector loads),
     // read back per second with broadcast ds_reads instead of per-second scalar loads
     constexpr bool ROWL = TMH_ROW_LDS && sizeof(R) == 4 && !SITES;
@@ -2278,6 +2342,17 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             else if (held)
                 *hw |= 1u << (jb & 31);
         }
+        if constexpr (SER) {
+            // the second's row of the fleet series: lanes are the chains of one step, so the sums
+            // are wave reductions (integers: order-free) and the counts ballots (scalar; in the
+            // fault-free copy n_ok is loop-invariant).  Lanes that are not ok add 0.
+            const bool okl = ok && live;
+            const uint32_t nok = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(okl));
+            const uint32_t ncov = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(okl && covered));
+            const int qm = okl ? series_q<R>(meter) : 0;
+            if (__builtin_constant_p(pv) && pv == R(0)) series_add<false>(ser_lds, jb, 0, qm, nok, ncov);
+            else series_add<true>(ser_lds, jb, okl ? series_q<R>(pv) : 0, qm, nok, ncov);
+        }
         if constexpr (!FF) {
             csi = ok ? csi : R(NAN);
             pv = ok ? pv : R(NAN);
@@ -2368,7 +2443,9 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const R meter = meter_w<R>(w[q]);
-            finish(j + q, j + q - j0, false, R(0), R(0), meter, meter, false, ff);
+            // (the covered bit is an output of the series only: its count column)
+            const bool covered = SER && ((cov_w >> ((j + q - j0) & 31)) & 1u);
+            finish(j + q, j + q - j0, covered, R(0), R(0), meter, meter, false, ff);
         }
     };
     auto day4 = [&](uint32_t j, const U4& pn, const U4& pm, auto ff) __attribute__((always_inline)) {
@@ -2488,6 +2565,8 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         atomicAdd(fx + 2 * (size_t)n + c, (unsigned long long)llrint(acc.r * sg.fx_scale));
         __hip_atomic_fetch_max(sg.acc_mx + c, max_key(acc.max()), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    if constexpr (SER)   // (group_chains is a multiple of the workgroup's chains: one group per tile)
+        series_flush<WGT>(ser_lds, se, se.group_chains ? cblk * (uint32_t)WGT / se.group_chains : 0u, j0, j1);
 }
 
 
@@ -2495,6 +2574,9 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
 // by 64-bit atomics at the end.  Round 4 measured workgroups looping over several tiles
 // (one flush per workgroup): a persistent grid 8-40 % slower on C3 / C4, four tiles per
 // workgroup 13 % slower on C3 (the inlined tile loop spills 45 VGPRs instead of 4).
+// the expansion's output argument: the traces, or the series for the variant that writes no trace
+template <int OUT>
+using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView, TraceView>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
                                                      uint32_t n, int64_t W0, uint32_t nsteps, int64_t utc0,
@@ -2503,9 +2585,22 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
                                                      const double* __restrict__ sun,
                                                      const int2* __restrict__ events,
                                                      const uint32_t* __restrict__ n_events,
-                                                     const BlockDesc* __restrict__ desc, SegView sg, TraceView tr,
+                                                     const BlockDesc* __restrict__ desc, SegView sg, OutView<OUT> ov,
                                                      StatsView sv, const uint32_t* __restrict__ bperm)
 {
+    // the output view: the traces, or (OUT_SERIES, which writes no trace) the fleet series
+    TraceView tr{};
+    SeriesView se{};
+    if constexpr (out_base(OUT) == OUT_SERIES) se = ov;
+    else tr = ov;
+    SeriesLds* const ser_lds = series_lds<out_base(OUT) == OUT_SERIES>();
+    if constexpr (out_base(OUT) == OUT_SERIES) {
+        for (uint32_t i = threadIdx.x; i < BLOCK_STEPS; i += blockDim.x) {
+            ser_lds->sum[i][0] = 0;
+            ser_lds->sum[i][1] = 0;
+            ser_lds->cnt[i] = 0;
+        }
+    }
     extern __shared__ uint32_t lds_hist[];
     constexpr int WGT = exp_wg<R, OUT, SITES>();   // threads per workgroup
     __shared__ uint32_t cov_lds[4][WGT];
@@ -2537,7 +2632,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     auto tile = [&](uint32_t b, uint32_t cblk) __attribute__((always_inline)) {
         expand_tile<R, OUT, SITES, WGT>(b, cblk, kp, dp, st, chain0, n, W0, nsteps, utc0, tab64, tab32, sun, events,
                                         n_events, desc, sg, tr, sv, lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab,
-                                        row_lds, nd_tab);
+                                        row_lds, nd_tab, se, ser_lds);
     };
     {   // grid: x = time block, y = chain block; XCD-aware tile order (speed only): the
         // hardware deals workgroups round-robin over the 8 XCDs in launch order (x fastest),
@@ -2701,16 +2796,23 @@ constexpr uint32_t FIX_RPW = 16;
 #ifndef TMH_FIX_WAVES_SITES
 #define TMH_FIX_WAVES_SITES 1   // min waves per SIMD of the per-site fixup (its fp64 redo recomputes the site's geometry)
 #endif
-template <bool SITES>
+// SER: the engine has a fleet series (no traces then): column 0 of the second's row gets
+// q(pv fixed) - q(pv32), a two's-complement 64-bit add -- the meter, n_ok and the covered
+// count are final already
+template <bool SITES, bool SER = false>
 __global__ __launch_bounds__(64, (SITES ? TMH_FIX_WAVES_SITES : 1)) void fixup_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0, uint32_t n,
                                                     int64_t W0, uint32_t nsteps, int64_t utc0,
                                                     const double* __restrict__ tab64, const float* __restrict__ tab32,
                                                     const double* __restrict__ sun,
                                                     const int2* __restrict__ events,
                                                     const uint32_t* __restrict__ n_events,
-                                                    const BlockDesc* __restrict__ desc, SegView sg, TraceView tr,
-                                                    StatsView sv)
+                                                    const BlockDesc* __restrict__ desc, SegView sg,
+                                                    std::conditional_t<SER, SeriesView, TraceView> ov, StatsView sv)
 {
+    TraceView tr{};
+    SeriesView se{};
+    if constexpr (SER) se = ov;
+    else tr = ov;
     const uint32_t nrec = min(*sg.nfix, sg.fixcap);
     const int ne = (int)min(*n_events, ev_cap_dev(nsteps));
     const uint32_t lane = threadIdx.x;   // one wave per workgroup
@@ -2751,13 +2853,18 @@ __global__ __launch_bounds__(64, (SITES ? TMH_FIX_WAVES_SITES : 1)) void fixup_k
             const uint32_t cw = (lo & 3) == 0 ? fr.cov.x : ((lo & 3) == 1 ? fr.cov.y : ((lo & 3) == 2 ? fr.cov.z : fr.cov.w));
             const bool covered = (cw >> (i & 31)) & 1u;
             float pv32, meter, pv;
-            if (!redo_second<SITES>(kp, dp, st, sg, n, c, chain0, W0, utc0, j, db, covered, sv.acc != nullptr, events, ne,
+            if (!redo_second<SITES>(kp, dp, st, sg, n, c, chain0, W0, utc0, j, db, covered, SER || sv.acc != nullptr, events, ne,
                                     tab64, tab32, sun, pv32, meter, pv))
                 continue;
             const float res = meter - pv, res32 = meter - pv32;   // second_body's residual
             const size_t o = (size_t)j * tr.ld + c;
             if (tr.pv) reinterpret_cast<float*>(tr.pv)[o] = pv;
             if (tr.residual) reinterpret_cast<float*>(tr.residual)[o] = res;
+            if constexpr (SER) {
+                const long long dq = (long long)series_q<float>(pv) - (long long)series_q<float>(pv32);
+                const uint32_t g = se.group_chains ? c / se.group_chains : 0u;
+                if (dq) atomicAdd(se.sum + (size_t)g * se.gstride + (size_t)j * 4, (unsigned long long)dq);
+            }
             if (sv.acc) {
                 atomicAdd(&sg.corr[c], (double)pv - (double)pv32);
                 atomicAdd(&sg.corr[(size_t)n + c], (double)res - (double)res32);
@@ -3099,6 +3206,8 @@ struct tmh_engine {
     uint32_t walk_lanes = 0;  // lanes per chain in the walk (tmh_set_walk_lanes; 0: by batch size)
     bool walk_order = true;   // walk rows windiest chain first (tmh_set_walk_order)
     int last_expand = -1;     // TMH_OUT_* of the last expansion launched (tmh_engine_last_expand)
+    bool has_series = false;  // tmh_set_series: every expansion adds its window to `series`
+    tmh_series series{};
     // expansion tiles daylight blocks first (env TMH_EXP_COST_ORDER=1, A/B; measured slower in the C2
     // pipeline, round 6: 1.55 against 1.42-1.45 ms per step, same box -- launch order mixes the
     // store-bound night tiles with the VALU-bound day tiles over the launch)
@@ -3492,6 +3601,54 @@ int tmh_set_sites(struct tmh_engine* eng, const double* sites, const double* lin
     return TMH_OK;
 }
 
+int tmh_series_frac_bits(void) { return TMH_SERIES_FRAC_BITS; }
+double tmh_series_max_w(void) { return TMH_SERIES_MAX_W; }
+
+int tmh_set_series(struct tmh_engine* eng, const tmh_series* series)
+{
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (!series) {
+        eng->has_series = false;
+        eng->series = tmh_series{};
+        return TMH_OK;
+    }
+    if (!series->sum || series->n_steps == 0 || series->n_groups == 0)
+        return fail(TMH_E_INVAL, "series needs a buffer, n_steps > 0 and n_groups > 0");
+    if ((uintptr_t)series->sum & 7) return fail(TMH_E_INVAL, "series buffer must be 8-byte aligned");
+    if (series->group_chains % 512 != 0 || (series->group_chains == 0 && series->n_groups != 1))
+        return fail(TMH_E_INVAL, "series group_chains %u (x %u groups): 0 with one group, or a multiple of 512",
+                    series->group_chains, series->n_groups);
+    eng->series = *series;
+    eng->has_series = true;
+    return TMH_OK;
+}
+
+// A step / expansion with a fleet series set: everything the kernels assume, checked
+// on the host before any launch (tmhpvsim.h, tmh_set_series).
+static int check_series(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps, const tmh_trace* trace)
+{
+    const tmh_series& se = eng->series;
+    if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
+        return fail(TMH_E_INVAL, "a fleet series is set: no traces in the same call (a caller with traces can sum them)");
+    if (eng->path != TMH_PATH_TIME_PARALLEL || eng->kp.rng_mode != TMH_RNG_KEYED)
+        return fail(TMH_E_INVAL, "a fleet series needs the time-parallel path (keyed draws, no injected uniforms)");
+    if (eng->kp.ids) return fail(TMH_E_INVAL, "a fleet series cannot run on compacted chains (tmh_set_chain_ids)");
+    if (step0 < se.step0 || step0 + (int64_t)n_steps > se.step0 + (int64_t)se.n_steps)
+        return fail(TMH_E_INVAL, "window [%lld, +%u) outside the series [%lld, +%u)", (long long)step0, n_steps,
+                    (long long)se.step0, se.n_steps);
+    if (se.group_chains % 512 != 0 || (se.group_chains == 0 && se.n_groups != 1))
+        return fail(TMH_E_INVAL, "series group_chains %u: 0 with one group, or a multiple of 512", se.group_chains);
+    if (se.group_chains && (uint64_t)se.n_groups * se.group_chains < n_chains)
+        return fail(TMH_E_INVAL, "series of %u groups x %u chains < n_chains %u", se.n_groups, se.group_chains, n_chains);
+    // the kernels' 32-lane int32 partials: |pv| <= max(Paco, |Pnt|) (fp32 engines: as rounded to fp32)
+    const double paco = eng->kp.inverter[0], pnt = std::fabs(eng->kp.inverter[8]);
+    if (eng->kp.with_pv && !(paco < TMH_SERIES_MAX_W && (double)(float)paco < TMH_SERIES_MAX_W &&
+                             pnt < TMH_SERIES_MAX_W && (double)(float)pnt < TMH_SERIES_MAX_W))
+        return fail(TMH_E_INVAL, "inverter Paco %g W (|Pnt| %g W) not below TMH_SERIES_MAX_W %g W", paco, pnt,
+                    (double)TMH_SERIES_MAX_W);
+    return TMH_OK;
+}
+
 static int check_tables(const tmh_engine* eng, uint32_t n_chains)
 {
     if (eng->kp.ids) n_chains = std::max(n_chains, eng->kp.ids_n);
@@ -3593,6 +3750,18 @@ int tmh_test_set_segment_capacity(uint32_t cap, uint32_t pool_chunks)
     return TMH_OK;
 }
 
+int64_t tmh_test_guard_records(const struct tmh_engine* eng, const void* scratch, uint32_t n_chains, uint32_t n_steps)
+{
+    if (!eng || !scratch || n_chains == 0 || n_steps == 0) return fail(TMH_E_INVAL, "NULL engine/scratch or empty window");
+    if (eng->path != TMH_PATH_TIME_PARALLEL) return fail(TMH_E_INVAL, "guard records: the time-parallel path only");
+    if (int rc = hip_check(hipSetDevice(eng->device), "hipSetDevice")) return rc;
+    SegView sg;
+    scratch_layout(n_chains, n_steps, const_cast<void*>(scratch), &sg, tmh_engine_scratch_rbytes(eng));
+    uint32_t k = 0;
+    if (int rc = hip_check(hipMemcpy(&k, sg.nfix, sizeof k, hipMemcpyDeviceToHost), "guard records copy")) return rc;
+    return (int64_t)k;
+}
+
 int tmh_profile_enable(struct tmh_engine* eng, int on)
 {
     if (!eng) return fail(TMH_E_INVAL, "NULL engine");
@@ -3692,6 +3861,9 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     if (stats && stats->hist && (stats->n_bins == 0 || stats->n_bins > 16384 || !(stats->hi > stats->lo)))
         return fail(TMH_E_INVAL, "bad histogram spec (n_bins %u in [1,16384], hi > lo)", stats->n_bins);
     if (int rc = check_tables(eng, n_chains)) return rc;
+    const bool series = eng->has_series;   // (checked for a walk too: nothing of a refused window is launched)
+    if (series)
+        if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
     const bool tp = eng->path == TMH_PATH_TIME_PARALLEL;
     if (tp && (!scratch || scratch_bytes < tmh_engine_scratch_bytes(eng, n_chains, n_steps)))
         return fail(TMH_E_INVAL, "scratch too small: %zu < %zu", scratch_bytes, tmh_engine_scratch_bytes(eng, n_chains, n_steps));
@@ -3719,6 +3891,10 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
         sv.acc = stats->chain_acc;
         lds = stats->hist ? (size_t)stats->n_bins * 4 : 0;
     }
+    SeriesView sev{};
+    if (series)   // the window's first row of group 0
+        sev = SeriesView{reinterpret_cast<unsigned long long*>(eng->series.sum) + (size_t)(step0 - eng->series.step0) * 4,
+                         (uint64_t)eng->series.n_steps * 4, eng->series.group_chains, 0u};
     hipStream_t s = (hipStream_t)stream;
     const bool f64 = eng->kp.precision == TMH_FP64, keyed = eng->kp.rng_mode == TMH_RNG_KEYED;
     if (!tp) {   // sequential path: one kernel, run by the expand phase
@@ -3806,7 +3982,8 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     if (phases & PH_EXPAND) {
     hipEvent_t t_exp = eng->mark(s);
     const bool no_stats = !sv.hist && !sv.acc;
-    int out = (no_stats && tv.pv && tv.meter && tv.residual && !tv.csi && !tv.covered) ? OUT_TRACE3
+    int out = series ? OUT_SERIES   // (no trace pointers: check_series)
+              : (no_stats && tv.pv && tv.meter && tv.residual && !tv.csi && !tv.covered) ? OUT_TRACE3
                     : (!tv.pv && !tv.meter && !tv.residual && !tv.csi && !tv.covered) ? OUT_STATS
                                                                                       : OUT_ANY;
     const size_t hist_bins = stats && stats->hist ? stats->n_bins : 0;
@@ -3830,7 +4007,22 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     // fp32 kernels and a histogram spec their fp32 binning cannot resolve (StatsView::bin64):
     // the OUT_B64 instantiations bin in fp64 (no per-second branch in the others)
     const bool b64 = !f64 && sv.hist && sv.bin64;
-    if (eng->kp.sites) {   // per-chain sites: statistics only (C5), or any output
+    if (series) {   // the fleet series (+ statistics when given; the histogram bins as hist_bin_rt decides)
+#define LAUNCH_SER(R, S)                                                                                           \
+    hipLaunchKernelGGL((expand_kernel<R, OUT_SERIES | OUT_BRT, S>),                                                \
+                       exp_grid(exp_wg<R, OUT_SERIES, S>(), exp_tpw<R, OUT_SERIES, S>()),                        \
+                       dim3(exp_wg<R, OUT_SERIES, S>()), exp_lds(exp_hist_pack<R, OUT_SERIES, S>()), s, eng->kp,  \
+                       eng->dp, v, chain0, n_chains, step0, n_steps, utc0, pv.tab64, pv.tab32, pv.sun, pv.events,  \
+                       pv.n_events, pv.desc, sg, sev, sv, bperm)
+        if (eng->kp.sites) {
+            if (f64) LAUNCH_SER(double, true);
+            else LAUNCH_SER(float, true);
+        } else {
+            if (f64) LAUNCH_SER(double, false);
+            else LAUNCH_SER(float, false);
+        }
+#undef LAUNCH_SER
+    } else if (eng->kp.sites) {   // per-chain sites: statistics only (C5), or any output
         if (!TMH_SITES_STATS && out == OUT_STATS) out = OUT_ANY;
         if (f64) {
             if (out == OUT_STATS) LAUNCH(double, OUT_STATS, true);
@@ -3855,7 +4047,7 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
         else LAUNCH(float, OUT_ANY, false);
     }
 #undef LAUNCH
-    eng->last_expand = (eng->kp.sites ? ((out == OUT_STATS ? TMH_OUT_STATS : TMH_OUT_ANY) | TMH_OUT_SITES) : out) |
+    eng->last_expand = (eng->kp.sites ? ((out == OUT_SERIES ? TMH_OUT_SERIES : out == OUT_STATS ? TMH_OUT_STATS : TMH_OUT_ANY) | TMH_OUT_SITES) : out) |
                        (f64 ? TMH_OUT_FP64 : 0);
     eng->close(TMH_K_EXPAND, t_exp, s);
     if (int rc = hip_check(hipGetLastError(), "expand_kernel launch")) return rc;
@@ -3868,7 +4060,13 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
         // groups in a row -- 2.0e-3 are recorded, ~1 flagged second each, diagnostic run r05 --
         // and the kernel two redo latencies long.)
         const uint32_t gx = (uint32_t)std::min<uint64_t>(65535, ((uint64_t)sg.fixcap + FIX_RPW - 1) / FIX_RPW);
-        if (eng->kp.sites)
+        if (series && eng->kp.sites)
+            hipLaunchKernelGGL((fixup_kernel<true, true>), dim3(gx), dim3(64), 0, s, eng->kp, eng->dp, v, chain0, n_chains, step0,
+                               n_steps, utc0, pv.tab64, pv.tab32, pv.sun, pv.events, pv.n_events, pv.desc, sg, sev, sv);
+        else if (series)
+            hipLaunchKernelGGL((fixup_kernel<false, true>), dim3(gx), dim3(64), 0, s, eng->kp, eng->dp, v, chain0, n_chains, step0,
+                               n_steps, utc0, pv.tab64, pv.tab32, pv.sun, pv.events, pv.n_events, pv.desc, sg, sev, sv);
+        else if (eng->kp.sites)
             hipLaunchKernelGGL(fixup_kernel<true>, dim3(gx), dim3(64), 0, s, eng->kp, eng->dp, v, chain0, n_chains, step0,
                                n_steps, utc0, pv.tab64, pv.tab32, pv.sun, pv.events, pv.n_events, pv.desc, sg, tv, sv);
         else
@@ -3952,6 +4150,8 @@ int tmh_run(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_cha
     const size_t need = eng->path == TMH_PATH_TIME_PARALLEL ? pb + tmh_engine_scratch_bytes(eng, n_chains, n_steps) : pb;
     if (!workspace || workspace_bytes < need)
         return fail(TMH_E_INVAL, "workspace too small: %zu < %zu", workspace_bytes, need);
+    if (eng->has_series)   // before the plan's launches
+        if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
     if (int rc = tmh_plan(eng, step0, n_steps, workspace, stream)) return rc;
     return tmh_step(eng, state, chain0, n_chains, step0, n_steps, inj, trace, stats, workspace,
                     (char*)workspace + pb, workspace_bytes - pb, stream);

@@ -1571,16 +1571,49 @@ struct Acc {
     __device__ double max() const { return fmax(mx, (double)mxf); }
 };
 
-// output specialisations of the time-parallel expansion (chosen on the host)
-enum : int {
+// output specialisations of the time-parallel expansion (chosen on the host).  A named type:
+// expand_kernel's signature depends on out_base(OUT) == OUT_SERIES, and an unnamed enum's
+// compiler-numbered name in that mangled expression differs between the host and device passes
+enum OutKind : int {
     OUT_ANY = 0,      // any combination of trace fields and statistics
     OUT_TRACE3 = 1,   // exactly pv, meter, residual traces (the trace-mode hot path)
     OUT_STATS = 2,    // statistics only, no trace
+    OUT_SERIES = 3,   // the fleet series (per-second integer sums over the chains), statistics if given, no trace
     // flags on OUT_ANY / OUT_STATS (fp32 kernels): OUT_B64 bins in fp64 (a histogram spec whose
     // fp32 bin position is not accurate enough, StatsView::bin64); OUT_BRT decides at run time
     OUT_B64 = 8, OUT_BRT = 16
 };
 constexpr int out_base(int out) { return out & 7; }
+// no trace: the statistics-only expansion's workgroup shape
+constexpr bool out_no_trace(int out) { return out_base(out) == OUT_STATS || out_base(out) == OUT_SERIES; }
+
+// The fleet series of a window (tmh_series): rows of 4 int64 per step, `sum` at the
+// window's first step of group 0, gstride elements from a group to the next.
+struct SeriesView {
+    unsigned long long* sum;
+    uint64_t gstride;
+    uint32_t group_chains, pad;   // 0: one group
+};
+constexpr int SERIES_FRAC_BITS = TMH_SERIES_FRAC_BITS;
+// q(v): v in units of 2^-SERIES_FRAC_BITS W, rounded half to even (|v| < TMH_SERIES_MAX_W: |q| < 2^26)
+template <typename R>
+__device__ __forceinline__ int series_q(R v)
+{
+    if constexpr (sizeof(R) == 4) return (int)rintf(v * (float)(1 << SERIES_FRAC_BITS));
+    else return (int)rint(v * (double)(1 << SERIES_FRAC_BITS));
+}
+// The sums of v over lanes 0-31 in lane 31 and over lanes 32-63 in lane 63 (other lanes:
+// partial sums).  Four shifted adds scan each row of 16 lanes (zeros shifted in), then
+// rows 1 and 3 add lane 15 of the row before.  32 x 2^26 fits the int32.
+__device__ __forceinline__ int half_wave_sum(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);    // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);    // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);    // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);    // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1, 3
+    return v;
+}
 
 // held: a guard-band second whose pv / residual fixup_kernel replaces; it enters
 // the sums here (fixup_kernel adds the exact difference) but not the maximum or

@@ -121,6 +121,9 @@ class BatchedSim:
         self.hist = None
         self.chain_acc = None
         self._hist_spec = None
+        self.series_raw = None    # int64 [n_groups, n_steps, 4] (enable_series)
+        self._series = None
+        self._last_scratch = None
         with torch.cuda.device(self.device):
             _lib.check(L.tmh_init(self._eng, _ptr(self.state), self.chain0, self.n,
                                   C.byref(self._us) if self._us is not None else None, self._stream()))
@@ -167,6 +170,56 @@ class BatchedSim:
         return _lib.Stats(self.hist.data_ptr() if self.hist is not None else None, n_bins, 0, lo, hi,
                           self.chain_acc.data_ptr())
 
+    # ------------------------------------------------------------------ fleet series
+    def enable_series(self, n_steps, step0=None, group_chains=0, buffer=None):
+        """Accumulate the fleet series (tmhpvsim_amd.series: exact per-second integer sums
+        of pv and meter, n_ok and the covered count over the chains) of steps [step0,
+        step0 + n_steps) in every later run; step0 defaults to the current step.  Chain i
+        belongs to group i // group_chains (0: one group; else a multiple of 512).
+        buffer: an int64 device tensor [n_groups, n_steps, 4] to add into (several sims
+        sharing one series); by default a zeroed one.  Runs with a series take no traces
+        (trace=()) and no compaction; n_steps=None switches the series off."""
+        torch = _torch()
+        if n_steps is None:
+            _lib.check(self.L.tmh_set_series(self._eng, None))
+            self.series_raw, self._series = None, None
+            return None
+        n_steps, gc = int(n_steps), int(group_chains)
+        if n_steps < 1 or gc < 0 or gc % 512:
+            raise ValueError("enable_series: n_steps >= 1, group_chains 0 or a multiple of 512")
+        n_groups = 1 if gc == 0 else -(-self.n // gc)
+        if buffer is None:
+            buffer = torch.zeros(n_groups, n_steps, 4, dtype=torch.int64, device=self.device)
+        elif (buffer.dtype != torch.int64 or buffer.device != self.device or not buffer.is_contiguous()
+              or buffer.dim() != 3 or buffer.shape[0] < n_groups or tuple(buffer.shape[1:]) != (n_steps, 4)):
+            raise ValueError(f"series buffer must be a contiguous int64 [>= {n_groups}, {n_steps}, 4] tensor on {self.device}")
+        st = _lib.Series(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, gc,
+                         int(buffer.shape[0]), 0)
+        _lib.check(self.L.tmh_set_series(self._eng, C.byref(st)))
+        self.series_raw, self._series = buffer, st
+        return buffer
+
+    def series(self, bin_s=1, mean=False):
+        """The series in watts (series.to_watts of series_raw): pv, meter, residual, n_ok and
+        the covered fraction per bin of bin_s seconds, [n_groups, n_bins] each."""
+        from .series import to_watts
+        if self.series_raw is None:
+            raise ValueError("no series: call enable_series first")
+        _torch().cuda.synchronize(self.device)
+        return to_watts(self.series_raw, bin_s=bin_s, mean=mean)
+
+    def guard_records(self):
+        """Tests: the fp32 guard-band records (chain, 128-s block) of the last window that run()
+        issued as a single tmh_run (tmh_test_guard_records; synchronises the device)."""
+        if self._last_scratch is None:
+            raise ValueError("no single-window run yet")
+        ws, off, k = self._last_scratch
+        _torch().cuda.synchronize(self.device)
+        r = self.L.tmh_test_guard_records(self._eng, C.c_void_p(ws.data_ptr() + off), self.n, k)
+        if r < 0:
+            _lib.check(int(r))
+        return int(r)
+
     # ------------------------------------------------------------------ run
     def workspace(self, n_steps):
         """plan + scratch of one window (tmh_engine_scratch_bytes: this engine's precision)"""
@@ -186,6 +239,15 @@ class BatchedSim:
         trace = tuple(trace or ())
         if compact and (trace or self._us is not None):
             raise ValueError("compact=True needs a keyed statistics run (trace=(), no injected uniforms)")
+        if self._series is not None:   # (the library refuses each too, window by window)
+            if compact:
+                raise ValueError("a fleet series cannot run compacted (a compacted tile would mix groups)")
+            if trace:
+                raise ValueError("a fleet series run takes no traces (trace=()): sum the traces instead "
+                                 "(series.from_traces)")
+            s0, sn = self._series.step0, self._series.n_steps
+            if self.step < s0 or self.step + n_steps > s0 + sn:
+                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the series [{s0}, +{sn})")
         if n_steps > ROLL_MAX:   # one rolling clock covers at most ROLL_MAX steps: run in pieces (same bits)
             res = out if out is not None else self._alloc(n_steps, trace)
             done = 0
@@ -223,6 +285,7 @@ class BatchedSim:
                                           C.byref(self._us) if self._us is not None else None,
                                           C.byref(tr), C.byref(st) if st is not None else None,
                                           _ptr(ws), ws.numel(), self._stream()))
+                self._last_scratch = (ws, int(self.L.tmh_plan_bytes(k)), k)
                 done += k
         self.step += n_steps
         return res
