@@ -29,9 +29,14 @@ class OrcParams(C.Structure):
 
 
 def build(force=False):
-    if force or not os.path.exists(LIB_PATH) or \
-            os.path.getmtime(LIB_PATH) < os.path.getmtime(os.path.join(HERE, "tmh_oracle.c")):
-        subprocess.run(["make", "-s", "-C", HERE], check=True)
+    # under a lock: several processes may come here at once (the spawned ranks of
+    # tests/test_dist_cpu.py), and a second make, or a load, must not meet a half-written library
+    import fcntl
+    with open(os.path.join(HERE, ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if force or not os.path.exists(LIB_PATH) or \
+                os.path.getmtime(LIB_PATH) < os.path.getmtime(os.path.join(HERE, "tmh_oracle.c")):
+            subprocess.run(["make", "-s", "-C", HERE], check=True)
     return LIB_PATH
 
 

@@ -47,6 +47,25 @@ def test_abi_version_and_layout():
     assert L.tmh_scratch_bytes(1 << 20, 86400) < 70_000 * (1 << 20)
 
 
+# (n_chains, n_steps) -> tmh_state_bytes, tmh_plan_bytes, tmh_scratch_bytes.  The literals were
+# read from the library built from commit 22f039e, the parent of the layout-helper refactor:
+# they pin field order, alignment and sizes of state_layout, plan_layout and scratch_layout.
+# (1000, 129) is two 128-s blocks, (16384, 2592000) the C4 window.
+PINNED_BYTES = {
+    (1, 1): (13824, 1792, 70656),
+    (1000, 129): (8351744, 49920, 1331712),
+    (4096, 86400): (34193408, 32511744, 155575808),
+    (16384, 2592000): (136773632, 975327488, 18079670784),
+}
+
+
+@pytest.mark.parametrize("shape", sorted(PINNED_BYTES))
+def test_buffer_sizes_pinned(shape):
+    L = _lib.load()
+    n, steps = shape
+    assert (L.tmh_state_bytes(n), L.tmh_plan_bytes(steps), L.tmh_scratch_bytes(n, steps)) == PINNED_BYTES[shape]
+
+
 def test_engine_create_validates_before_touching_device():
     L = _lib.load()
     ck = _lib.Clock()

@@ -35,13 +35,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-
-// min waves per SIMD of the construction kernels (init, variates, geometry, boundary draws), i.e.
-// their VGPR bound: beside the expansion (72-VGPR waves) a wave that needs more registers than
-// one expansion wave frees waits for several to retire (A/B builds)
-#ifndef TMH_BUILD_WAVES
-#define TMH_BUILD_WAVES 4   // geom_kernel 146 -> 128 VGPRs (38 spilled): C2 +0.9 % over three pairs, round 6
-#endif
 #include <cstring>
 #include <string>
 #include <type_traits>
@@ -61,6 +54,26 @@ namespace {
 
 constexpr int BLOCK_STEPS = 128;   // seconds per P2 work-item
 static_assert(BLOCK_STEPS <= 128, "FixRec holds a 128-bit mask of a block's seconds");
+
+// ---- occupancy and shape constants (tuning results, each measured on the same box)
+// min waves per SIMD of the construction kernels (init, variates, geometry, boundary draws), i.e.
+// their VGPR bound: beside the expansion (72-VGPR waves) a wave that needs more registers than
+// one expansion wave frees waits for several to retire
+constexpr int BUILD_WAVES = 4;   // geom_kernel 146 -> 128 VGPRs (38 spilled): C2 +0.9 % over three pairs, round 6
+// statistics workgroups of 512 chains (C3 / C4): one histogram flush per 65,536
+// chain-seconds instead of 32,768 (32-bit LDS bins, 16 KB); round 4, same box: C4
+// 2.41 -> 2.51e11 chain-s/s, C3 2.87e11 either way (its expansion 240 -> 235 ms alone)
+constexpr int EXP_WG_STATS = 512;
+// min waves per SIMD (__launch_bounds__) of each expansion instantiation (exp_waves):
+//  fp32 single-site trace (C2): 7 = at most 72 VGPRs (alone -4 % vs 6, no VGPR spills);
+//  fp32 statistics / other outputs (C3, C4): 6 = 80 VGPRs (the 16-bit-pair LDS histogram,
+//    8 KB, + 12 KB staging: 8 workgroups per CU; +6 % over 5 waves);
+//  fp64 single-site: 4 = at most 128 VGPRs (the trace kernel takes 110, no VGPR spills since the
+//    round-4 PV-constant and table changes; 5 waves = 96 VGPRs spill 14 and run 6 % slower, round 5);
+//  per-chain sites (C5): 3 = at most 168 VGPRs (12-18 spilled): C5 5.36 against 4.47e10 at 2 (206 VGPRs,
+//    round 6, same box) and 4.37e10 at 4 (79 spilled); 2 was 35 % faster than 1 (round 2)
+constexpr int EXP_WAVES_TRACE = 7, EXP_WAVES_STATS = 6, EXP_WAVES_F64 = 4, EXP_WAVES_SITES = 3;
+constexpr int FIX_WAVES_SITES = 1;   // min waves per SIMD of the per-site fixup (its fp64 redo recomputes the site's geometry)
 
 struct BlockDesc {                 // as of the step before the block start; -1 = none in the window
     int32_t q0, q1;                // minute-draw indices of the last two minute boundaries
@@ -213,7 +226,7 @@ __device__ __forceinline__ void init_cc_pair(const KParams& kp, uint32_t c, cons
     a = draw_cc(kp, gid(kp.ids, c), ch, u[1]);
 }
 
-__global__ __launch_bounds__(256, TMH_BUILD_WAVES) void init_variates_kernel(KParams kp, StateView st, uint64_t chain0, uint32_t n,
+__global__ __launch_bounds__(256, BUILD_WAVES) void init_variates_kernel(KParams kp, StateView st, uint64_t chain0, uint32_t n,
                                                             double hf)
 {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -244,7 +257,7 @@ __global__ __launch_bounds__(256, TMH_BUILD_WAVES) void init_variates_kernel(KPa
 
 // ClearskyindexModel.__init__ (clearskyindexmodel.py:57-99)
 template <int RNG>
-__global__ __launch_bounds__(256, TMH_BUILD_WAVES) void init_kernel(KParams kp, StateView st, uint64_t chain0, uint32_t n,
+__global__ __launch_bounds__(256, BUILD_WAVES) void init_kernel(KParams kp, StateView st, uint64_t chain0, uint32_t n,
                                                    double hf, InjView inj)
 {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -336,7 +349,7 @@ __global__ __launch_bounds__(256, TMH_BUILD_WAVES) void init_kernel(KParams kp, 
 }
 
 // ------------------------------------------------------------ plan kernels
-__global__ __launch_bounds__(256, TMH_BUILD_WAVES) void geom_kernel(GParams gp, int64_t step0, uint32_t n, double* tab64,
+__global__ __launch_bounds__(256, BUILD_WAVES) void geom_kernel(GParams gp, int64_t step0, uint32_t n, double* tab64,
                                                    float* tab32, double* sun)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -618,7 +631,7 @@ __device__ __forceinline__ int first_t_bin(const KParams& kp, uint32_t c, double
 // chains, 3.13 -> 4.14e10 live chain-s/s); a full C5 batch (65,536) computes the quantile in the
 // walk, only for the hours whose state sits in the t bin (precomputed: 5.36 -> 4.96e10).  mk_pre:
 // this launch precomputes (markov_cc_kernel's tb = -1 otherwise).
-__global__ __launch_bounds__(256, TMH_BUILD_WAVES) void event_draws_kernel(DrawParams dp, KParams kp, bool mk_pre, uint64_t chain0,
+__global__ __launch_bounds__(256, BUILD_WAVES) void event_draws_kernel(DrawParams dp, KParams kp, bool mk_pre, uint64_t chain0,
                                                           uint32_t n, uint32_t nsteps, const int2* __restrict__ events,
                                                           const uint32_t* __restrict__ n_events, double* evd,
                                                           uint32_t* identity_order, uint32_t* identity_rank)
@@ -1463,23 +1476,15 @@ constexpr int WALK_REG = 64;   // sigma entries held in VGPRs per chain (entries
 // against 2.96e11; a latency-bound batch (C4's 16,384 chains, 2 waves per SIMD) keeps the
 // unspilled walk (the TP walk: C4 3.01 against 3.09e11).
 // (a 4-lane TP walk, 16 entries at 3 or 4 waves per SIMD: C3 2.90 / 2.72e11, round 6)
-// the 16-lane walk (latency-bound batches: C2, C5) -- A/B builds: its register entries and minimum
-// waves per SIMD (its VGPRs decide how many expansion waves fit beside two walk waves)
-#ifndef TMH_WALK16_REG
-#define TMH_WALK16_REG WALK_REG
-#endif
-#ifndef TMH_WALK16_WAVES
-#define TMH_WALK16_WAVES 1
-#endif
 template <int G, bool TP>
 constexpr int walk_reg()
 {
-    return TP ? 32 : (G == 16 ? TMH_WALK16_REG : WALK_REG);
+    return TP ? 32 : WALK_REG;
 }
 template <int G, bool TP>
 constexpr int walk_waves()
 {
-    return TP ? 4 : (G == 16 ? TMH_WALK16_WAVES : 1);
+    return TP ? 4 : 1;
 }
 constexpr int WALK_FIX = 16;   // entries scanned unconditionally (one chunk at G = 16); the rest only when some chain of the wave needs them
 static_assert(WALK_FIX >= 12, "reset_sigma writes up to 11 entries into the unconditional chunks");
@@ -1524,9 +1529,6 @@ __global__ __launch_bounds__(256, (walk_waves<G, TP>())) void segments_kernel(Dr
                                                           PrevView prev)
 {
     static_assert(G == 4 || G == 8 || G == 16, "lanes per chain");
-#ifdef TMH_WALK_SETPRIO
-    __builtin_amdgcn_s_setprio(TMH_WALK_SETPRIO);   // A/B builds: the walk's waves issue first on their SIMD
-#endif
     constexpr int NCH = walk_reg<G, TP>() / G;                     // register chunks
     constexpr int NFIX = (WALK_FIX + G - 1) / G < NCH ? (WALK_FIX + G - 1) / G : NCH;
     static_assert(NCH * G == walk_reg<G, TP>() && NCH * G >= 12, "register entries: a multiple of G, >= 12 (reset_sigma)");
@@ -1999,87 +2001,30 @@ __device__ __forceinline__ void row_store(__amdgpu_buffer_rsrc_t rs, uint32_t of
 // sampler pairs and does no fp64 work in fp32 mode.
 // 256-thread workgroups: one-wave workgroups (so the SIMDs take expansion waves
 // independently of a walk wave's footprint) measured +5 % alone, no gain beside the walks
-// statistics workgroups of 512 chains (C3 / C4): one histogram flush per 65,536
-// chain-seconds instead of 32,768 (32-bit LDS bins, 16 KB); round 4, same box: C4
-// 2.41 -> 2.51e11 chain-s/s, C3 2.87e11 either way (its expansion 240 -> 235 ms alone)
-#ifndef TMH_EXP_WG_STATS
-#define TMH_EXP_WG_STATS 512
-#endif
-#ifndef TMH_HELD_OR
-#define TMH_HELD_OR 0   // fp32 expansion: the guard-band bit as an unconditional LDS or (A/B builds; DESIGN round 6)
-#endif
-#ifndef TMH_DISC_LDS
-#define TMH_DISC_LDS 0   // fp32 single-site expansion: DISC's coefficient sets from an LDS table (disc_row; A/B builds)
-#endif
-#ifndef TMH_ROW_LDS
-#define TMH_ROW_LDS 0   // fp32 single-site expansion: the tile's geometry rows staged in LDS (A/B builds)
-#endif
-#ifndef TMH_ROW_LDS_WAVES
-#define TMH_ROW_LDS_WAVES 6
-#endif
-// expand_kernel's tile order: 0 launch order, 1 / 2 XCD-aware (below).  Order 1 for the
+// expand_kernel's tile order: 0 launch order, 1 XCD-aware (below).  Order 1 for the
 // per-site kernels (C5: 4.20 against 3.995e10 live chain-s/s, same box), launch order for
-// the rest (C2: order 1 2.17 against 2.39e11); TMH_EXP_TILE_ORDER sets one order for every
-// instantiation (A/B builds).
+// the rest (C2: order 1 2.17 against 2.39e11).
 template <typename R, int OUT, bool SITES>
 constexpr int exp_tile_order()
 {
-#ifdef TMH_EXP_TILE_ORDER
-    return TMH_EXP_TILE_ORDER;
-#else
     return SITES ? 1 : 0;
-#endif
 }
 template <typename R, int OUT, bool SITES>
 constexpr int exp_wg()
 {
-    return out_no_trace(OUT) && !SITES ? TMH_EXP_WG_STATS : 256;
+    return out_no_trace(OUT) && !SITES ? EXP_WG_STATS : 256;
 }
 // the LDS histogram as 16-bit bin pairs when one tile (WG chains x 128 s) cannot fill a
 // 16-bit bin, else one 32-bit word per bin
-// time blocks per workgroup: the statistics-only single-site expansion (C3, C4) may loop over
-// TMH_STATS_TPW consecutive blocks, one histogram flush for all of them (A/B builds)
-#ifndef TMH_STATS_TPW
-#define TMH_STATS_TPW 1
-#endif
-template <typename R, int OUT, bool SITES>
-constexpr int exp_tpw()
-{
-    return out_no_trace(OUT) && !SITES ? TMH_STATS_TPW : 1;
-}
 template <typename R, int OUT, bool SITES>
 constexpr bool exp_hist_pack()
 {
-    return exp_wg<R, OUT, SITES>() * BLOCK_STEPS * exp_tpw<R, OUT, SITES>() <= 32768;
+    return exp_wg<R, OUT, SITES>() * BLOCK_STEPS <= 32768;
 }
-#ifndef TMH_PVF_VGPR
-#define TMH_PVF_VGPR 0
-#endif
-constexpr int PVF_VGPR = TMH_PVF_VGPR;   // leading PVF fields pinned in VGPRs in the fp32 single-site expansion
-#ifndef TMH_EXP_WAVES_TRACE
-#define TMH_EXP_WAVES_TRACE 7
-#endif
-// min waves per SIMD (__launch_bounds__) of each expansion instantiation:
-//  fp32 single-site trace (C2): 7 = at most 72 VGPRs (alone -4 % vs 6, no VGPR spills);
-//  fp32 statistics / other outputs (C3, C4): 6 = 80 VGPRs (the 16-bit-pair LDS histogram,
-//    8 KB, + 12 KB staging: 8 workgroups per CU; +6 % over 5 waves);
-//  fp64 single-site: 4 = at most 128 VGPRs (the trace kernel takes 110, no VGPR spills since the
-//    round-4 PV-constant and table changes; 5 waves = 96 VGPRs spill 14 and run 6 % slower, round 5);
-//  per-chain sites (C5): 3 = at most 168 VGPRs (12-18 spilled): C5 5.36 against 4.47e10 at 2 (206 VGPRs,
-//    round 6, same box) and 4.37e10 at 4 (79 spilled); 2 was 35 % faster than 1 (round 2)
 template <typename R, int OUT, bool SITES>
 constexpr int exp_waves()
 {
-#ifndef TMH_EXP_WAVES_F64
-#define TMH_EXP_WAVES_F64 4
-#endif
-#ifndef TMH_EXP_WAVES_STATS
-#define TMH_EXP_WAVES_STATS 6
-#endif
-#ifndef TMH_EXP_WAVES_SITES
-#define TMH_EXP_WAVES_SITES 3
-#endif
-    return SITES ? TMH_EXP_WAVES_SITES : (sizeof(R) == 8 ? TMH_EXP_WAVES_F64 : (out_base(OUT) == OUT_TRACE3 ? (TMH_ROW_LDS ? TMH_ROW_LDS_WAVES : TMH_EXP_WAVES_TRACE) : TMH_EXP_WAVES_STATS));
+    return SITES ? EXP_WAVES_SITES : (sizeof(R) == 8 ? EXP_WAVES_F64 : (out_base(OUT) == OUT_TRACE3 ? EXP_WAVES_TRACE : EXP_WAVES_STATS));
 }
 // The fleet series' workgroup accumulator (OUT_SERIES only; a function-local LDS array,
 // so the other instantiations allocate none): per second of the tile the 64-bit sums of
@@ -2155,29 +2100,16 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                             const BlockDesc* __restrict__ desc, const SegView& sg,
                                             const TraceView& tr, const StatsView& sv, uint32_t* lds_hist,
                                             uint32_t (*cov_lds)[WGT], R (*min_lds)[WGT], uint4* held_lds,
-                                            const PV64* pv_lds, const double* pv_lds_tab, float* row_lds,
+                                            const PV64* pv_lds, const double* pv_lds_tab,
                                             const float4* nd_lds, const SeriesView& se, SeriesLds* ser_lds)
 {
     constexpr bool SER = out_base(OUT) == OUT_SERIES;
-    // TMH_ROW_LDS: the tile's fp32 geometry rows copied to LDS once (coalesced vector loads),
-    // read back per second with broadcast ds_reads instead of per-second scalar loads
-    constexpr bool ROWL = TMH_ROW_LDS && sizeof(R) == 4 && !SITES;
-    // fp32: DISC's coefficient sets from the LDS table after the quantile's (the single-site
-    // second bodies; TMH_DISC_LDS=0 builds the constant-coefficient branches instead, for A/B)
-    const float4* disc_lds = sizeof(R) == 4 && TMH_DISC_LDS ? nd_lds + ND32_N : nullptr;
     const uint32_t c = cblk * blockDim.x + threadIdx.x;
     const bool live = c < n;
     const uint32_t j0 = b * BLOCK_STEPS, j1 = min(j0 + (uint32_t)BLOCK_STEPS, nsteps);
     const uint64_t chain = chain0 + gid(kp.ids, c);
     const int64_t fm = first_minute(utc0, W0);
-    // the fp32 PV constants as per-lane registers (VGPRs): held in SGPRs across
-    // the loop they are spilled to VGPR lanes and read back by v_readlane each step
-    PVF pkv = kp.pvf;
-    if constexpr (sizeof(R) == 4 && !SITES) {
-        float* f = reinterpret_cast<float*>(&pkv);
-#pragma unroll
-        for (int i = 0; i < PVF_VGPR; ++i) asm volatile("v_mov_b32 %0, %1" : "=v"(f[i]) : "s"(f[i]));
-    }
+    PVF pkv = kp.pvf;   // the tile's own copy of the fp32 PV constants
     Acc acc{0.0, 0.0, 0.0, -INFINITY};
     bool alive = false;
     int32_t fault = INT_MAX;
@@ -2261,12 +2193,6 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     constexpr int RW = sizeof(R) == 8 ? ROW : ROW32;   // geometry row: wave-uniform, scalar loads
     const R* rowp = (sizeof(R) == 8 ? reinterpret_cast<const R*>(tab64) : reinterpret_cast<const R*>(tab32)) +
                     (size_t)j0 * RW;
-    if constexpr (ROWL) {
-        const uint32_t nw = (j1 - j0) * ROW32;
-        const float* src = tab32 + (size_t)j0 * ROW32;
-        for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) row_lds[i] = src[i];
-        __syncthreads();
-    }
     __amdgpu_buffer_rsrc_t rs_pv, rs_m, rs_r;
     // the lane's byte offset in a trace row (lanes past the last chain at 2^31: outside the
     // resource's range, so their stores are dropped without an exec mask); the row's offset
@@ -2334,13 +2260,9 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         const bool ok = FF || (int32_t)j < fault_eff;
         held = held && ok && live;   // lanes past the last chain run on uninitialised samplers: never held
         if constexpr (sizeof(R) == 4) {
-            // jb is wave-uniform: the word and the bit are scalars.  TMH_HELD_OR: every lane ors
-            // its bit or 0 into its word (one ds_or, no exec-mask branch around a rare store)
+            // jb is wave-uniform: the word and the bit are scalars
             uint32_t* hw = reinterpret_cast<uint32_t*>(&held_lds[threadIdx.x]) + (jb >> 5);
-            if constexpr (TMH_HELD_OR)
-                __hip_atomic_fetch_or(hw, held ? 1u << (jb & 31) : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            else if (held)
-                *hw |= 1u << (jb & 31);
+            if (held) *hw |= 1u << (jb & 31);
         }
         if constexpr (SER) {
             // the second's row of the fleet series: lanes are the chains of one step, so the sums
@@ -2372,18 +2294,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     };
     auto second = [&](uint32_t j, uint32_t un, uint32_t um, auto ff) __attribute__((always_inline)) {
         R row[row_w<R>()];
-        uint32_t fl;
-        if constexpr (ROWL) {
-            const float* lr = row_lds + (j - j0) * ROW32;
 #pragma unroll
-            for (int i = 0; i < ROW32; ++i) row[i] = lr[i];
-            fl = __builtin_amdgcn_readfirstlane(__float_as_uint(row[G_FLAGS + G32]));
-        } else {
-#pragma unroll
-            for (int i = 0; i < row_w<R>(); ++i) row[i] = rowp[i];
-            rowp += RW;
-            fl = sizeof(R) == 8 ? (uint32_t)(double)rowp[G_FLAGS - RW] : __float_as_uint(row[G_FLAGS + G32]);
-        }
+        for (int i = 0; i < row_w<R>(); ++i) row[i] = rowp[i];
+        rowp += RW;
+        const uint32_t fl = sizeof(R) == 8 ? (uint32_t)(double)rowp[G_FLAGS - RW] : __float_as_uint(row[G_FLAGS + G32]);
         apply_events(j, fl);
         const uint32_t jb = j - j0;   // wave-uniform
         if ((jb & 31) == 0) cov_w = cov_lds[jb >> 5][threadIdx.x];
@@ -2415,8 +2329,8 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 second_body<R>(kp, pkv, row, flp, fs, covered, ndtri64(un, (LdsD*)pv_lds_tab), meter_w<R>(um), csi, pv,
                                meter, res, held, p, (LdsD*)pv_lds_tab);
             } else {
-                second_body<R, !SITES && !ROWL>(kp, pkv, row, flp, fs, covered, noise_lds<R>(un, nd_lds), meter_w<R>(um),
-                                                csi, pv, meter, res, held, nullptr, nullptr, disc_lds);
+                second_body<R, !SITES>(kp, pkv, row, flp, fs, covered, noise_lds<R>(un, nd_lds), meter_w<R>(um), csi, pv,
+                                       meter, res, held);
             }
         }
         finish(j, jb, covered, csi, pv, meter, res, held, ff);
@@ -2428,7 +2342,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // a group's first second).  Such a group applies its first second's events once and runs
     // four straight-line seconds with no flag tests; a night second is its meter alone (no
     // row loads).  Other groups (sunrise, sunset, DISC's zenith limit) take the per-second path.
-    constexpr bool FASTG = !SITES && !ROWL && out_base(OUT) != OUT_ANY;
+    constexpr bool FASTG = !SITES && out_base(OUT) != OUT_ANY;
     // TMH_ISA_MARKS (analysis builds only, scripts/isa_loop.py --groups): comment markers around
     // the four-second group bodies, so the listing's instructions per group can be counted
 #ifdef TMH_ISA_MARKS
@@ -2468,7 +2382,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                meter_w<R>(wm[q]), csi, pv, meter, res, held, p, (LdsD*)pv_lds_tab);
             } else {
                 second_body<R, true>(kp, pkv, row, FL_DISCOK, fs, covered, noise_lds<R>(wn[q], nd_lds),
-                                     meter_w<R>(wm[q]), csi, pv, meter, res, held, nullptr, nullptr, disc_lds);
+                                     meter_w<R>(wm[q]), csi, pv, meter, res, held);
             }
             finish(j + q, jb, covered, csi, pv, meter, res, held, ff);
         }
@@ -2513,16 +2427,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 bool need = out_base(OUT) == OUT_ANY || !kp.with_pv || (SITES && wave_day);
                 if (!need && !SITES) {   // any daylight second among the four (scalar loads of their flags)
                     uint32_t nf = FL_NIGHT;
-                    if constexpr (ROWL) {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) nf &= __float_as_uint(row_lds[(j - j0 + q) * ROW32 + G_FLAGS + G32]);
-                        nf = __builtin_amdgcn_readfirstlane(nf);
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            nf &= sizeof(R) == 8 ? (uint32_t)(double)rowp[q * RW + G_FLAGS]
-                                                 : __float_as_uint((float)rowp[q * RW + G_FLAGS + G32]);
-                    }
+                    for (int q = 0; q < 4; ++q)
+                        nf &= sizeof(R) == 8 ? (uint32_t)(double)rowp[q * RW + G_FLAGS]
+                                             : __float_as_uint((float)rowp[q * RW + G_FLAGS + G32]);
                     need = nf == 0;
                 }
                 U4 pn{0u, 0u, 0u, 0u};
@@ -2542,10 +2450,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     };
     // (fp32 single-site only: in the fp64 and per-site kernels, which sit at their
     // register bounds, the second copy adds spills)
-#ifndef TMH_EXP_FF_F64
-#define TMH_EXP_FF_F64 0   // the fault-free loop copy for the fp64 single-site kernels too (A/B builds)
-#endif
-    if ((sizeof(R) == 4 || (TMH_EXP_FF_F64 && out_base(OUT) == OUT_TRACE3)) && !SITES && wave_ok) loops(std::true_type{});
+    if (sizeof(R) == 4 && !SITES && wave_ok) loops(std::true_type{});
     else loops(std::false_type{});
     if constexpr (sizeof(R) == 4) {
         const uint4 hm = held_lds[threadIdx.x];
@@ -2609,19 +2514,14 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     // fp64: the PV constants; fp64 and per-chain sites: the log / exp table (one copy per workgroup)
     __shared__ PV64 pv_lds[1];   // (176 + 16 bytes in the fp32 kernels: unused)
     __shared__ __attribute__((aligned(16))) double pv_tab[sizeof(R) == 8 || SITES ? PV_TAB : 2];
-    __shared__ __attribute__((aligned(16))) float row_lds[TMH_ROW_LDS && sizeof(R) == 4 && !SITES ? BLOCK_STEPS * ROW32 : 1];
     // fp32: the noise quantile's table (ndtri_t), 8 KB, copied once per workgroup
-    // (with TMH_DISC_LDS, DISC's coefficient sets after it: disc_row)
-    __shared__ float4 nd_tab[sizeof(R) == 4 ? ND32_N + (TMH_DISC_LDS ? DISC_TAB : 0) : 1];
+    __shared__ float4 nd_tab[sizeof(R) == 4 ? ND32_N : 1];
     if constexpr (sizeof(R) == 8 || SITES) {
         if (threadIdx.x < PV64_N) reinterpret_cast<double*>(pv_lds)[threadIdx.x] = reinterpret_cast<const double*>(&kp.pv64)[threadIdx.x];
         for (uint32_t i = threadIdx.x; i < PV_TAB; i += blockDim.x) pv_tab[i] = g_pv_tab[i];
     }
     if constexpr (sizeof(R) == 4)
-    {
         for (uint32_t i = threadIdx.x; i < ND32_N; i += blockDim.x) nd_tab[i] = g_nd32_tab[i];
-        if (TMH_DISC_LDS && threadIdx.x < DISC_TAB) nd_tab[ND32_N + threadIdx.x] = disc_row(threadIdx.x);
-    }
     __syncthreads();
     constexpr bool PACK = exp_hist_pack<R, OUT, SITES>();
     const uint32_t nw = PACK ? (sv.n_bins + 1) / 2 : sv.n_bins;   // 16-bit bin pairs, or bins
@@ -2632,69 +2532,42 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     auto tile = [&](uint32_t b, uint32_t cblk) __attribute__((always_inline)) {
         expand_tile<R, OUT, SITES, WGT>(b, cblk, kp, dp, st, chain0, n, W0, nsteps, utc0, tab64, tab32, sun, events,
                                         n_events, desc, sg, tr, sv, lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab,
-                                        row_lds, nd_tab, se, ser_lds);
+                                        nd_tab, se, ser_lds);
     };
-    {   // grid: x = time block, y = chain block; XCD-aware tile order (speed only): the
-        // hardware deals workgroups round-robin over the 8 XCDs in launch order (x fastest),
-        // so workgroup L runs on XCD L % 8.  XCD x takes the x-th contiguous range of tiles in
-        // the order (time block m of a stride-8 permutation of the blocks, chain block): its
-        // workgroups then read the geometry rows (scalar loads) of ~every 8th 128-s block
-        // only, 1/8 of the window's rows (C2 fp32: 0.95 of 7.6 MB) in its 4 MB L2, each time
-        // block by all its chain blocks in a row, and every XCD still gets an even share of
-        // day and night blocks.  Bijections for any grid: XCD x has q + (x < r) workgroups
-        // (N = 8 q + r), and the permutation lists the blocks b = x mod 8 for x = 0..7.
-        const uint32_t T = gridDim.x, CB = gridDim.y, N = T * CB;
-        const uint32_t L = blockIdx.x + T * blockIdx.y, x = L & 7u, q = N >> 3, r = N & 7u;
-        const uint32_t k = x * q + min(x, r) + (L >> 3);
-        const uint32_t m = k / CB, qt = T >> 3, rt = T & 7u, big = rt * (qt + 1);
-        const uint32_t xm = m < big ? m / (qt + 1) : rt + (m - big) / max(qt, 1u);
-        const uint32_t b = xm + 8u * (m - (xm * qt + min(xm, rt)));
-        constexpr int ORD = exp_tile_order<R, OUT, SITES>();
-        uint32_t bs, cs;
-        if constexpr (ORD == 0) {   // launch order
-            bs = blockIdx.x;
-            cs = blockIdx.y;
-            (void)b;
-            if (exp_tpw<R, OUT, SITES>() == 1 && bperm) {
-                // cost order (round 6): the tiles in chunks of TCH blocks of the plan's order
-                // (daylight blocks first), each chunk's tiles chain block by chain block, time
-                // block fastest -- so concurrent workgroups still write different trace rows, as
-                // in launch order, but the day tiles are all dealt before the night ones
-                constexpr uint32_t TCH = 16;
-                const uint32_t per = TCH * CB, ch = L / per, rr = L - ch * per;
-                const uint32_t cc = min(TCH, T - ch * TCH), y = rr / cc;
-                bs = bperm[ch * TCH + (rr - y * cc)];
-                cs = y;
-            }
-        } else if constexpr (ORD == 2) {
-            // order 2: the tiles listed class by class (time blocks b = x mod 8), chain block major
-            // inside a class (consecutive workgroups of an XCD: different time blocks, as in launch
-            // order, so the trace rows written at a time spread over the HBM channels); XCD x's
-            // contiguous range of that list is (nearly) class x: 1/8 of the rows per L2
-            const uint32_t kbig = big * CB;   // tiles of the rt classes with qt + 1 blocks
-            const uint32_t x2 = k < kbig ? k / (CB * (qt + 1)) : rt + (k - kbig) / max(CB * qt, 1u);
-            const uint32_t cum = x2 <= rt ? x2 * CB * (qt + 1) : kbig + (x2 - rt) * CB * qt;
-            const uint32_t nbx = qt + (x2 < rt ? 1u : 0u), i2 = k - cum;
-            bs = __builtin_amdgcn_readfirstlane(x2 + 8u * (i2 % nbx));
-            cs = __builtin_amdgcn_readfirstlane(i2 / nbx);
-            (void)b;
-        } else {
+    {   // grid: x = time block, y = chain block; the workgroup's tile (bs, cs)
+        const uint32_t T = gridDim.x, CB = gridDim.y, L = blockIdx.x + T * blockIdx.y;
+        uint32_t bs = blockIdx.x, cs = blockIdx.y;   // launch order
+        if constexpr (exp_tile_order<R, OUT, SITES>() == 1) {
+            // XCD-aware tile order (speed only): the
+            // hardware deals workgroups round-robin over the 8 XCDs in launch order (x fastest),
+            // so workgroup L runs on XCD L % 8.  XCD x takes the x-th contiguous range of tiles in
+            // the order (time block m of a stride-8 permutation of the blocks, chain block): its
+            // workgroups then read the geometry rows (scalar loads) of ~every 8th 128-s block
+            // only, 1/8 of the window's rows (C2 fp32: 0.95 of 7.6 MB) in its 4 MB L2, each time
+            // block by all its chain blocks in a row, and every XCD still gets an even share of
+            // day and night blocks.  Bijections for any grid: XCD x has q + (x < r) workgroups
+            // (N = 8 q + r), and the permutation lists the blocks b = x mod 8 for x = 0..7.
+            const uint32_t N = T * CB, x = L & 7u, q = N >> 3, r = N & 7u;
+            const uint32_t k = x * q + min(x, r) + (L >> 3);
+            const uint32_t m = k / CB, qt = T >> 3, rt = T & 7u, big = rt * (qt + 1);
+            const uint32_t xm = m < big ? m / (qt + 1) : rt + (m - big) / max(qt, 1u);
+            const uint32_t b = xm + 8u * (m - (xm * qt + min(xm, rt)));
             // (uniform, but computed by VALU integer division: readfirstlane keeps them in SGPRs, so
             // the row pointer and the tile's block loads stay scalar)
             bs = __builtin_amdgcn_readfirstlane(b);
             cs = __builtin_amdgcn_readfirstlane(k % CB);
+        } else if (bperm) {
+            // cost order (round 6): the tiles in chunks of TCH blocks of the plan's order
+            // (daylight blocks first), each chunk's tiles chain block by chain block, time
+            // block fastest -- so concurrent workgroups still write different trace rows, as
+            // in launch order, but the day tiles are all dealt before the night ones
+            constexpr uint32_t TCH = 16;
+            const uint32_t per = TCH * CB, ch = L / per, rr = L - ch * per;
+            const uint32_t cc = min(TCH, T - ch * TCH), y = rr / cc;
+            bs = bperm[ch * TCH + (rr - y * cc)];
+            cs = y;
         }
-        constexpr int TPW = exp_tpw<R, OUT, SITES>();
-        if constexpr (TPW == 1) tile(bs, cs);
-        else {   // time blocks bs TPW .. bs TPW + TPW - 1 (x counts super-blocks of TPW blocks)
-            for (int t = 0; t < TPW; ++t) {
-                // laundered per tile: nothing of a tile is hoisted out of the loop and held in
-                // registers across it (the per-chain loads are repeated instead)
-                uint32_t bb = bs * TPW + t, cc = cs;
-                asm volatile("" : "+s"(bb), "+s"(cc));
-                if (bb < sg.nblk) tile(bb, cc);
-            }
-        }
+        tile(bs, cs);
     }
     if (sv.hist) {
         __syncthreads();
@@ -2793,14 +2666,11 @@ __global__ __launch_bounds__(256) void state_move_kernel(StateView src, StateVie
 // (record, second) a work-item: ~1 flagged second in 20 per wave, 95 us per C2 batch.)
 // Grid-stride over the record groups.
 constexpr uint32_t FIX_RPW = 16;
-#ifndef TMH_FIX_WAVES_SITES
-#define TMH_FIX_WAVES_SITES 1   // min waves per SIMD of the per-site fixup (its fp64 redo recomputes the site's geometry)
-#endif
 // SER: the engine has a fleet series (no traces then): column 0 of the second's row gets
 // q(pv fixed) - q(pv32), a two's-complement 64-bit add -- the meter, n_ok and the covered
 // count are final already
 template <bool SITES, bool SER = false>
-__global__ __launch_bounds__(64, (SITES ? TMH_FIX_WAVES_SITES : 1)) void fixup_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0, uint32_t n,
+__global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0, uint32_t n,
                                                     int64_t W0, uint32_t nsteps, int64_t utc0,
                                                     const double* __restrict__ tab64, const float* __restrict__ tab32,
                                                     const double* __restrict__ sun,
@@ -3082,25 +2952,31 @@ struct PlanView {
     uint32_t* bperm;   // [nblk]: the 128-s blocks, daylight blocks first (block_order_kernel)
 };
 
+// Carves 256-byte-aligned fields out of a buffer, in call order; base == nullptr only counts.
+struct Carver {
+    char* base;
+    size_t o = 0;
+    template <typename T>
+    void take(T*& field, size_t bytes)
+    {
+        if (base) field = (T*)(base + o);
+        o += align_up(bytes);
+    }
+};
+
 size_t plan_layout(uint32_t n_steps, void* base, PlanView* v)
 {
-    size_t o = 0;
-    char* b = (char*)base;
-    if (v) v->tab64 = (double*)(b + o);
-    o += align_up((size_t)n_steps * ROW * 8);
-    if (v) v->tab32 = (float*)(b + o);
-    o += align_up((size_t)n_steps * ROW32 * 4);
-    if (v) v->events = (int2*)(b + o);
-    o += align_up((size_t)ev_cap(n_steps) * 8);
-    if (v) v->n_events = (uint32_t*)(b + o);
-    o += ALIGN;
-    if (v) v->desc = (BlockDesc*)(b + o);
-    o += align_up((size_t)(nblk_of(n_steps) + 1) * sizeof(BlockDesc));
-    if (v) v->sun = (double*)(b + o);
-    o += align_up((size_t)n_steps * SUN_W * 8);
-    if (v) v->bperm = (uint32_t*)(b + o);
-    o += align_up((size_t)nblk_of(n_steps) * 4);
-    return o;
+    PlanView none{};
+    PlanView& p = v ? *v : none;
+    Carver c{v ? (char*)base : nullptr};
+    c.take(p.tab64, (size_t)n_steps * ROW * 8);
+    c.take(p.tab32, (size_t)n_steps * ROW32 * 4);
+    c.take(p.events, (size_t)ev_cap(n_steps) * 8);
+    c.take(p.n_events, 4);
+    c.take(p.desc, (size_t)(nblk_of(n_steps) + 1) * sizeof(BlockDesc));
+    c.take(p.sun, (size_t)n_steps * SUN_W * 8);
+    c.take(p.bperm, (size_t)nblk_of(n_steps) * 4);
+    return c.o;
 }
 
 // segment records (one per call + the window-start one): 656 a day, a multiple of 16,
@@ -3116,79 +2992,58 @@ uint32_t fix_cap(uint32_t n, uint32_t n_steps) { return (uint32_t)((uint64_t)n *
 // rbytes: bytes per minute-table entry, the engine's real (4 in fp32 mode, 8 in fp64)
 size_t scratch_layout(uint32_t n, uint32_t n_steps, void* base, SegView* v, size_t rbytes)
 {
-    size_t o = 0;
-    char* b = (char*)base;
-    const uint32_t nblk = nblk_of(n_steps);
+    SegView none{};
+    SegView& g = v ? *v : none;
+    Carver c{v ? (char*)base : nullptr};
+    g.cap = seg_cap(n_steps);
+    g.nblk = nblk_of(n_steps);
+    g.pool_cap = pool_chunks(n);
+    g.evcap = ev_cap(n_steps);
+    g.kcap = cand_cap(n_steps);
+    g.nmin = n_steps / 60 + 2;
+    g.fixcap = fix_cap(n, n_steps);
+    c.take(g.rec, (size_t)n * g.cap * 8);
+    c.take(g.ovf, (size_t)n * OVF_SLOTS * 4);
+    c.take(g.pool, (size_t)g.pool_cap * OVF_CHUNK * 8);
+    c.take(g.pool_n, 3 * 4);   // pool_n | walk_q | pool_short
     if (v) {
-        v->cap = seg_cap(n_steps);
-        v->nblk = nblk;
-        v->rec = (int2*)(b + o);
+        g.walk_q = g.pool_n + 1;
+        g.pool_short = g.pool_n + 2;
     }
-    o += align_up((size_t)n * seg_cap(n_steps) * 8);
-    if (v) {
-        v->ovf = (int32_t*)(b + o);
-        v->pool_cap = pool_chunks(n);
-    }
-    o += align_up((size_t)n * OVF_SLOTS * 4);
-    if (v) v->pool = (int2*)(b + o);
-    o += align_up((size_t)pool_chunks(n) * OVF_CHUNK * 8);
-    if (v) {
-        v->pool_n = (uint32_t*)(b + o);
-        v->walk_q = v->pool_n + 1;
-        v->pool_short = v->pool_n + 2;
-    }
-    o += ALIGN;
-    if (v) v->order = (uint32_t*)(b + o);
-    o += align_up((size_t)n * 4);
-    if (v) v->rank = (uint32_t*)(b + o);
-    o += align_up((size_t)n * 4);
-    if (v) v->ovf_first = (int32_t*)(b + o);
-    o += align_up((size_t)n * 4);
-    if (v) v->count = (uint32_t*)(b + o);
-    o += align_up((size_t)n * 4);
-    if (v) v->fault = (int32_t*)(b + o);
-    o += align_up((size_t)n * 4);
-    if (v) v->status = (uint32_t*)(b + o);
-    o += align_up((size_t)n * 4);
-    if (v) v->end_p1 = (double*)(b + o);
-    o += align_up((size_t)n * 4 * 8);
-    const uint32_t evc = ev_cap(n_steps);
-    if (v) {
-        v->evcap = evc;
-        v->evd = (double*)(b + o);
-    }
-    o += align_up((size_t)n * evc * 4 * 8);
-    const uint32_t kc = cand_cap(n_steps);
-    if (v) {
-        v->kcap = kc;
-        v->cand = (double*)(b + o);
-    }
-    o += align_up((size_t)n * kc * 8);
-    const uint32_t nmin = n_steps / 60 + 2;
-    if (v) {
-        v->nmin = nmin;
-        v->mtab = (void*)(b + o);
-    }
-    o += align_up((size_t)n * nmin * 2 * rbytes);
-    if (v) v->mend = (double*)(b + o);
-    o += align_up((size_t)n * 4 * 8);
-    const uint32_t fc = fix_cap(n, n_steps);
-    if (v) {
-        v->fixcap = fc;
-        v->fix = (FixRec*)(b + o);
-    }
-    o += align_up((size_t)fc * sizeof(FixRec));
-    if (v) v->nfix = (uint32_t*)(b + o);   // nfix | corr[2][n] | acc_fx | acc_mx: reset before each expansion
-    o += ALIGN;
-    if (v) v->corr = (double*)(b + o);
-    o += align_up((size_t)n * 2 * 8);
-    if (v) v->acc_fx = (long long*)(b + o);
-    o += align_up((size_t)n * 3 * 8);
-    if (v) v->acc_mx = (long long*)(b + o);
-    o += align_up((size_t)n * 8);
-    if (v) v->brec = (uint32_t*)(b + o);
-    o += align_up((size_t)nblk * n * 4);
-    return o;
+    c.take(g.order, (size_t)n * 4);
+    c.take(g.rank, (size_t)n * 4);
+    c.take(g.ovf_first, (size_t)n * 4);
+    c.take(g.count, (size_t)n * 4);
+    c.take(g.fault, (size_t)n * 4);
+    c.take(g.status, (size_t)n * 4);
+    c.take(g.end_p1, (size_t)n * 4 * 8);
+    c.take(g.evd, (size_t)n * g.evcap * 4 * 8);
+    c.take(g.cand, (size_t)n * g.kcap * 8);
+    c.take(g.mtab, (size_t)n * g.nmin * 2 * rbytes);
+    c.take(g.mend, (size_t)n * 4 * 8);
+    c.take(g.fix, (size_t)g.fixcap * sizeof(FixRec));
+    c.take(g.nfix, 4);   // nfix | corr[2][n] | acc_fx | acc_mx: reset before each expansion
+    c.take(g.corr, (size_t)n * 2 * 8);
+    c.take(g.acc_fx, (size_t)n * 3 * 8);
+    c.take(g.acc_mx, (size_t)n * 8);
+    c.take(g.brec, (size_t)g.nblk * n * 4);
+    return c.o;
+}
+
+// A launch's runtime choices as template arguments: with_value<Vs...>(v, f) calls
+// f(std::integral_constant<int, V>{}) for the V among Vs that equals v, with_real(f64, f) calls
+// f(double{}) or f(float{}).  The launchers name only the combinations the library uses (an
+// `if constexpr` where a combination does not exist), so no other kernel is instantiated.
+template <int... Vs, typename F>
+void with_value(int v, F&& f)
+{
+    (void)(... || (v == Vs && (f(std::integral_constant<int, Vs>{}), true)));
+}
+template <typename F>
+void with_real(bool f64, F&& f)
+{
+    if (f64) f(double{});
+    else f(float{});
 }
 
 }  // namespace
@@ -3807,12 +3662,10 @@ int tmh_init(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_ch
     dim3 grid((n_chains + 255) / 256), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (eng->kp.rng_mode == TMH_RNG_KEYED)
-    {
         hipLaunchKernelGGL(init_variates_kernel, dim3(grid.x, 10), block, 0, s, eng->kp, v, chain0, n_chains, hf);
-        hipLaunchKernelGGL(init_kernel<TMH_RNG_KEYED>, grid, block, 0, s, eng->kp, v, chain0, n_chains, hf, iv);
-    }
-    else
-        hipLaunchKernelGGL(init_kernel<TMH_RNG_INJECTED>, grid, block, 0, s, eng->kp, v, chain0, n_chains, hf, iv);
+    with_value<TMH_RNG_KEYED, TMH_RNG_INJECTED>(eng->kp.rng_mode, [&](auto rng) {
+        hipLaunchKernelGGL(init_kernel<decltype(rng)::value>, grid, block, 0, s, eng->kp, v, chain0, n_chains, hf, iv);
+    });
     return hip_check(hipGetLastError(), "init_kernel launch");
 }
 
@@ -3840,8 +3693,181 @@ int tmh_plan(struct tmh_engine* eng, int64_t step0, uint32_t n_steps, void* plan
     return hip_check(hipGetLastError(), "plan kernels launch");
 }
 
-enum { PH_DRAWS = 1, PH_SEGMENTS = 4, PH_WALK = PH_DRAWS | PH_SEGMENTS, PH_EXPAND = 2, PH_COMMIT = 8, PH_ALL = 15,
-       PH_MINUTES = 16, PH_NO_MINUTES = 32 };
+enum { PH_DRAWS = 1, PH_SEGMENTS = 4, PH_WALK = PH_DRAWS | PH_SEGMENTS, PH_EXPAND = 2, PH_COMMIT = 8, PH_ALL = 15 };
+
+// What the phases of one step share (step_phases validates the call and fills it in)
+struct StepCtx {
+    tmh_engine* eng;
+    hipStream_t s;
+    uint64_t chain0;
+    uint32_t n_chains;
+    int64_t step0;
+    uint32_t n_steps;
+    PrevView prev;
+    StateView v;
+    PlanView pv;
+    SegView sg;   // time-parallel path only
+    InjView iv;
+    TraceView tv;
+    StatsView sv;
+    SeriesView sev;
+    bool f64() const { return eng->kp.precision == TMH_FP64; }
+    bool series() const { return eng->has_series; }
+    uint32_t cb() const { return (n_chains + 255) / 256; }   // 256-chain blocks
+    int64_t utc0() const { return eng->gp.clock.utc0; }
+};
+
+// event, hour and minute draws, the walk rows' order and the try-0 candidates
+static int phase_draws(const StepCtx& c)
+{
+    tmh_engine* const eng = c.eng;
+    hipStream_t s = c.s;
+    const dim3 cbs(c.cb()), t256(256);
+    // the walk rows' order, read by the candidate table's layout and by the walk: computed
+    // here (tmh_set_walk_order before a window's draws), so the walk uses the order its
+    // window's draws were made with whatever the engine's flag says when it runs
+    const bool mk_pre = eng->dp.markov && c.n_chains <= eng->mk_pre_max;
+    hipLaunchKernelGGL(event_draws_kernel, dim3(c.sg.evcap, c.cb()), t256, 0, s, eng->dp, eng->kp, mk_pre, c.chain0,
+                       c.n_chains, c.n_steps, c.pv.events, c.pv.n_events, c.sg.evd,
+                       eng->walk_order ? nullptr : c.sg.order, eng->walk_order ? nullptr : c.sg.rank);
+    if (eng->dp.markov)
+        hipLaunchKernelGGL(markov_cc_kernel, cbs, t256, 0, s, eng->kp, mk_pre, c.v, c.chain0, c.n_chains, c.n_steps,
+                           c.pv.events, c.pv.n_events, c.sg.evd, c.prev);
+    if (eng->walk_order) {
+        const uint32_t tiles = (c.n_chains + ORDER_TILE - 1) / ORDER_TILE;
+        if (tiles <= WALK_RANK_TILES)   // small batches (latency-bound on the construction stream): the rank sort
+            hipLaunchKernelGGL(walk_rank_kernel, dim3(tiles * (ORDER_TILE / ORDER_EPB)), t256, 0, s, c.v, c.n_chains,
+                               c.sg, c.prev);
+        else
+            hipLaunchKernelGGL(walk_order_kernel, dim3(tiles), dim3(1024), 0, s, c.v, c.n_chains, c.sg, c.prev);
+    }
+    hipEvent_t t_cand = eng->mark(s);
+    {   // candidates + the window's minute draws (+ counter resets), one launch
+        const int64_t fmh = first_minute_host(c.utc0(), c.step0);
+        const uint32_t nm = fmh < (int64_t)c.n_steps ? (uint32_t)((c.n_steps - 1 - fmh) / 60 + 1) : 0;
+        const uint32_t ny = c.sg.kcap + nm;   // rows; the kernel strides over y past 65,535 (long windows)
+        const dim3 grid(c.cb(), std::min(ny, 65535u));
+        const BlockDesc* de = c.pv.desc + nblk_of(c.n_steps);
+        with_real(c.f64(), [&](auto r) {
+            hipLaunchKernelGGL(draws_tail_kernel<decltype(r)>, grid, t256, 0, s, eng->dp, c.v, c.chain0, c.n_chains,
+                               c.step0, c.n_steps, fmh, ny, c.pv.tab64, c.pv.events, c.pv.n_events, de, c.sg, c.prev);
+        });
+    }
+    eng->close(TMH_K_CANDIDATES, t_cand, s);
+    return hip_check(hipGetLastError(), "draws kernels launch");
+}
+
+// the segment walk, the overflow settlement and the blocks' start records
+static int phase_segments(const StepCtx& c)
+{
+    tmh_engine* const eng = c.eng;
+    hipStream_t s = c.s;
+    hipEvent_t t_seg = eng->mark(s);
+    // groups of walk_lanes lanes, 16 per workgroup (16 G threads, 16 x WALK_CAND candidate slots in LDS)
+    const uint32_t rows = (uint32_t)(((uint64_t)c.n_chains + eng->walk_cpr - 1) / eng->walk_cpr);
+    const uint32_t G = eng->walk_lanes ? eng->walk_lanes : (c.n_chains > WALK_AUTO_SMALL ? 4u : 16u);
+    const uint32_t gpw = 16;   // groups (chains) per workgroup
+    const dim3 wg((rows + gpw - 1) / gpw), wt(gpw * G);
+    const size_t wlds = gpw * WALK_CAND * sizeof(double);
+    const bool q = rows < c.n_chains;   // groups take queued chains
+    // 0 plain, 1 queued, 2 the throughput variant (8 lanes, no queue)
+    const int mode = q ? 1 : (G == 8 && rows >= eng->walk_tp_rows) ? 2 : 0;
+    with_value<4, 8, 16>((int)G, [&](auto lanes) {
+        with_value<0, 1, 2>(mode, [&](auto m) {
+            constexpr int GG = decltype(lanes)::value, M = decltype(m)::value;
+            constexpr bool Q = M == 1, TP = M == 2;
+            if constexpr (!TP || GG == 8)
+                hipLaunchKernelGGL((segments_kernel<Q, GG, TP>), wg, wt, wlds, s, eng->dp, c.v, c.chain0, c.n_chains,
+                                   c.step0, c.n_steps, eng->gp.clock, c.pv.events, c.pv.n_events, c.sg, c.prev);
+        });
+    });
+    hipLaunchKernelGGL(overflow_settle_kernel, dim3(c.cb()), dim3(256), 0, s, c.n_chains, c.sg);
+    hipLaunchKernelGGL(block_rec_kernel, dim3(c.cb(), (c.sg.nblk + BREC_G - 1) / BREC_G), dim3(256), 0, s, c.n_chains,
+                       c.step0, c.sg);
+    eng->close(TMH_K_SEGMENTS, t_seg, s);
+    return hip_check(hipGetLastError(), "segments kernel launch");
+}
+
+// the expansion: one instantiation per (precision, output kind, per-chain sites)
+static int phase_expand(const StepCtx& c)
+{
+    tmh_engine* const eng = c.eng;
+    const TraceView& tv = c.tv;
+    const StatsView& sv = c.sv;
+    hipEvent_t t_exp = eng->mark(c.s);
+    const bool f64 = c.f64(), sites = eng->kp.sites != nullptr, no_stats = !sv.hist && !sv.acc;
+    int out = c.series() ? OUT_SERIES   // (no trace pointers: check_series)
+              : (no_stats && tv.pv && tv.meter && tv.residual && !tv.csi && !tv.covered) ? OUT_TRACE3
+                    : (!tv.pv && !tv.meter && !tv.residual && !tv.csi && !tv.covered) ? OUT_STATS
+                                                                                      : OUT_ANY;
+    if (out == OUT_TRACE3 && tv.ld * (f64 ? 8u : 4u) * BLOCK_STEPS >= (1ull << 31))   // one block's rows: one buffer range
+        return fail(TMH_E_INVAL, "trace ld %llu too large (a 128-step block of rows must stay under 2 GiB)",
+                    (unsigned long long)tv.ld);
+    if (sites && out == OUT_TRACE3) out = OUT_ANY;   // per-chain sites: statistics only (C5), or any output
+    // x = time blocks, y = chain blocks; LDS: the histogram (16-bit bin pairs or bins)
+    auto launch = [&](auto r, auto okind, auto st, const auto& view) {
+        using R = decltype(r);
+        constexpr int O = decltype(okind)::value;
+        constexpr bool S = decltype(st)::value;
+        constexpr uint32_t wg = exp_wg<R, O, S>();
+        constexpr bool pack = exp_hist_pack<R, O, S>();
+        const size_t bins = sv.n_bins, lds = pack ? (bins + 1) / 2 * 4 : bins * 4;
+        hipLaunchKernelGGL((expand_kernel<R, O, S>), dim3(c.sg.nblk, (c.n_chains + wg - 1) / wg), dim3(wg), lds, c.s,
+                           eng->kp, eng->dp, c.v,
+                           c.chain0, c.n_chains, c.step0, c.n_steps, c.utc0(), c.pv.tab64, c.pv.tab32, c.pv.sun,
+                           c.pv.events, c.pv.n_events, c.pv.desc, c.sg, view, sv, eng->cost_order ? c.pv.bperm : nullptr);
+    };
+    // fp32 kernels and a histogram spec their fp32 binning cannot resolve (StatsView::bin64):
+    // the OUT_B64 instantiations bin in fp64 (no per-second branch in the others)
+    const bool b64 = !f64 && sv.hist && sv.bin64;
+    with_real(f64, [&](auto r) {
+        with_value<0, 1>(sites, [&](auto st) {
+            constexpr bool F32 = sizeof(r) == 4, S = decltype(st)::value;
+            auto traces = [&](auto okind) { launch(r, okind, st, tv); };
+            // the fleet series (+ statistics when given; the histogram bins as hist_bin_rt decides)
+            if (c.series()) launch(r, std::integral_constant<int, OUT_SERIES | OUT_BRT>{}, st, c.sev);
+            else if (b64) {
+                if constexpr (F32) with_value<OUT_STATS | OUT_B64, OUT_ANY | OUT_B64>(out | OUT_B64, traces);
+            } else if constexpr (S) with_value<OUT_STATS, OUT_ANY>(out, traces);
+            else with_value<OUT_TRACE3, OUT_STATS, OUT_ANY>(out, traces);
+        });
+    });
+    eng->last_expand = out | (sites ? TMH_OUT_SITES : 0) | (f64 ? TMH_OUT_FP64 : 0);
+    eng->close(TMH_K_EXPAND, t_exp, c.s);
+    return hip_check(hipGetLastError(), "expand_kernel launch");
+}
+
+// the fp32 guard-band seconds redone in fp64, then the window's commit
+static int phase_commit(const StepCtx& c, hipEvent_t t_step)
+{
+    tmh_engine* const eng = c.eng;
+    if (!c.f64() && eng->kp.with_pv) {   // the fp32 guard-band seconds, in fp64
+        // one wave per FIX_RPW records, one workgroup per group of the record capacity (up to
+        // 65,535, grid-stride past it: C3): the groups past the count exit at once.  (A grid
+        // sized for ~1.3e-3 records per (chain, block) left a quarter of the C2 workgroups two
+        // groups in a row -- 2.0e-3 are recorded, ~1 flagged second each, diagnostic run r05 --
+        // and the kernel two redo latencies long.)
+        const uint32_t gx = (uint32_t)std::min<uint64_t>(65535, ((uint64_t)c.sg.fixcap + FIX_RPW - 1) / FIX_RPW);
+        with_value<0, 1>(eng->kp.sites != nullptr, [&](auto st) {
+            auto launch = [&](auto ser, const auto& view) {   // the series (no traces then), or the traces
+                hipLaunchKernelGGL((fixup_kernel<decltype(st)::value, decltype(ser)::value>), dim3(gx), dim3(64), 0, c.s,
+                                   eng->kp, eng->dp, c.v, c.chain0, c.n_chains, c.step0, c.n_steps, c.utc0(), c.pv.tab64,
+                                   c.pv.tab32, c.pv.sun, c.pv.events, c.pv.n_events, c.pv.desc, c.sg, view, c.sv);
+            };
+            if (c.series()) launch(std::true_type{}, c.sev);
+            else launch(std::false_type{}, c.tv);
+        });
+        if (int rc = hip_check(hipGetLastError(), "fixup_kernel launch")) return rc;
+    }
+    const MinuteCtx mc{eng->dp, c.chain0, c.step0, first_minute_host(c.utc0(), c.step0), c.pv.events, 0, c.pv.tab64};
+    const uint32_t acc_n = eng->kp.ids ? eng->kp.ids_n : 0u;
+    with_real(c.f64(), [&](auto r) {
+        hipLaunchKernelGGL(commit_kernel<decltype(r)>, dim3(c.cb()), dim3(256), 0, c.s, c.v, c.n_chains, c.sg, c.sv, mc,
+                           c.pv.n_events, c.pv.desc + nblk_of(c.n_steps), eng->dp.markov, eng->dp.ids, acc_n);
+    });
+    eng->close(TMH_K_STEP, t_step, c.s);
+    return hip_check(hipGetLastError(), "commit_kernel launch");
+}
 
 static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_chains, int64_t step0,
                        uint32_t n_steps, const tmh_ustream* inj, const tmh_trace* trace, const tmh_stats* stats,
@@ -3868,14 +3894,12 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     if (tp && (!scratch || scratch_bytes < tmh_engine_scratch_bytes(eng, n_chains, n_steps)))
         return fail(TMH_E_INVAL, "scratch too small: %zu < %zu", scratch_bytes, tmh_engine_scratch_bytes(eng, n_chains, n_steps));
     if (int rc = hip_check(hipSetDevice(eng->device), "hipSetDevice")) return rc;
-    PlanView pv;
-    plan_layout(n_steps, (void*)plan, &pv);
-    StateView v = make_view(state, n_chains);
-    InjView iv{inj ? inj->u : nullptr, inj ? inj->stride : 0, inj ? inj->len : 0};
-    TraceView tv{};
-    if (trace) tv = TraceView{trace->csi, trace->pv, trace->meter, trace->residual, trace->covered, trace->ld};
-    StatsView sv{};
-    size_t lds = 0;
+    StepCtx c{eng, (hipStream_t)stream, chain0, n_chains, step0, n_steps, prev};   // (the views: zero)
+    plan_layout(n_steps, (void*)plan, &c.pv);
+    c.v = make_view(state, n_chains);
+    c.iv = InjView{inj ? inj->u : nullptr, inj ? inj->stride : 0, inj ? inj->len : 0};
+    if (trace) c.tv = TraceView{trace->csi, trace->pv, trace->meter, trace->residual, trace->covered, trace->ld};
+    StatsView& sv = c.sv;
     if (stats) {
         sv.hist = stats->hist;
         sv.n_bins = stats->hist ? stats->n_bins : 0;
@@ -3889,201 +3913,36 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
             sv.bin64 = err > 1e-3 ? 1u : 0u;
         }
         sv.acc = stats->chain_acc;
-        lds = stats->hist ? (size_t)stats->n_bins * 4 : 0;
     }
-    SeriesView sev{};
     if (series)   // the window's first row of group 0
-        sev = SeriesView{reinterpret_cast<unsigned long long*>(eng->series.sum) + (size_t)(step0 - eng->series.step0) * 4,
-                         (uint64_t)eng->series.n_steps * 4, eng->series.group_chains, 0u};
-    hipStream_t s = (hipStream_t)stream;
-    const bool f64 = eng->kp.precision == TMH_FP64, keyed = eng->kp.rng_mode == TMH_RNG_KEYED;
-    if (!tp) {   // sequential path: one kernel, run by the expand phase
+        c.sev = SeriesView{reinterpret_cast<unsigned long long*>(eng->series.sum) + (size_t)(step0 - eng->series.step0) * 4,
+                           (uint64_t)eng->series.n_steps * 4, eng->series.group_chains, 0u};
+    if (!tp) {   // sequential path: one kernel, run by the expand phase (LDS: the histogram's 32-bit bins)
         if (!(phases & PH_EXPAND)) return TMH_OK;
-        dim3 grid((n_chains + 255) / 256), block(256);
-#define LAUNCH(R, M)                                                                                                 \
-    hipLaunchKernelGGL((chain_kernel<R, M>), grid, block, lds, s, eng->kp, v, chain0, n_chains, step0, n_steps,      \
-                       pv.tab64, pv.tab32, pv.sun, iv, tv, sv)
-        if (f64 && keyed) LAUNCH(double, TMH_RNG_KEYED);
-        else if (f64) LAUNCH(double, TMH_RNG_INJECTED);
-        else if (keyed) LAUNCH(float, TMH_RNG_KEYED);
-        else LAUNCH(float, TMH_RNG_INJECTED);
-#undef LAUNCH
+        with_real(c.f64(), [&](auto r) {
+            with_value<TMH_RNG_KEYED, TMH_RNG_INJECTED>(eng->kp.rng_mode, [&](auto rng) {
+                hipLaunchKernelGGL((chain_kernel<decltype(r), decltype(rng)::value>), dim3(c.cb()), dim3(256),
+                                   (size_t)sv.n_bins * 4, c.s, eng->kp, c.v, chain0, n_chains, step0, n_steps, c.pv.tab64,
+                                   c.pv.tab32, c.pv.sun, c.iv, c.tv, sv);
+            });
+        });
         return hip_check(hipGetLastError(), "chain_kernel launch");
     }
-    SegView sg;
-    scratch_layout(n_chains, n_steps, scratch, &sg, f64 ? 8 : 4);
+    scratch_layout(n_chains, n_steps, scratch, &c.sg, c.f64() ? 8 : 4);
     {   // fixed-point scale of the statistics: |a window's sum| <= (9,000 + max(Paco, 0)) W x n_steps < 2^62 / 2^k
         const double bound = (9000.0 + std::max(eng->kp.inverter[0], 0.0) + 1.0) * (double)n_steps;
         const int k = 62 - (int)std::ceil(std::log2(bound));
-        sg.fx_scale = std::ldexp(1.0, k);
-        sg.fx_inv = std::ldexp(1.0, -k);
+        c.sg.fx_scale = std::ldexp(1.0, k);
+        c.sg.fx_inv = std::ldexp(1.0, -k);
     }
-    const uint32_t cb = (n_chains + 255) / 256;
-    const int64_t utc0 = eng->gp.clock.utc0;
-    hipEvent_t t_step = phases == PH_ALL ? eng->mark(s) : nullptr;
-    if (phases & PH_DRAWS) {
-        // the walk rows' order, read by the candidate table's layout and by the walk: computed
-        // here (tmh_set_walk_order before a window's draws), so the walk uses the order its
-        // window's draws were made with whatever the engine's flag says when it runs
-        const bool mk_pre = eng->dp.markov && n_chains <= eng->mk_pre_max;
-        hipLaunchKernelGGL(event_draws_kernel, dim3(sg.evcap, cb), dim3(256), 0, s, eng->dp, eng->kp, mk_pre, chain0, n_chains, n_steps,
-                           pv.events, pv.n_events, sg.evd, eng->walk_order ? nullptr : sg.order,
-                           eng->walk_order ? nullptr : sg.rank);
-        if (eng->dp.markov)
-            hipLaunchKernelGGL(markov_cc_kernel, dim3(cb), dim3(256), 0, s, eng->kp, mk_pre, v, chain0, n_chains, n_steps,
-                               pv.events, pv.n_events, sg.evd, prev);
-        if (eng->walk_order)
-        {
-            const uint32_t tiles = (n_chains + ORDER_TILE - 1) / ORDER_TILE;
-            if (tiles <= WALK_RANK_TILES)   // small batches (latency-bound on the construction stream): the rank sort
-                hipLaunchKernelGGL(walk_rank_kernel, dim3(tiles * (ORDER_TILE / ORDER_EPB)), dim3(256), 0, s, v, n_chains,
-                                   sg, prev);
-            else
-                hipLaunchKernelGGL(walk_order_kernel, dim3(tiles), dim3(1024), 0, s, v, n_chains, sg, prev);
-        }
-        hipEvent_t t_cand = eng->mark(s);
-        {   // candidates + the window's minute draws (+ counter resets), one launch
-            const int64_t fmh = first_minute_host(utc0, step0);
-            const uint32_t nm = fmh < (int64_t)n_steps ? (uint32_t)((n_steps - 1 - fmh) / 60 + 1) : 0;
-            const uint32_t ny = sg.kcap + nm;   // rows; the kernel strides over y past 65,535 (long windows)
-            const dim3 grid(cb, std::min(ny, 65535u));
-            const BlockDesc* de = pv.desc + nblk_of(n_steps);
-            if (f64)
-                hipLaunchKernelGGL(draws_tail_kernel<double>, grid, dim3(256), 0, s, eng->dp, v, chain0, n_chains, step0,
-                                   n_steps, fmh, ny, pv.tab64, pv.events, pv.n_events, de, sg, prev);
-            else
-                hipLaunchKernelGGL(draws_tail_kernel<float>, grid, dim3(256), 0, s, eng->dp, v, chain0, n_chains, step0,
-                                   n_steps, fmh, ny, pv.tab64, pv.events, pv.n_events, de, sg, prev);
-        }
-        eng->close(TMH_K_CANDIDATES, t_cand, s);
-        if (int rc = hip_check(hipGetLastError(), "draws kernels launch")) return rc;
-    }
-    if (phases & PH_SEGMENTS) {
-    hipEvent_t t_seg = eng->mark(s);
-    // groups of walk_lanes lanes, 16 per workgroup (16 G threads, 16 x WALK_CAND candidate slots in LDS)
-    const uint32_t rows = (uint32_t)(((uint64_t)n_chains + eng->walk_cpr - 1) / eng->walk_cpr);
-    const uint32_t G = eng->walk_lanes ? eng->walk_lanes : (n_chains > WALK_AUTO_SMALL ? 4u : 16u);
-    const uint32_t gpw = 16;   // groups (chains) per workgroup
-    const dim3 wg((rows + gpw - 1) / gpw), wt(gpw * G);
-    const size_t wlds = gpw * WALK_CAND * sizeof(double);
-#define WALK(Q, GG, ...)                                                                                          \
-    hipLaunchKernelGGL((segments_kernel<Q, GG, ##__VA_ARGS__>), wg, wt, wlds, s, eng->dp, v, chain0, n_chains, step0, \
-                       n_steps, eng->gp.clock, pv.events, pv.n_events, sg, prev)
-    const bool q = rows < n_chains;   // groups take queued chains
-    if (G == 4) { if (q) WALK(true, 4); else WALK(false, 4); }
-    else if (G == 8) { if (q) WALK(true, 8); else if (rows >= eng->walk_tp_rows) WALK(false, 8, true); else WALK(false, 8); }
-    else { if (q) WALK(true, 16); else WALK(false, 16); }
-#undef WALK
-    hipLaunchKernelGGL(overflow_settle_kernel, dim3(cb), dim3(256), 0, s, n_chains, sg);
-    hipLaunchKernelGGL(block_rec_kernel, dim3(cb, (sg.nblk + BREC_G - 1) / BREC_G), dim3(256), 0, s, n_chains, step0, sg);
-    eng->close(TMH_K_SEGMENTS, t_seg, s);
-    if (int rc = hip_check(hipGetLastError(), "segments kernel launch")) return rc;
-    }
-    if (phases & PH_EXPAND) {
-    hipEvent_t t_exp = eng->mark(s);
-    const bool no_stats = !sv.hist && !sv.acc;
-    int out = series ? OUT_SERIES   // (no trace pointers: check_series)
-              : (no_stats && tv.pv && tv.meter && tv.residual && !tv.csi && !tv.covered) ? OUT_TRACE3
-                    : (!tv.pv && !tv.meter && !tv.residual && !tv.csi && !tv.covered) ? OUT_STATS
-                                                                                      : OUT_ANY;
-    const size_t hist_bins = stats && stats->hist ? stats->n_bins : 0;
-    // x = time blocks, y = chain blocks; LDS: the histogram (16-bit bin pairs or bins)
-    auto exp_grid = [&](uint32_t wg, uint32_t tpw) { return dim3((sg.nblk + tpw - 1) / tpw, (n_chains + wg - 1) / wg); };
-    // the tiles in cost order (block_order_kernel's plan permutation; TMH_EXP_COST_ORDER=1, A/B only)
-    const uint32_t* bperm = eng->cost_order ? pv.bperm : nullptr;
-    auto exp_lds = [&](bool pack) { return pack ? (hist_bins + 1) / 2 * 4 : hist_bins * 4; };
-    if (out == OUT_TRACE3 && tv.ld * (f64 ? 8u : 4u) * BLOCK_STEPS >= (1ull << 31))   // one block's rows: one buffer range
-        return fail(TMH_E_INVAL, "trace ld %llu too large (a 128-step block of rows must stay under 2 GiB)",
-                    (unsigned long long)tv.ld);
-#define LAUNCH(R, O, S)                                                                                            \
-    hipLaunchKernelGGL((expand_kernel<R, O, S>),                                                                   \
-                       exp_grid(exp_wg<R, O, S>(), exp_tpw<R, O, S>()), dim3(exp_wg<R, O, S>()),                 \
-                       exp_lds(exp_hist_pack<R, O, S>()), s,                                                      \
-                       eng->kp, eng->dp, v, chain0, n_chains, step0, n_steps,   \
-                       utc0, pv.tab64, pv.tab32, pv.sun, pv.events, pv.n_events, pv.desc, sg, tv, sv, bperm)
-#ifndef TMH_SITES_STATS
-#define TMH_SITES_STATS 1   // per-chain sites: the statistics-only instantiation (0: OUT_ANY for every output, A/B)
-#endif
-    // fp32 kernels and a histogram spec their fp32 binning cannot resolve (StatsView::bin64):
-    // the OUT_B64 instantiations bin in fp64 (no per-second branch in the others)
-    const bool b64 = !f64 && sv.hist && sv.bin64;
-    if (series) {   // the fleet series (+ statistics when given; the histogram bins as hist_bin_rt decides)
-#define LAUNCH_SER(R, S)                                                                                           \
-    hipLaunchKernelGGL((expand_kernel<R, OUT_SERIES | OUT_BRT, S>),                                                \
-                       exp_grid(exp_wg<R, OUT_SERIES, S>(), exp_tpw<R, OUT_SERIES, S>()),                        \
-                       dim3(exp_wg<R, OUT_SERIES, S>()), exp_lds(exp_hist_pack<R, OUT_SERIES, S>()), s, eng->kp,  \
-                       eng->dp, v, chain0, n_chains, step0, n_steps, utc0, pv.tab64, pv.tab32, pv.sun, pv.events,  \
-                       pv.n_events, pv.desc, sg, sev, sv, bperm)
-        if (eng->kp.sites) {
-            if (f64) LAUNCH_SER(double, true);
-            else LAUNCH_SER(float, true);
-        } else {
-            if (f64) LAUNCH_SER(double, false);
-            else LAUNCH_SER(float, false);
-        }
-#undef LAUNCH_SER
-    } else if (eng->kp.sites) {   // per-chain sites: statistics only (C5), or any output
-        if (!TMH_SITES_STATS && out == OUT_STATS) out = OUT_ANY;
-        if (f64) {
-            if (out == OUT_STATS) LAUNCH(double, OUT_STATS, true);
-            else LAUNCH(double, OUT_ANY, true);
-        } else if (b64) {
-            if (out == OUT_STATS) LAUNCH(float, OUT_STATS | OUT_B64, true);
-            else LAUNCH(float, OUT_ANY | OUT_B64, true);
-        } else {
-            if (out == OUT_STATS) LAUNCH(float, OUT_STATS, true);
-            else LAUNCH(float, OUT_ANY, true);
-        }
-    } else if (f64) {
-        if (out == OUT_TRACE3) LAUNCH(double, OUT_TRACE3, false);
-        else if (out == OUT_STATS) LAUNCH(double, OUT_STATS, false);
-        else LAUNCH(double, OUT_ANY, false);
-    } else if (b64) {
-        if (out == OUT_STATS) LAUNCH(float, OUT_STATS | OUT_B64, false);
-        else LAUNCH(float, OUT_ANY | OUT_B64, false);
-    } else {
-        if (out == OUT_TRACE3) LAUNCH(float, OUT_TRACE3, false);
-        else if (out == OUT_STATS) LAUNCH(float, OUT_STATS, false);
-        else LAUNCH(float, OUT_ANY, false);
-    }
-#undef LAUNCH
-    eng->last_expand = (eng->kp.sites ? ((out == OUT_SERIES ? TMH_OUT_SERIES : out == OUT_STATS ? TMH_OUT_STATS : TMH_OUT_ANY) | TMH_OUT_SITES) : out) |
-                       (f64 ? TMH_OUT_FP64 : 0);
-    eng->close(TMH_K_EXPAND, t_exp, s);
-    if (int rc = hip_check(hipGetLastError(), "expand_kernel launch")) return rc;
-    }
-    if (!(phases & PH_COMMIT)) return TMH_OK;
-    if (!f64 && eng->kp.with_pv) {   // the fp32 guard-band seconds, in fp64
-        // one wave per FIX_RPW records, one workgroup per group of the record capacity (up to
-        // 65,535, grid-stride past it: C3): the groups past the count exit at once.  (A grid
-        // sized for ~1.3e-3 records per (chain, block) left a quarter of the C2 workgroups two
-        // groups in a row -- 2.0e-3 are recorded, ~1 flagged second each, diagnostic run r05 --
-        // and the kernel two redo latencies long.)
-        const uint32_t gx = (uint32_t)std::min<uint64_t>(65535, ((uint64_t)sg.fixcap + FIX_RPW - 1) / FIX_RPW);
-        if (series && eng->kp.sites)
-            hipLaunchKernelGGL((fixup_kernel<true, true>), dim3(gx), dim3(64), 0, s, eng->kp, eng->dp, v, chain0, n_chains, step0,
-                               n_steps, utc0, pv.tab64, pv.tab32, pv.sun, pv.events, pv.n_events, pv.desc, sg, sev, sv);
-        else if (series)
-            hipLaunchKernelGGL((fixup_kernel<false, true>), dim3(gx), dim3(64), 0, s, eng->kp, eng->dp, v, chain0, n_chains, step0,
-                               n_steps, utc0, pv.tab64, pv.tab32, pv.sun, pv.events, pv.n_events, pv.desc, sg, sev, sv);
-        else if (eng->kp.sites)
-            hipLaunchKernelGGL(fixup_kernel<true>, dim3(gx), dim3(64), 0, s, eng->kp, eng->dp, v, chain0, n_chains, step0,
-                               n_steps, utc0, pv.tab64, pv.tab32, pv.sun, pv.events, pv.n_events, pv.desc, sg, tv, sv);
-        else
-            hipLaunchKernelGGL(fixup_kernel<false>, dim3(gx), dim3(64), 0, s, eng->kp, eng->dp, v, chain0, n_chains, step0,
-                               n_steps, utc0, pv.tab64, pv.tab32, pv.sun, pv.events, pv.n_events, pv.desc, sg, tv, sv);
-        if (int rc = hip_check(hipGetLastError(), "fixup_kernel launch")) return rc;
-    }
-    const MinuteCtx mc{eng->dp, chain0, step0, first_minute_host(utc0, step0), pv.events, 0, pv.tab64};
-    const uint32_t acc_n = eng->kp.ids ? eng->kp.ids_n : 0u;
-    if (f64)
-        hipLaunchKernelGGL(commit_kernel<double>, dim3(cb), dim3(256), 0, s, v, n_chains, sg, sv, mc, pv.n_events,
-                           pv.desc + nblk_of(n_steps), eng->dp.markov, eng->dp.ids, acc_n);
-    else
-        hipLaunchKernelGGL(commit_kernel<float>, dim3(cb), dim3(256), 0, s, v, n_chains, sg, sv, mc, pv.n_events,
-                           pv.desc + nblk_of(n_steps), eng->dp.markov, eng->dp.ids, acc_n);
-    eng->close(TMH_K_STEP, t_step, s);
-    return hip_check(hipGetLastError(), "commit_kernel launch");
+    hipEvent_t t_step = phases == PH_ALL ? eng->mark(c.s) : nullptr;
+    if (phases & PH_DRAWS)
+        if (int rc = phase_draws(c)) return rc;
+    if (phases & PH_SEGMENTS)
+        if (int rc = phase_segments(c)) return rc;
+    if (phases & PH_EXPAND)
+        if (int rc = phase_expand(c)) return rc;
+    return (phases & PH_COMMIT) ? phase_commit(c, t_step) : TMH_OK;
 }
 
 int tmh_step(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_chains, int64_t step0,
@@ -4134,8 +3993,8 @@ int tmh_expand_part(struct tmh_engine* eng, void* state, uint64_t chain0, uint32
         return fail(TMH_E_INVAL, "bad expand parts %d", parts);
     if (eng && eng->path != TMH_PATH_TIME_PARALLEL && parts != (TMH_EXPAND_KERNEL | TMH_EXPAND_COMMIT))
         return fail(TMH_E_INVAL, "tmh_expand_part in parts needs the time-parallel path");
-    const int ph = ((parts & TMH_EXPAND_KERNEL) ? PH_EXPAND : 0) | ((parts & TMH_EXPAND_COMMIT) ? PH_COMMIT : 0) |
-                   ((parts & TMH_EXPAND_MINUTES) ? PH_MINUTES : 0) | ((parts & TMH_EXPAND_NO_MINUTES) ? PH_NO_MINUTES : 0);
+    // (TMH_EXPAND_MINUTES / TMH_EXPAND_NO_MINUTES are accepted and ignored)
+    const int ph = ((parts & TMH_EXPAND_KERNEL) ? PH_EXPAND : 0) | ((parts & TMH_EXPAND_COMMIT) ? PH_COMMIT : 0);
     return step_phases(eng, state, chain0, n_chains, step0, n_steps, inj, trace, stats, plan, scratch, scratch_bytes,
                        stream, ph);
 }

@@ -25,8 +25,7 @@ namespace tmh {
 constexpr double SQRT6 = 2.449489742783178;
 constexpr float EPS0F = (float)(SQRT6 * 0.001), EPS1F = (float)(SQRT6 * (0.0015 * 8));
 struct PVF {
-    // the addends of pv_power_f's affine maps first: the first PVF_VGPR fields can be pinned in
-    // VGPRs (a VOP3 FMA reads one SGPR, so a map with two SGPR constants costs a v_mov per use)
+    // the addends of pv_power_f's affine maps first, then their factors
     float temp_air, nkq273, impo_c0, bvmpo1, vmpo, ab0, b0, c0;
     float tk, fd, nmbvmp, nkq, impo_c1, aimp, c2ns, c3ns;
     float paco, pso, ab1, b1, c1;
@@ -1171,16 +1170,8 @@ __device__ __forceinline__ bool lane_row(LaneSite& ls, const double* sun, const 
         tl = ls.tl;
     }
     double g[ROW];
-#ifndef TMH_HA_ROTATE
-#define TMH_HA_ROTATE 1   // 0: a sincos per chain-second (A/B builds)
-#endif
-#if TMH_HA_ROTATE
     const double sdh = sun[SUN_SDH], cdh = sun[SUN_CDH];
     const double sha = fma(ls.s0, cdh, ls.c0 * sdh), cha = fma(ls.c0, cdh, -(ls.s0 * sdh));
-#else
-    double sha, cha;
-    sincos_pi(hour_angle(ls.k, sun), &sha, &cha);
-#endif
     if (site_geom_hc<false, sizeof(R) == 4>(ls.k, sun, tl, module, g, t, sha, cha)) return true;
     site_row<R>(g, sun, row);
     return g[G_GHICS] == 0.0;
@@ -1223,10 +1214,8 @@ __device__ __forceinline__ PP lds_fence(PP p)
 // kernels build with -ffp-contract=off); fp64 C2 trace loop -5 % VALU.  DISC's polynomials
 // keep the multiply-add form: fused as well, the trace kernel took 122 VGPRs instead of 110,
 // i.e. two waves per SIMD beside a 146-VGPR walk wave instead of three (measured: alone
-// 2.74 against 2.89 ms, in the pipeline 3.05 against 2.94 ms).
-#ifndef TMH_DISC64_HORNER
-#define TMH_DISC64_HORNER 0   // A/B builds: 9 fmas, but 33 VGPRs spilled in the fp64 trace loop (2.99-3.07 against 2.55-2.70 ms alone, round 6)
-#endif
+// 2.74 against 2.89 ms, in the pipeline 3.05 against 2.94 ms; as Horner fmas, 9 instead of 14
+// operations, it spilled 33 VGPRs in the fp64 trace loop: 2.99-3.07 against 2.55-2.70 ms alone, round 6).
 template <typename PP, typename LT>
 __device__ __forceinline__ double pv_power_d(PP p, const double* g, double csi, LT lt)
 {
@@ -1237,19 +1226,6 @@ __device__ __forceinline__ double pv_power_d(PP p, const double* g, double csi, 
     kt = kt < 1.0 ? kt : 1.0;
     const double am = g[G_AM];
     double a, b, cc;
-#if TMH_DISC64_HORNER
-    // Horner with fmas (round 6): within ~1e-16 relative of pvmodel.py's power form (the fp64
-    // bar is 1e-12), 9 fmas instead of 14 multiplies and adds
-    if (kt <= 0.6) {
-        a = fma(fma(fma(-2.222, kt, 2.286), kt, -1.56), kt, 0.512);
-        b = fma(0.962, kt, 0.37);
-        cc = fma(fma(-2.048, kt, 0.932), kt, -0.28);
-    } else {
-        a = fma(fma(fma(11.56, kt, -27.49), kt, 21.77), kt, -5.743);
-        b = fma(fma(fma(31.9, kt, 66.05), kt, -118.5), kt, 41.4);
-        cc = fma(fma(fma(73.81, kt, -222.0), kt, 184.2), kt, -47.01);
-    }
-#else
     const double kt2 = kt * kt, kt3 = kt2 * kt;
     if (kt <= 0.6) {
         a = 0.512 - 1.56 * kt + 2.286 * kt2 - 2.222 * kt3;
@@ -1260,7 +1236,6 @@ __device__ __forceinline__ double pv_power_d(PP p, const double* g, double csi, 
         b = 41.4 - 118.5 * kt + 66.05 * kt2 + 31.9 * kt3;
         cc = -47.01 + 184.2 * kt - 222.0 * kt2 + 73.81 * kt3;
     }
-#endif
     double ex;
     if constexpr (__is_same(LT, decltype(nullptr))) ex = exp_tab(cc * am, (const double*)g_pv_tab);
     else ex = exp_tab(cc * am, lt);
@@ -1333,25 +1308,6 @@ __device__ __forceinline__ float disc_poly(const Cubic& p, float t)
     return v;
 }
 
-// The same coefficients as a table (round 6): the single-site expansion keeps it in LDS after
-// the noise quantile's and reads the lane's set, so DISC's kt split costs an address select
-// instead of divergent branches.  Rows {d3, d2, d1, d0} of a, b, c for kt <= 0.6, then for
-// kt > 0.6; the low set's missing leading terms are 0, and Horner through a zero leading term
-// gives disc_poly's value bit for bit (0 t + 0 = +-0, then +-0 t + d = d exactly, d != 0).
-constexpr int DISC_TAB = 6;
-__device__ __forceinline__ float4 disc_row(int i)
-{
-    const Cubic& p = i % 3 == 0 ? (i < 3 ? DISC_A_LO : DISC_A_HI)
-                                : (i % 3 == 1 ? (i < 3 ? DISC_B_LO : DISC_B_HI) : (i < 3 ? DISC_C_LO : DISC_C_HI));
-    const int deg = i == 1 ? 1 : (i == 2 ? 2 : 3);
-    const float d3 = deg >= 3 ? disc_shift(p, 3) : 0.0f, d2 = deg >= 2 ? disc_shift(p, 2) : 0.0f;
-    return make_float4(d3, d2, disc_shift(p, 1), disc_shift(p, 0));
-}
-__device__ __forceinline__ float disc_horner(const float4& d, float t)
-{
-    return fmaf(fmaf(fmaf(d.x, t, d.y), t, d.z), t, d.w);
-}
-
 // Guard band of the fp32 chain's two discontinuities (DISC's kt = 0.6 split and
 // the inverter's p_dc < Pso cut-in): a second whose fp32 kt or p_dc lies this
 // close to its threshold may have fallen on the other side than the fp64
@@ -1367,8 +1323,7 @@ constexpr float KT_GUARD = 4e-6f, PDC_GUARD = 1e-4f;
 // UROW: the row is wave-uniform (the single-site kernels' scalar loads), so the clamp's bound
 // is an SGPR operand of a plain v_min_f32
 template <bool UROW = false>
-__device__ __forceinline__ float pv_power_f(const PVF& k, const float* g, float csi, bool discok, bool& risky,
-                                            const float4* dtab = nullptr)
+__device__ __forceinline__ float pv_power_f(const PVF& k, const float* g, float csi, bool discok, bool& risky)
 {
     // min(csi, csimax) as a median with -inf: no canonicalising max of the row's value first.
     // On a NaN csi it returns csimax, as fminf did (tmh_probe fn 10, test_probe_math); a NaN
@@ -1383,20 +1338,11 @@ __device__ __forceinline__ float pv_power_f(const PVF& k, const float* g, float 
     // DISC Kn: coefficient sets split at kt = 0.6 (compile-time constants, no
     // SGPRs).  Both sets are evaluated and the results selected: cheaper than
     // selecting twelve coefficient pairs per lane.
-    // UROW with dtab (the single-site expansion): the lane's set from the LDS table (disc_row)
     const bool lo = kt <= 0.6f;
     const float t = kt - 0.6f;
-    float a, b, cc;
-    if (UROW && dtab) {
-        const float4* d = dtab + (lo ? 0 : 3);
-        a = disc_horner(d[0], t);
-        b = disc_horner(d[1], t);
-        cc = disc_horner(d[2], t);
-    } else {
-        a = lo ? disc_poly<3>(DISC_A_LO, t) : disc_poly<3>(DISC_A_HI, t);
-        b = lo ? disc_poly<1>(DISC_B_LO, t) : disc_poly<3>(DISC_B_HI, t);
-        cc = lo ? disc_poly<2>(DISC_C_LO, t) : disc_poly<3>(DISC_C_HI, t);
-    }
+    const float a = lo ? disc_poly<3>(DISC_A_LO, t) : disc_poly<3>(DISC_A_HI, t);
+    const float b = lo ? disc_poly<1>(DISC_B_LO, t) : disc_poly<3>(DISC_B_HI, t);
+    const float cc = lo ? disc_poly<2>(DISC_C_LO, t) : disc_poly<3>(DISC_C_HI, t);
     // exp(cc am) = exp2(cc * (am log2 e)): the fp32 row holds am log2 e (one rounding)
     const float dkn = fmaf(b, __builtin_amdgcn_exp2f(cc * g[G_AM]), a);
     float dni = (g[G_KNC] - dkn) * g[G_I0];
@@ -1530,8 +1476,7 @@ __device__ __forceinline__ R meter_w(uint32_t w)
 template <typename R, bool UROW = false, typename P64 = decltype(nullptr), typename LT = decltype(nullptr)>
 __device__ __forceinline__ void second_body(const KParams& kp, const PVF& pk, const R* row, uint32_t fl,
                                             const FSamp<R>& fs, bool covered, R z, R meter_in, R& csi, R& pv, R& meter,
-                                            R& res, bool& risky, P64 p64 = nullptr, LT lt = nullptr,
-                                            const float4* dtab = nullptr)
+                                            R& res, bool& risky, P64 p64 = nullptr, LT lt = nullptr)
 {
     risky = false;
     const R cloudcover = rinterp_row(fs, S_CC, row, G_HOURF);   // == interp() bit for bit when R = double
@@ -1549,7 +1494,7 @@ __device__ __forceinline__ void second_body(const KParams& kp, const PVF& pk, co
         else
             pv = (kp.with_pv && !(fl & FL_NIGHT)) ? pv_power_d(p64, row, csi, lt) : R(0);
     }
-    else pv = (kp.with_pv && !(fl & FL_NIGHT)) ? pv_power_f<UROW>(pk, row + G32, csi, (fl & FL_DISCOK) != 0, risky, dtab) : 0.0f;
+    else pv = (kp.with_pv && !(fl & FL_NIGHT)) ? pv_power_f<UROW>(pk, row + G32, csi, (fl & FL_DISCOK) != 0, risky) : 0.0f;
     meter = meter_in;
     res = meter - pv;
 }
