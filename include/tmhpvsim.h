@@ -22,6 +22,11 @@
  *  - model faults that the reference raises as Python exceptions are reported
  *    per chain in the state's status word (TMH_CHAIN_*); a faulted chain is
  *    frozen and emits NaN (covered = 255) from the faulting step on.
+ *  - outputs of a window: per-second traces (tmh_trace), per-chain totals and a
+ *    histogram (tmh_stats), the fleet series (tmh_series: per second, summed over
+ *    the chains) and interval metering (tmh_intervals: per chain, summed over the
+ *    seconds of each metering interval -- what a household's 15-minute or hourly
+ *    meter reads; exact integer sums, compacted windows included).
  *  - `stream` is a hipStream_t (NULL = default stream); all work is enqueued
  *    asynchronously on it.  One engine per device; not re-entrant per engine.
  */
@@ -158,6 +163,28 @@ typedef struct tmh_series {
     int64_t step0;
     uint32_t n_steps, group_chains, n_groups, reserved;
 } tmh_series;
+
+/* Interval metering: what each chain's interval meter reads -- exact per-chain sums per
+ * metering interval (15 minutes, an hour, any number of seconds), accumulated over calls
+ * (the caller zero-initialises).  sum: device int64 [n_intervals][4][ld]; cell (k, col, i)
+ * sits at sum[(k*4 + col)*ld + i] and holds, over the seconds of interval k (steps
+ * [step0 + k*interval_s, step0 + (k+1)*interval_s), cut at step0 + n_steps) at which chain
+ * i is ok (live and before its fault):
+ *   [0] sum of q(pv)   [1] sum of q(meter)   [2] ok seconds   [3] ok seconds with the covered bit
+ * with the fleet series' q and TMH_SERIES_FRAC_BITS (the engine's final value -- fp32
+ * engines: after the guard-band fixup -- rounded half to even); residual energy is
+ * [1] - [0].  i is the chain's index in the batch (under tmh_set_chain_ids: ids[slot], as
+ * tmh_stats.chain_acc), so compacted windows fill the same table.  Integer sums: the bits
+ * do not depend on block, wave, window, batch, compaction or launch order.  A chain
+ * faulted at construction adds nothing; one that faults inside an interval keeps its
+ * seconds before the fault. */
+typedef struct tmh_intervals {
+    int64_t* sum;        /* device int64 [n_intervals][4][ld], accumulated; the caller zero-initialises */
+    int64_t step0;       /* origin: step s belongs to interval (s - step0) / interval_s */
+    uint32_t n_steps;    /* steps covered; n_intervals = ceil(n_steps / interval_s); a last partial interval is kept */
+    uint32_t interval_s; /* >= 1, any value (60, 900 and 3600 are the usual ones) */
+    uint64_t ld;         /* >= the batch's chains (>= n_full under tmh_set_chain_ids) */
+} tmh_intervals;
 
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
@@ -296,6 +323,18 @@ int tmh_set_sites(struct tmh_engine* eng, const double* sites, const double* lin
  * below TMH_SERIES_MAX_W.  Per-chain statistics and the histogram are accumulated
  * beside the series when tmh_stats gives them. */
 int tmh_set_series(struct tmh_engine* eng, const tmh_series* series);
+/* Interval metering (tmh_intervals above): every later expansion of this engine adds its
+ * window to iv->sum; NULL switches it off.  A setter like tmh_set_series; the struct is
+ * copied, the buffer must outlive the launches; the table is final after the
+ * TMH_EXPAND_COMMIT half.  Refused here: a NULL or misaligned (8 bytes) sum, n_steps,
+ * ld or interval_s of 0.  With intervals set, a step / expansion call (and a walk of
+ * that window) is refused (TMH_E_INVAL, before any launch) when: a trace pointer is
+ * non-NULL; a fleet series is set too; the engine runs the sequential path or injected
+ * uniforms; the window is not inside [step0, step0 + n_steps); ld is smaller than the
+ * chains it must hold (n_chains, under tmh_set_chain_ids n_full); inverter Paco or |Pnt|
+ * is not below TMH_SERIES_MAX_W.  Compacted windows are accepted.  Per-chain statistics
+ * and the histogram are accumulated beside the intervals when tmh_stats gives them. */
+int tmh_set_intervals(struct tmh_engine* eng, const tmh_intervals* iv);
 /* Tests only: the fp32 guard-band records (chain, block) the last expansion on
  * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
  * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
@@ -320,7 +359,10 @@ int tmh_run(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_cha
 /* Build the chain-independent plan of the window [step0, step0 + n_steps) into
  * `plan` (tmh_plan_bytes(n_steps) bytes).  The first TMH_GEOM_FIELDS * n_steps
  * doubles are the clock/geometry table (row layout in DESIGN.md).  One plan
- * serves every chain batch of the same site and window. */
+ * serves every chain batch of the same site and window.  A plan is read-only
+ * from here on: nothing may write to it while a walk or an expansion that was
+ * given it is still running (the expansion reads its rows as constant memory);
+ * reuse the buffer for another window only after those have finished. */
 int tmh_plan(struct tmh_engine* eng, int64_t step0, uint32_t n_steps, void* plan, void* stream);
 
 /* tmh_run on a plan built by tmh_plan(step0, n_steps) for this engine. */
@@ -396,13 +438,15 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * (tests and measurement: which kernel instantiation produced a line or a trace):
  * TMH_OUT_ANY (any trace fields and/or statistics), TMH_OUT_TRACE3 (exactly pv,
  * meter, residual, no statistics: the trace-mode hot path), TMH_OUT_STATS
- * (statistics only), TMH_OUT_SERIES (a fleet series, with or without statistics), plus
+ * (statistics only), TMH_OUT_SERIES (a fleet series, with or without statistics),
+ * TMH_OUT_INTERVALS (interval metering, with or without statistics), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
 #define TMH_OUT_TRACE3 1
 #define TMH_OUT_STATS 2
 #define TMH_OUT_SERIES 3
+#define TMH_OUT_INTERVALS 4
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

@@ -11,6 +11,8 @@ tmhpvsim/metersim.py:79-95).
                                         [--batch N --start T --seconds S --seed K --out FILE]
     python -m tmhpvsim_amd.cli fleet FILE --batch N --no-realtime [--bin S] [--precision fp32|fp64]
                                           [--start T --seconds S --seed K]
+    python -m tmhpvsim_amd.cli intervals FILE --batch N --no-realtime --interval S [--all-chains NPZ]
+                                              [--precision fp32|fp64] [--start T --seconds S --seed K]
 
 Without --batch the commands are the reference's AMQP pipelines (a fanout
 exchange carrying one JSON float per second, pvsim.py:43-84, metersim.py:13-62):
@@ -29,6 +31,11 @@ large) and writes the fleet's means per bin of --bin seconds: header
 `time,n_ok,meter,pv,residual load,covered` -- the bin's start, its ok chain-seconds,
 the mean meter, pv and residual load per ok chain-second (W) and the share of them
 under cloud (tmhpvsim_amd.series).
+`intervals` runs N chains with interval metering only (tmhpvsim_amd.intervals: each
+chain's exact energy per metering interval of --interval seconds; no per-second trace
+leaves the GPU) and writes the reference's CSV columns `time,meter,pv,residual load` as
+interval means for chain 0, one row per interval stamped with the interval's start;
+--all-chains writes every chain's raw table and its watt / watt-hour arrays to an .npz.
 There is no CPU fallback: the batch mode fails if the engine cannot run.
 """
 from __future__ import annotations
@@ -77,6 +84,24 @@ def _fleet_run(n, start, seconds, seed, precision, bin_s):
     if bad:
         logger.warning(f"{bad} of {n} chains faulted (reference exceptions); the means are over the ok chains")
     return {k: v[0] for k, v in out.items()}
+
+
+def _intervals_run(n, start, seconds, seed, precision, interval_s):
+    from .engine import BatchedSim
+    from .params import ModelParams
+    import torch
+    if not torch.cuda.is_available():
+        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
+    params = ModelParams(seed=int(seed))
+    sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
+                     horizon=int(seconds))
+    raw = sim.enable_intervals(int(seconds), int(interval_s))
+    sim.run(int(seconds), trace=())
+    out = sim.intervals()
+    bad = int((sim.status() != 0).sum())
+    if bad:
+        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their intervals hold the seconds before the fault")
+    return raw.cpu().numpy(), out
 
 
 def _times(start, seconds):
@@ -179,6 +204,32 @@ def fleet(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, se
             w.writerow([t0 + dt.timedelta(seconds=i * bin_s), int(out["n_ok"][i]), float(out["meter"][i]),
                         float(out["pv"][i]), float(out["residual"][i]), float(out["covered"][i])])
     click.echo(f"wrote {len(out['n_ok'])} rows to {file}")
+
+
+@main.command()
+@click.argument("file")
+@common
+@click.option("--precision", type=click.Choice(["fp64", "fp32"]), default="fp32", help="batch mode arithmetic")
+@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
+              help="seconds per metering interval (a last partial interval is kept)")
+@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
+def intervals(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, interval_s, all_chains):
+    """Interval means of chain 0 over --batch chains to FILE (CSV; interval-metering engine run)."""
+    logging.basicConfig(level=logging.WARN - 10 * verbose)
+    _need_batch(realtime, batch, "intervals")
+    raw, out = _intervals_run(batch, start, seconds, seed, precision, interval_s)
+    t0 = dt.datetime.fromisoformat(str(start))
+    rows = raw.shape[0]
+    with open(file, mode="w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(["time", "meter", "pv", "residual load"])
+        for k in range(rows):
+            w.writerow([t0 + dt.timedelta(seconds=k * interval_s), float(out["meter"][k, 0]), float(out["pv"][k, 0]),
+                        float(out["residual"][k, 0])])
+    if all_chains:
+        import numpy as np
+        np.savez(all_chains, raw=raw, interval_s=interval_s, **out)
+    click.echo(f"wrote {rows} rows to {file}" + (f" and {batch} chains to {all_chains}" if all_chains else ""))
 
 
 if __name__ == "__main__":

@@ -47,7 +47,7 @@
 
 using namespace tmh;
 static_assert(OUT_ANY == TMH_OUT_ANY && OUT_TRACE3 == TMH_OUT_TRACE3 && OUT_STATS == TMH_OUT_STATS &&
-                  OUT_SERIES == TMH_OUT_SERIES,
+                  OUT_SERIES == TMH_OUT_SERIES && OUT_INTERVALS == TMH_OUT_INTERVALS,
               "expansion variants: tmh_model.h and include/tmhpvsim.h agree");
 
 namespace {
@@ -2101,9 +2101,11 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                             const TraceView& tr, const StatsView& sv, uint32_t* lds_hist,
                                             uint32_t (*cov_lds)[WGT], R (*min_lds)[WGT], uint4* held_lds,
                                             const PV64* pv_lds, const double* pv_lds_tab,
-                                            const float4* nd_lds, const SeriesView& se, SeriesLds* ser_lds)
+                                            const float4* nd_lds, const SeriesView& se, SeriesLds* ser_lds,
+                                            const IntervalsView& ivv)
 {
     constexpr bool SER = out_base(OUT) == OUT_SERIES;
+    constexpr bool IVL = out_base(OUT) == OUT_INTERVALS;
     const uint32_t c = cblk * blockDim.x + threadIdx.x;
     const bool live = c < n;
     const uint32_t j0 = b * BLOCK_STEPS, j1 = min(j0 + (uint32_t)BLOCK_STEPS, nsteps);
@@ -2191,8 +2193,13 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // start at 2^31, out of the resource's range, so the stores need no exec mask.
     // (The host keeps a block's rows under 2 GiB: tmh_expand checks the trace's ld.)
     constexpr int RW = sizeof(R) == 8 ? ROW : ROW32;   // geometry row: wave-uniform, scalar loads
-    const R* rowp = (sizeof(R) == 8 ? reinterpret_cast<const R*>(tab64) : reinterpret_cast<const R*>(tab32)) +
-                    (size_t)j0 * RW;
+    // (OUT_INTERVALS flushes with global atomics inside the block's loop, after which the compiler
+    // no longer takes a plain global load for unclobbered and loads the rows per lane: there the
+    // row pointer is a constant-address-space one -- the plan is read-only while the expansion
+    // runs -- so the row loads stay scalar)
+    using RowP = std::conditional_t<IVL, const __attribute__((address_space(4))) R*, const R*>;
+    RowP rowp = (RowP)(sizeof(R) == 8 ? reinterpret_cast<const R*>(tab64) : reinterpret_cast<const R*>(tab32)) +
+                (size_t)j0 * RW;
     __amdgpu_buffer_rsrc_t rs_pv, rs_m, rs_r;
     // the lane's byte offset in a trace row (lanes past the last chain at 2^31: outside the
     // resource's range, so their stores are dropped without an exec mask); the row's offset
@@ -2252,6 +2259,43 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             fpush(fs, S_CLEAR_NOISE, ncr);
         }
     };
+    // Interval metering (OUT_INTERVALS): lanes are chains, so a lane sums its own q(pv) and
+    // q(meter) over the seconds of a piece -- the part of the block inside one metering
+    // interval -- in two 64-bit integers (128 s x 2^26 does not fit 32 bits): no wave
+    // reduction, no LDS.  The piece's end iv_next and its interval iv_k are wave-uniform
+    // (scalars); iv_flush adds the piece to the chain's cell (k, col, i) with device-scope
+    // 64-bit atomics, zeros skipped.  The two count columns come from what the block holds
+    // already: ok seconds = the piece's overlap with [j0, fault_eff), covered seconds = the
+    // popcount of the staged covered words over that overlap.
+    long long iv_pv = 0, iv_m = 0;
+    uint32_t iv_k = 0, iv_next = j1;
+    if constexpr (IVL) {
+        iv_k = __builtin_amdgcn_readfirstlane((ivv.rel0 + j0) / ivv.interval_s);
+        const uint64_t nb = (uint64_t)(iv_k + 1u) * ivv.interval_s - ivv.rel0;   // the next boundary, as a window step
+        iv_next = __builtin_amdgcn_readfirstlane((uint32_t)min(nb, (uint64_t)j1));
+    }
+    auto iv_flush = [&](uint32_t pa, uint32_t pb) __attribute__((always_inline)) {
+        if (live) {
+            unsigned long long* cell = ivv.sum + (size_t)iv_k * 4 * ivv.ld + gid(kp.ids, c);
+            if (iv_pv) atomicAdd(cell, (unsigned long long)iv_pv);
+            if (iv_m) atomicAdd(cell + ivv.ld, (unsigned long long)iv_m);
+            const int32_t lo = (int32_t)(pa - j0), hi = min((int32_t)pb, fault_eff) - (int32_t)j0;
+            if (hi > lo) {
+                atomicAdd(cell + 2 * ivv.ld, (unsigned long long)(hi - lo));
+                uint32_t nc = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const int32_t wl = max(lo - 32 * w, 0), wh = min(hi - 32 * w, 32);
+                    if (wh > wl)
+                        nc += __popc(cov_lds[w][threadIdx.x] & ((wh - wl == 32 ? ~0u : ((1u << (wh - wl)) - 1u)) << wl));
+                }
+                if (nc) atomicAdd(cell + 3 * ivv.ld, (unsigned long long)nc);
+            }
+        }
+        iv_pv = 0;
+        iv_m = 0;
+        ++iv_k;
+    };
     // the second's outputs: NaN on a faulted lane, the guard-band bit, the trace stores or
     // the statistics (jb = j - j0, wave-uniform)
     auto finish = [&](uint32_t j, uint32_t jb, bool covered, R csi, R pv, R meter, R res, bool held, auto ff)
@@ -2274,6 +2318,12 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             const int qm = okl ? series_q<R>(meter) : 0;
             if (__builtin_constant_p(pv) && pv == R(0)) series_add<false>(ser_lds, jb, 0, qm, nok, ncov);
             else series_add<true>(ser_lds, jb, okl ? series_q<R>(pv) : 0, qm, nok, ncov);
+        }
+        if constexpr (IVL) {
+            // the lane's own sums of the piece; a second that is not ok adds 0, a night second's
+            // literal pv = 0 nothing (lanes past the last chain are never flushed)
+            if (!(__builtin_constant_p(pv) && pv == R(0))) iv_pv += (long long)(ok ? series_q<R>(pv) : 0);
+            iv_m += (long long)(ok ? series_q<R>(meter) : 0);
         }
         if constexpr (!FF) {
             csi = ok ? csi : R(NAN);
@@ -2394,59 +2444,76 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // costs a quarter of a block instead of half.
     auto loops = [&](auto ff) __attribute__((always_inline)) {
         uint32_t j = j0;
-        if (((W0 + j0) & 3) == 0) {
-            for (; j + 4 <= j1; j += 4) {
-                const uint64_t g = (uint64_t)(W0 + j) >> 2;
-                TMH_MARK("meter begin");
-                const U4 pm = keyed_block(kp.seed, chain, g, TAG_METER4, 0);
-                TMH_MARK("meter end");
-                if constexpr (FASTG) {
-                    const uint32_t fl0 = sizeof(R) == 8 ? (uint32_t)(double)rowp[G_FLAGS]   // the group's first row
-                                                        : __float_as_uint((float)rowp[G_FLAGS + G32]);
-                    if (!kp.with_pv || (fl0 & FL_G_NIGHT)) {
-                        apply_events(j, fl0);
-                        if (((j - j0) & 31) == 0) cov_w = cov_lds[(j - j0) >> 5][threadIdx.x];
-                        rowp += 4 * RW;
-                        TMH_MARK("night4 begin");
-                        night4(j, pm, ff);
-                        TMH_MARK("night4 end");
-                        continue;
-                    }
-                    if (fl0 & FL_G_DAY) {
-                        TMH_MARK("noise begin");
-                        const U4 pn = keyed_block(kp.seed, chain, g, TAG_NOISE4, 0);
-                        TMH_MARK("noise end");
-                        apply_events(j, fl0);
-                        if (((j - j0) & 31) == 0) cov_w = cov_lds[(j - j0) >> 5][threadIdx.x];
-                        TMH_MARK("day4 begin");
-                        day4(j, pn, pm, ff);
-                        TMH_MARK("day4 end");
-                        continue;
+        // the piece [pa, je) of the block that one metering interval covers (IVL; else the whole block)
+        uint32_t pa = j0, je = IVL ? iv_next : j1;
+        do {
+            if (((W0 + j0) & 3) == 0) {
+                if constexpr (IVL) {   // a piece that starts inside a four-second group: single seconds up to the grid
+                    for (; j < je && (j & 3u); ++j) {
+                        const uint64_t g = (uint64_t)(W0 + j) >> 2;
+                        const uint32_t q = (uint32_t)(W0 + j) & 3u;
+                        second(j, word_of(keyed_block(kp.seed, chain, g, TAG_NOISE4, 0), q),
+                               word_of(keyed_block(kp.seed, chain, g, TAG_METER4, 0), q), ff);
                     }
                 }
-                bool need = out_base(OUT) == OUT_ANY || !kp.with_pv || (SITES && wave_day);
-                if (!need && !SITES) {   // any daylight second among the four (scalar loads of their flags)
-                    uint32_t nf = FL_NIGHT;
+                for (; j + 4 <= je; j += 4) {
+                    const uint64_t g = (uint64_t)(W0 + j) >> 2;
+                    TMH_MARK("meter begin");
+                    const U4 pm = keyed_block(kp.seed, chain, g, TAG_METER4, 0);
+                    TMH_MARK("meter end");
+                    if constexpr (FASTG) {
+                        const uint32_t fl0 = sizeof(R) == 8 ? (uint32_t)(double)rowp[G_FLAGS]   // the group's first row
+                                                            : __float_as_uint((float)rowp[G_FLAGS + G32]);
+                        if (!kp.with_pv || (fl0 & FL_G_NIGHT)) {
+                            apply_events(j, fl0);
+                            if (((j - j0) & 31) == 0) cov_w = cov_lds[(j - j0) >> 5][threadIdx.x];
+                            rowp += 4 * RW;
+                            TMH_MARK("night4 begin");
+                            night4(j, pm, ff);
+                            TMH_MARK("night4 end");
+                            continue;
+                        }
+                        if (fl0 & FL_G_DAY) {
+                            TMH_MARK("noise begin");
+                            const U4 pn = keyed_block(kp.seed, chain, g, TAG_NOISE4, 0);
+                            TMH_MARK("noise end");
+                            apply_events(j, fl0);
+                            if (((j - j0) & 31) == 0) cov_w = cov_lds[(j - j0) >> 5][threadIdx.x];
+                            TMH_MARK("day4 begin");
+                            day4(j, pn, pm, ff);
+                            TMH_MARK("day4 end");
+                            continue;
+                        }
+                    }
+                    bool need = out_base(OUT) == OUT_ANY || !kp.with_pv || (SITES && wave_day);
+                    if (!need && !SITES) {   // any daylight second among the four (scalar loads of their flags)
+                        uint32_t nf = FL_NIGHT;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        nf &= sizeof(R) == 8 ? (uint32_t)(double)rowp[q * RW + G_FLAGS]
-                                             : __float_as_uint((float)rowp[q * RW + G_FLAGS + G32]);
-                    need = nf == 0;
+                        for (int q = 0; q < 4; ++q)
+                            nf &= sizeof(R) == 8 ? (uint32_t)(double)rowp[q * RW + G_FLAGS]
+                                                 : __float_as_uint((float)rowp[q * RW + G_FLAGS + G32]);
+                        need = nf == 0;
+                    }
+                    U4 pn{0u, 0u, 0u, 0u};
+                    if (need) pn = keyed_block(kp.seed, chain, g, TAG_NOISE4, 0);
+                    second(j, pn.x, pm.x, ff);
+                    second(j + 1, pn.y, pm.y, ff);
+                    second(j + 2, pn.z, pm.z, ff);
+                    second(j + 3, pn.w, pm.w, ff);
                 }
-                U4 pn{0u, 0u, 0u, 0u};
-                if (need) pn = keyed_block(kp.seed, chain, g, TAG_NOISE4, 0);
-                second(j, pn.x, pm.x, ff);
-                second(j + 1, pn.y, pm.y, ff);
-                second(j + 2, pn.z, pm.z, ff);
-                second(j + 3, pn.w, pm.w, ff);
             }
-        }
-        for (; j < j1; ++j) {   // a window start off the four-step grid, or a short last block (rare)
-            const uint64_t g = (uint64_t)(W0 + j) >> 2;
-            const uint32_t q = (uint32_t)(W0 + j) & 3u;
-            second(j, word_of(keyed_block(kp.seed, chain, g, TAG_NOISE4, 0), q),
-                   word_of(keyed_block(kp.seed, chain, g, TAG_METER4, 0), q), ff);
-        }
+            for (; j < je; ++j) {   // a window start off the four-step grid, or a short last block or piece (rare)
+                const uint64_t g = (uint64_t)(W0 + j) >> 2;
+                const uint32_t q = (uint32_t)(W0 + j) & 3u;
+                second(j, word_of(keyed_block(kp.seed, chain, g, TAG_NOISE4, 0), q),
+                       word_of(keyed_block(kp.seed, chain, g, TAG_METER4, 0), q), ff);
+            }
+            if constexpr (IVL) {
+                iv_flush(pa, je);
+                pa = je;
+                je = ivv.interval_s >= j1 - je ? j1 : je + ivv.interval_s;
+            }
+        } while (IVL && j < j1);
     };
     // (fp32 single-site only: in the fp64 and per-site kernels, which sit at their
     // register bounds, the second copy adds spills)
@@ -2479,9 +2546,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
 // by 64-bit atomics at the end.  Round 4 measured workgroups looping over several tiles
 // (one flush per workgroup): a persistent grid 8-40 % slower on C3 / C4, four tiles per
 // workgroup 13 % slower on C3 (the inlined tile loop spills 45 VGPRs instead of 4).
-// the expansion's output argument: the traces, or the series for the variant that writes no trace
+// the expansion's output argument: the traces, or the series / the intervals for the variants that write no trace
 template <int OUT>
-using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView, TraceView>;
+using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView,
+                                   std::conditional_t<out_base(OUT) == OUT_INTERVALS, IntervalsView, TraceView>>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
                                                      uint32_t n, int64_t W0, uint32_t nsteps, int64_t utc0,
@@ -2493,10 +2561,13 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
                                                      const BlockDesc* __restrict__ desc, SegView sg, OutView<OUT> ov,
                                                      StatsView sv, const uint32_t* __restrict__ bperm)
 {
-    // the output view: the traces, or (OUT_SERIES, which writes no trace) the fleet series
+    // the output view: the traces, or (OUT_SERIES / OUT_INTERVALS, which write no trace) the
+    // fleet series / the interval table
     TraceView tr{};
     SeriesView se{};
+    IntervalsView ivv{};
     if constexpr (out_base(OUT) == OUT_SERIES) se = ov;
+    else if constexpr (out_base(OUT) == OUT_INTERVALS) ivv = ov;
     else tr = ov;
     SeriesLds* const ser_lds = series_lds<out_base(OUT) == OUT_SERIES>();
     if constexpr (out_base(OUT) == OUT_SERIES) {
@@ -2532,7 +2603,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     auto tile = [&](uint32_t b, uint32_t cblk) __attribute__((always_inline)) {
         expand_tile<R, OUT, SITES, WGT>(b, cblk, kp, dp, st, chain0, n, W0, nsteps, utc0, tab64, tab32, sun, events,
                                         n_events, desc, sg, tr, sv, lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab,
-                                        nd_tab, se, ser_lds);
+                                        nd_tab, se, ser_lds, ivv);
     };
     {   // grid: x = time block, y = chain block; the workgroup's tile (bs, cs)
         const uint32_t T = gridDim.x, CB = gridDim.y, L = blockIdx.x + T * blockIdx.y;
@@ -2669,7 +2740,9 @@ constexpr uint32_t FIX_RPW = 16;
 // SER: the engine has a fleet series (no traces then): column 0 of the second's row gets
 // q(pv fixed) - q(pv32), a two's-complement 64-bit add -- the meter, n_ok and the covered
 // count are final already
-template <bool SITES, bool SER = false>
+// IVL: the engine has interval metering (no traces either): the same difference goes to
+// column 0 of the cell (interval of the second, chain)
+template <bool SITES, bool SER = false, bool IVL = false>
 __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0, uint32_t n,
                                                     int64_t W0, uint32_t nsteps, int64_t utc0,
                                                     const double* __restrict__ tab64, const float* __restrict__ tab32,
@@ -2677,11 +2750,14 @@ __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kerne
                                                     const int2* __restrict__ events,
                                                     const uint32_t* __restrict__ n_events,
                                                     const BlockDesc* __restrict__ desc, SegView sg,
-                                                    std::conditional_t<SER, SeriesView, TraceView> ov, StatsView sv)
+                                                    std::conditional_t<SER, SeriesView, std::conditional_t<IVL, IntervalsView, TraceView>> ov,
+                                                    StatsView sv)
 {
     TraceView tr{};
     SeriesView se{};
+    IntervalsView ivv{};
     if constexpr (SER) se = ov;
+    else if constexpr (IVL) ivv = ov;
     else tr = ov;
     const uint32_t nrec = min(*sg.nfix, sg.fixcap);
     const int ne = (int)min(*n_events, ev_cap_dev(nsteps));
@@ -2723,7 +2799,7 @@ __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kerne
             const uint32_t cw = (lo & 3) == 0 ? fr.cov.x : ((lo & 3) == 1 ? fr.cov.y : ((lo & 3) == 2 ? fr.cov.z : fr.cov.w));
             const bool covered = (cw >> (i & 31)) & 1u;
             float pv32, meter, pv;
-            if (!redo_second<SITES>(kp, dp, st, sg, n, c, chain0, W0, utc0, j, db, covered, SER || sv.acc != nullptr, events, ne,
+            if (!redo_second<SITES>(kp, dp, st, sg, n, c, chain0, W0, utc0, j, db, covered, SER || IVL || sv.acc != nullptr, events, ne,
                                     tab64, tab32, sun, pv32, meter, pv))
                 continue;
             const float res = meter - pv, res32 = meter - pv32;   // second_body's residual
@@ -2734,6 +2810,11 @@ __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kerne
                 const long long dq = (long long)series_q<float>(pv) - (long long)series_q<float>(pv32);
                 const uint32_t g = se.group_chains ? c / se.group_chains : 0u;
                 if (dq) atomicAdd(se.sum + (size_t)g * se.gstride + (size_t)j * 4, (unsigned long long)dq);
+            }
+            if constexpr (IVL) {
+                const long long dq = (long long)series_q<float>(pv) - (long long)series_q<float>(pv32);
+                const uint32_t k = (ivv.rel0 + j) / ivv.interval_s;
+                if (dq) atomicAdd(ivv.sum + (size_t)k * 4 * ivv.ld + gid(kp.ids, c), (unsigned long long)dq);
             }
             if (sv.acc) {
                 atomicAdd(&sg.corr[c], (double)pv - (double)pv32);
@@ -3063,6 +3144,8 @@ struct tmh_engine {
     int last_expand = -1;     // TMH_OUT_* of the last expansion launched (tmh_engine_last_expand)
     bool has_series = false;  // tmh_set_series: every expansion adds its window to `series`
     tmh_series series{};
+    bool has_intervals = false;   // tmh_set_intervals: every expansion adds its window to `intervals`
+    tmh_intervals intervals{};
     // expansion tiles daylight blocks first (env TMH_EXP_COST_ORDER=1, A/B; measured slower in the C2
     // pipeline, round 6: 1.55 against 1.42-1.45 ms per step, same box -- launch order mixes the
     // store-bound night tiles with the VALU-bound day tiles over the launch)
@@ -3504,6 +3587,51 @@ static int check_series(const tmh_engine* eng, uint32_t n_chains, int64_t step0,
     return TMH_OK;
 }
 
+int tmh_set_intervals(struct tmh_engine* eng, const tmh_intervals* iv)
+{
+    if (iv) {   // (the struct first: a bad one is named whatever the engine)
+        if (!iv->sum || iv->n_steps == 0 || iv->ld == 0)
+            return fail(TMH_E_INVAL, "intervals need a buffer, n_steps > 0 and ld > 0");
+        if ((uintptr_t)iv->sum & 7) return fail(TMH_E_INVAL, "intervals buffer must be 8-byte aligned");
+        if (iv->interval_s == 0) return fail(TMH_E_INVAL, "intervals: interval_s must be >= 1");
+    }
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (!iv) {
+        eng->has_intervals = false;
+        eng->intervals = tmh_intervals{};
+        return TMH_OK;
+    }
+    eng->intervals = *iv;
+    eng->has_intervals = true;
+    return TMH_OK;
+}
+
+// A step / expansion with interval metering set: everything the kernels assume, checked
+// on the host before any launch (tmhpvsim.h, tmh_set_intervals).
+static int check_intervals(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps, const tmh_trace* trace)
+{
+    const tmh_intervals& iv = eng->intervals;
+    if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
+        return fail(TMH_E_INVAL, "intervals are set: no traces in the same call (a caller with traces can sum them)");
+    if (eng->has_series) return fail(TMH_E_INVAL, "intervals and a fleet series are both set: one of the two per engine");
+    if (eng->path != TMH_PATH_TIME_PARALLEL || eng->kp.rng_mode != TMH_RNG_KEYED)
+        return fail(TMH_E_INVAL, "intervals need the time-parallel path (keyed draws, no injected uniforms)");
+    if (step0 < iv.step0 || step0 + (int64_t)n_steps > iv.step0 + (int64_t)iv.n_steps)
+        return fail(TMH_E_INVAL, "window [%lld, +%u) outside the intervals [%lld, +%u)", (long long)step0, n_steps,
+                    (long long)iv.step0, iv.n_steps);
+    const uint32_t need = eng->kp.ids ? std::max(n_chains, eng->kp.ids_n) : n_chains;   // compacted: the full batch
+    if (iv.ld < need) return fail(TMH_E_INVAL, "intervals ld %llu < the batch's %u chains", (unsigned long long)iv.ld, need);
+    if (!iv.sum || ((uintptr_t)iv.sum & 7) || iv.interval_s == 0)
+        return fail(TMH_E_INVAL, "intervals need an 8-byte aligned buffer and interval_s >= 1");
+    // q's int32 range, as for the series: |pv| <= max(Paco, |Pnt|) (fp32 engines: as rounded to fp32)
+    const double paco = eng->kp.inverter[0], pnt = std::fabs(eng->kp.inverter[8]);
+    if (eng->kp.with_pv && !(paco < TMH_SERIES_MAX_W && (double)(float)paco < TMH_SERIES_MAX_W &&
+                             pnt < TMH_SERIES_MAX_W && (double)(float)pnt < TMH_SERIES_MAX_W))
+        return fail(TMH_E_INVAL, "inverter Paco %g W (|Pnt| %g W) not below TMH_SERIES_MAX_W %g W", paco, pnt,
+                    (double)TMH_SERIES_MAX_W);
+    return TMH_OK;
+}
+
 static int check_tables(const tmh_engine* eng, uint32_t n_chains)
 {
     if (eng->kp.ids) n_chains = std::max(n_chains, eng->kp.ids_n);
@@ -3711,8 +3839,10 @@ struct StepCtx {
     TraceView tv;
     StatsView sv;
     SeriesView sev;
+    IntervalsView ivv;
     bool f64() const { return eng->kp.precision == TMH_FP64; }
     bool series() const { return eng->has_series; }
+    bool intervals() const { return eng->has_intervals; }
     uint32_t cb() const { return (n_chains + 255) / 256; }   // 256-chain blocks
     int64_t utc0() const { return eng->gp.clock.utc0; }
 };
@@ -3796,7 +3926,8 @@ static int phase_expand(const StepCtx& c)
     const StatsView& sv = c.sv;
     hipEvent_t t_exp = eng->mark(c.s);
     const bool f64 = c.f64(), sites = eng->kp.sites != nullptr, no_stats = !sv.hist && !sv.acc;
-    int out = c.series() ? OUT_SERIES   // (no trace pointers: check_series)
+    int out = c.intervals() ? OUT_INTERVALS   // (no trace pointers, no series: check_intervals)
+              : c.series() ? OUT_SERIES   // (no trace pointers: check_series)
               : (no_stats && tv.pv && tv.meter && tv.residual && !tv.csi && !tv.covered) ? OUT_TRACE3
                     : (!tv.pv && !tv.meter && !tv.residual && !tv.csi && !tv.covered) ? OUT_STATS
                                                                                       : OUT_ANY;
@@ -3824,9 +3955,16 @@ static int phase_expand(const StepCtx& c)
         with_value<0, 1>(sites, [&](auto st) {
             constexpr bool F32 = sizeof(r) == 4, S = decltype(st)::value;
             auto traces = [&](auto okind) { launch(r, okind, st, tv); };
-            // the fleet series (+ statistics when given; the histogram bins as hist_bin_rt decides)
-            if (c.series()) launch(r, std::integral_constant<int, OUT_SERIES | OUT_BRT>{}, st, c.sev);
-            else if (b64) {
+            auto ivl = [&](auto okind) { launch(r, okind, st, c.ivv); };
+            if (c.intervals()) {
+                // interval metering (+ statistics when given, binned as the statistics-only kernel of the
+                // same histogram spec bins them: no per-second run-time choice)
+                if constexpr (F32) with_value<OUT_INTERVALS, OUT_INTERVALS | OUT_B64>(OUT_INTERVALS | (b64 ? OUT_B64 : 0), ivl);
+                else ivl(std::integral_constant<int, OUT_INTERVALS>{});
+            } else if (c.series()) {
+                // the fleet series (+ statistics when given; the histogram bins as hist_bin_rt decides)
+                launch(r, std::integral_constant<int, OUT_SERIES | OUT_BRT>{}, st, c.sev);
+            } else if (b64) {
                 if constexpr (F32) with_value<OUT_STATS | OUT_B64, OUT_ANY | OUT_B64>(out | OUT_B64, traces);
             } else if constexpr (S) with_value<OUT_STATS, OUT_ANY>(out, traces);
             else with_value<OUT_TRACE3, OUT_STATS, OUT_ANY>(out, traces);
@@ -3849,13 +3987,14 @@ static int phase_commit(const StepCtx& c, hipEvent_t t_step)
         // and the kernel two redo latencies long.)
         const uint32_t gx = (uint32_t)std::min<uint64_t>(65535, ((uint64_t)c.sg.fixcap + FIX_RPW - 1) / FIX_RPW);
         with_value<0, 1>(eng->kp.sites != nullptr, [&](auto st) {
-            auto launch = [&](auto ser, const auto& view) {   // the series (no traces then), or the traces
-                hipLaunchKernelGGL((fixup_kernel<decltype(st)::value, decltype(ser)::value>), dim3(gx), dim3(64), 0, c.s,
+            auto launch = [&](auto ser, auto ivl, const auto& view) {   // the series or the intervals (no traces then), or the traces
+                hipLaunchKernelGGL((fixup_kernel<decltype(st)::value, decltype(ser)::value, decltype(ivl)::value>), dim3(gx), dim3(64), 0, c.s,
                                    eng->kp, eng->dp, c.v, c.chain0, c.n_chains, c.step0, c.n_steps, c.utc0(), c.pv.tab64,
                                    c.pv.tab32, c.pv.sun, c.pv.events, c.pv.n_events, c.pv.desc, c.sg, view, c.sv);
             };
-            if (c.series()) launch(std::true_type{}, c.sev);
-            else launch(std::false_type{}, c.tv);
+            if (c.intervals()) launch(std::false_type{}, std::true_type{}, c.ivv);
+            else if (c.series()) launch(std::true_type{}, std::false_type{}, c.sev);
+            else launch(std::false_type{}, std::false_type{}, c.tv);
         });
         if (int rc = hip_check(hipGetLastError(), "fixup_kernel launch")) return rc;
     }
@@ -3890,6 +4029,8 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     const bool series = eng->has_series;   // (checked for a walk too: nothing of a refused window is launched)
     if (series)
         if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
+    if (eng->has_intervals)   // (a walk of a refused window is refused too)
+        if (int rc = check_intervals(eng, n_chains, step0, n_steps, trace)) return rc;
     const bool tp = eng->path == TMH_PATH_TIME_PARALLEL;
     if (tp && (!scratch || scratch_bytes < tmh_engine_scratch_bytes(eng, n_chains, n_steps)))
         return fail(TMH_E_INVAL, "scratch too small: %zu < %zu", scratch_bytes, tmh_engine_scratch_bytes(eng, n_chains, n_steps));
@@ -3917,6 +4058,9 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     if (series)   // the window's first row of group 0
         c.sev = SeriesView{reinterpret_cast<unsigned long long*>(eng->series.sum) + (size_t)(step0 - eng->series.step0) * 4,
                            (uint64_t)eng->series.n_steps * 4, eng->series.group_chains, 0u};
+    if (eng->has_intervals)   // the whole table; the window's first step from the intervals' origin
+        c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(eng->intervals.sum), eng->intervals.ld,
+                              (uint32_t)(step0 - eng->intervals.step0), eng->intervals.interval_s};
     if (!tp) {   // sequential path: one kernel, run by the expand phase (LDS: the histogram's 32-bit bins)
         if (!(phases & PH_EXPAND)) return TMH_OK;
         with_real(c.f64(), [&](auto r) {
@@ -4011,6 +4155,8 @@ int tmh_run(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_cha
         return fail(TMH_E_INVAL, "workspace too small: %zu < %zu", workspace_bytes, need);
     if (eng->has_series)   // before the plan's launches
         if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
+    if (eng->has_intervals)
+        if (int rc = check_intervals(eng, n_chains, step0, n_steps, trace)) return rc;
     if (int rc = tmh_plan(eng, step0, n_steps, workspace, stream)) return rc;
     return tmh_step(eng, state, chain0, n_chains, step0, n_steps, inj, trace, stats, workspace,
                     (char*)workspace + pb, workspace_bytes - pb, stream);

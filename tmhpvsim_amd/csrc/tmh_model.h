@@ -1524,13 +1524,17 @@ enum OutKind : int {
     OUT_TRACE3 = 1,   // exactly pv, meter, residual traces (the trace-mode hot path)
     OUT_STATS = 2,    // statistics only, no trace
     OUT_SERIES = 3,   // the fleet series (per-second integer sums over the chains), statistics if given, no trace
+    OUT_INTERVALS = 4,   // interval metering (per-chain integer sums per metering interval), statistics if given, no trace
     // flags on OUT_ANY / OUT_STATS (fp32 kernels): OUT_B64 bins in fp64 (a histogram spec whose
     // fp32 bin position is not accurate enough, StatsView::bin64); OUT_BRT decides at run time
     OUT_B64 = 8, OUT_BRT = 16
 };
 constexpr int out_base(int out) { return out & 7; }
 // no trace: the statistics-only expansion's workgroup shape
-constexpr bool out_no_trace(int out) { return out_base(out) == OUT_STATS || out_base(out) == OUT_SERIES; }
+constexpr bool out_no_trace(int out)
+{
+    return out_base(out) == OUT_STATS || out_base(out) == OUT_SERIES || out_base(out) == OUT_INTERVALS;
+}
 
 // The fleet series of a window (tmh_series): rows of 4 int64 per step, `sum` at the
 // window's first step of group 0, gstride elements from a group to the next.
@@ -1538,6 +1542,14 @@ struct SeriesView {
     unsigned long long* sum;
     uint64_t gstride;
     uint32_t group_chains, pad;   // 0: one group
+};
+// Interval metering of a window (tmh_intervals): cell (k, col, i) at sum[(k * 4 + col) * ld + i],
+// k = (rel0 + j) / interval_s for the window's step j (rel0: the window's first step from
+// the intervals' origin), i the chain's index in the full batch (gid).
+struct IntervalsView {
+    unsigned long long* sum;
+    uint64_t ld;
+    uint32_t rel0, interval_s;
 };
 constexpr int SERIES_FRAC_BITS = TMH_SERIES_FRAC_BITS;
 // q(v): v in units of 2^-SERIES_FRAC_BITS W, rounded half to even (|v| < TMH_SERIES_MAX_W: |q| < 2^26)

@@ -123,6 +123,9 @@ class BatchedSim:
         self._hist_spec = None
         self.series_raw = None    # int64 [n_groups, n_steps, 4] (enable_series)
         self._series = None
+        self.intervals_raw = None    # int64 [n_intervals, 4, n] (enable_intervals)
+        self._intervals = None
+        self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
             _lib.check(L.tmh_init(self._eng, _ptr(self.state), self.chain0, self.n,
@@ -208,6 +211,49 @@ class BatchedSim:
         _torch().cuda.synchronize(self.device)
         return to_watts(self.series_raw, bin_s=bin_s, mean=mean)
 
+    # ------------------------------------------------------------------ interval metering
+    def enable_intervals(self, n_steps, interval_s=900, step0=None, buffer=None):
+        """Accumulate every chain's interval meter (tmhpvsim_amd.intervals: exact per-chain
+        integer sums of pv and meter, the ok seconds and the covered seconds per metering
+        interval of interval_s seconds) over steps [step0, step0 + n_steps) in every later
+        run; step0 defaults to the current step.  Returns the raw int64 tensor
+        [n_intervals, 4, n].  buffer: an int64 device tensor of that shape to add into; it may
+        be a view with strides (4 ld, ld, 1) -- a column slice big[:, :, a:b] of a contiguous
+        table, so several batches or shards fill one table (ld is read from the strides); by
+        default a zeroed one.  Runs with intervals take no traces (trace=()) and no fleet
+        series; compaction is allowed.  n_steps=None switches the output off."""
+        from .intervals import n_intervals
+        torch = _torch()
+        if n_steps is None:
+            _lib.check(self.L.tmh_set_intervals(self._eng, None))
+            self.intervals_raw, self._intervals = None, None
+            return None
+        n_steps, interval_s = int(n_steps), int(interval_s)
+        if n_steps < 1 or interval_s < 1:
+            raise ValueError("enable_intervals: n_steps >= 1 and interval_s >= 1")
+        nk = n_intervals(n_steps, interval_s)
+        if buffer is None:
+            buffer = torch.zeros(nk, 4, self.n, dtype=torch.int64, device=self.device)
+        elif (buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (nk, 4, self.n)):
+            raise ValueError(f"intervals buffer must be an int64 [{nk}, 4, {self.n}] tensor on {self.device}")
+        ld = int(buffer.stride(1))
+        if ld < self.n or (self.n > 1 and buffer.stride(2) != 1) or (nk > 1 and buffer.stride(0) != 4 * ld):
+            raise ValueError(f"intervals buffer strides {tuple(buffer.stride())}: need (4 ld, ld, 1) with ld >= {self.n}")
+        st = _lib.Intervals(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
+        _lib.check(self.L.tmh_set_intervals(self._eng, C.byref(st)))
+        self.intervals_raw, self._intervals = buffer, st
+        return buffer
+
+    def intervals(self):
+        """The interval table in watts and watt-hours (intervals.to_watts of intervals_raw):
+        pv, meter, residual (means over the ok seconds), energy_wh_*, n_ok and the covered
+        fraction, [n_intervals, n] each."""
+        from .intervals import to_watts
+        if self.intervals_raw is None:
+            raise ValueError("no intervals: call enable_intervals first")
+        _torch().cuda.synchronize(self.device)
+        return to_watts(self.intervals_raw, self._intervals.interval_s, n_steps=self._intervals.n_steps)
+
     def guard_records(self):
         """Tests: the fp32 guard-band records (chain, 128-s block) of the last window that run()
         issued as a single tmh_run (tmh_test_guard_records; synchronises the device)."""
@@ -222,7 +268,9 @@ class BatchedSim:
 
     # ------------------------------------------------------------------ run
     def workspace(self, n_steps):
-        """plan + scratch of one window (tmh_engine_scratch_bytes: this engine's precision)"""
+        """plan + scratch of one window (tmh_engine_scratch_bytes: this engine's precision).  The
+        plan part is written by tmh_plan only and must stay unchanged until the window's expansion
+        has finished (the expansion reads it as constant memory)."""
         nb = self.L.tmh_plan_bytes(n_steps) + self.L.tmh_engine_scratch_bytes(self._eng, self.n, n_steps)
         return _torch().empty(nb, dtype=torch_uint8(), device=self.device)
 
@@ -233,7 +281,9 @@ class BatchedSim:
         on the chains still live at its start only (tmh_live_chains, tmh_state_move,
         tmh_set_chain_ids), so chains the reference's AssertionError ended
         (cloud_cover_binary.py:91; most C5 chains within the week) cost nothing
-        more.  Every chain's state and statistics come out as without compaction."""
+        more.  Every chain's state and statistics come out as without compaction.
+        `compact_slots` then lists the slots (chains still live) each window of the
+        run ran on, the first always n."""
         torch = _torch()
         n_steps = int(n_steps)
         trace = tuple(trace or ())
@@ -248,6 +298,15 @@ class BatchedSim:
             s0, sn = self._series.step0, self._series.n_steps
             if self.step < s0 or self.step + n_steps > s0 + sn:
                 raise ValueError(f"steps [{self.step}, +{n_steps}) outside the series [{s0}, +{sn})")
+        if self._intervals is not None:   # (likewise; compact=True is allowed)
+            if self._series is not None:
+                raise ValueError("interval metering and a fleet series are both enabled: one of the two per sim")
+            if trace:
+                raise ValueError("an interval-metering run takes no traces (trace=()): sum the traces instead "
+                                 "(intervals.from_traces)")
+            s0, sn = self._intervals.step0, self._intervals.n_steps
+            if self.step < s0 or self.step + n_steps > s0 + sn:
+                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the intervals [{s0}, +{sn})")
         if n_steps > ROLL_MAX:   # one rolling clock covers at most ROLL_MAX steps: run in pieces (same bits)
             res = out if out is not None else self._alloc(n_steps, trace)
             done = 0
@@ -300,6 +359,7 @@ class BatchedSim:
         ids = torch.empty(self.n, dtype=torch.int32, device=self.device)
         nlive = torch.zeros(1, dtype=torch.int32, device=self.device)
         tr = _lib.Trace(None, None, None, None, None, self.n)
+        self.compact_slots = []
         done = 0
         while done < n_steps:
             k = min(win, n_steps - done)
@@ -313,6 +373,7 @@ class BatchedSim:
                         _lib.check(L.tmh_state_move(self._eng, _ptr(self.state), self.n, _ptr(work), nl, _ptr(ids),
                                                     _ptr(nlive), nl, 0, s))
                         _lib.check(L.tmh_set_chain_ids(self._eng, _ptr(ids), self.n))
+            self.compact_slots.append(nl)
             try:
                 if nl:
                     _lib.check(L.tmh_run(self._eng, _ptr(cur), self.chain0, nl, self.step + done, k, None, C.byref(tr),
@@ -400,7 +461,10 @@ def run_windows(L, eng, state, chain0, n, wins, bufs, main, walk, trace_of, st, 
     The walk of a window needs only the previous window's walk (its end status,
     cloud-cover and wind pairs, call counts, sigma arrays), never its expansion, so the
     walks run back to back while the expansions follow; buffer w % K is reused once the
-    expansion of window w - K is done.  With small batches (the walk latency-bound) the
+    expansion of window w - K is done -- and not before: a window's plan is read-only from
+    its tmh_plan until its expansion has finished (the interval-metering expansion reads the
+    plan's geometry rows as constant memory), so nothing may rewrite a plan buffer under a
+    running expansion.  With small batches (the walk latency-bound) the
     per-window tail (fixup, commit, plan, draws) is off the walk's path.  trace_of(w):
     the window's tmh_trace; st: tmh_stats or None.  Same bits as one tmh_run per window."""
     import ctypes as C

@@ -310,6 +310,8 @@ class BatchPipeline:
         if self.nwin == 1 or sim.path != "time_parallel":
             for s0 in range(0, secs, win):   # windows: a trace window is overwritten by the next
                 w = min(win, secs - s0)
+                # (plan and step on one stream: the plan buffer is rewritten only after the step that
+                # read it -- a plan is read-only while its expansion runs, tmhpvsim.h tmh_plan)
                 _lib.check(L.tmh_plan(sim._eng, s0, w, self._p(cx.plan), cx.sptr))
                 _lib.check(L.tmh_step(sim._eng, self._p(cx.state), chain0, n, s0, w, None,
                                       C.byref(cx.tr), C.byref(cx.st) if cx.st is not None else None,
