@@ -26,7 +26,9 @@
  *    histogram (tmh_stats), the fleet series (tmh_series: per second, summed over
  *    the chains) and interval metering (tmh_intervals: per chain, summed over the
  *    seconds of each metering interval -- what a household's 15-minute or hourly
- *    meter reads; exact integer sums, compacted windows included).
+ *    meter reads; exact integer sums, compacted windows included) or, in its place,
+ *    the import / export registers (tmh_registers: the intervals' columns plus what
+ *    the chain drew from the grid and what it fed in, per interval).
  *  - `stream` is a hipStream_t (NULL = default stream); all work is enqueued
  *    asynchronously on it.  One engine per device; not re-entrant per engine.
  */
@@ -186,6 +188,26 @@ typedef struct tmh_intervals {
     uint64_t ld;         /* >= the batch's chains (>= n_full under tmh_set_chain_ids) */
 } tmh_intervals;
 
+/* Import / export registers: the two registers of a household's bidirectional meter (OBIS
+ * 1.8.0 / 2.8.0) beside the interval meter's columns -- how much each chain drew from the
+ * grid and how much it fed in, per metering interval.  Both are non-linear per second, so
+ * no other table gives them.  sum: device int64 [n_intervals][TMH_REGISTERS_COLS][ld],
+ * accumulated (the caller zero-initialises); cell (k, col, i) sits at sum[(k*6 + col)*ld + i].
+ * Columns 0-3 are tmh_intervals' (same q, TMH_SERIES_FRAC_BITS, ok rule, chain index and
+ * partial last interval); over the same ok seconds
+ *   [4] import = sum of max(q(meter) - q(pv), 0)   [5] export = sum of max(q(pv) - q(meter), 0)
+ * on the quantised integers (|q| < 2^26: a second's difference fits an int32), so for
+ * every cell [4] - [5] == [1] - [0] bit for bit, and the self-consumed energy is
+ * [0] - [5] == [1] - [4].  Integer sums, as the intervals'. */
+#define TMH_REGISTERS_COLS 6
+typedef struct tmh_registers {
+    int64_t* sum;        /* device int64 [n_intervals][6][ld], accumulated; the caller zero-initialises */
+    int64_t step0;       /* origin: step s belongs to interval (s - step0) / interval_s */
+    uint32_t n_steps;    /* steps covered; n_intervals = ceil(n_steps / interval_s); a last partial interval is kept */
+    uint32_t interval_s; /* >= 1, any value */
+    uint64_t ld;         /* >= the batch's chains (>= n_full under tmh_set_chain_ids) */
+} tmh_registers;
+
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
 /* TMH_SERIES_FRAC_BITS and TMH_SERIES_MAX_W as the library was built with them */
@@ -335,6 +357,17 @@ int tmh_set_series(struct tmh_engine* eng, const tmh_series* series);
  * is not below TMH_SERIES_MAX_W.  Compacted windows are accepted.  Per-chain statistics
  * and the histogram are accumulated beside the intervals when tmh_stats gives them. */
 int tmh_set_intervals(struct tmh_engine* eng, const tmh_intervals* iv);
+/* Import / export registers (tmh_registers above): every later expansion of this engine
+ * adds its window to rg->sum; NULL switches them off.  A setter like tmh_set_intervals,
+ * with the same refusals here (a NULL or misaligned sum, n_steps, ld or interval_s of 0)
+ * and at a step / expansion call or a walk of that window (TMH_E_INVAL, before any
+ * launch): a trace pointer; a fleet series or interval metering set too (the registers
+ * table holds the intervals' columns); the sequential path or injected uniforms; a window
+ * outside [step0, step0 + n_steps); ld too small; inverter Paco or |Pnt| not below
+ * TMH_SERIES_MAX_W.  Compacted windows are accepted.  Statistics and the histogram are
+ * accumulated beside the registers when tmh_stats gives them.  The table is final after
+ * the TMH_EXPAND_COMMIT half. */
+int tmh_set_registers(struct tmh_engine* eng, const tmh_registers* rg);
 /* Tests only: the fp32 guard-band records (chain, block) the last expansion on
  * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
  * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
@@ -439,7 +472,8 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * TMH_OUT_ANY (any trace fields and/or statistics), TMH_OUT_TRACE3 (exactly pv,
  * meter, residual, no statistics: the trace-mode hot path), TMH_OUT_STATS
  * (statistics only), TMH_OUT_SERIES (a fleet series, with or without statistics),
- * TMH_OUT_INTERVALS (interval metering, with or without statistics), plus
+ * TMH_OUT_INTERVALS (interval metering, with or without statistics),
+ * TMH_OUT_REGISTERS (import / export registers, with or without statistics), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
@@ -447,6 +481,7 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
 #define TMH_OUT_STATS 2
 #define TMH_OUT_SERIES 3
 #define TMH_OUT_INTERVALS 4
+#define TMH_OUT_REGISTERS 5
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

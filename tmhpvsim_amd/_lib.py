@@ -72,6 +72,13 @@ class Intervals(C.Structure):
                 ("ld", C.c_uint64)]
 
 
+class Registers(C.Structure):
+    """tmh_registers: int64 [n_intervals][6][ld] per-chain interval sums with the import and export registers
+    (tmh_set_registers); the fields of tmh_intervals."""
+    _fields_ = [("sum", C.c_void_p), ("step0", C.c_int64), ("n_steps", C.c_uint32), ("interval_s", C.c_uint32),
+                ("ld", C.c_uint64)]
+
+
 EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_bytes", "tmh_state_offsets", "tmh_plan_bytes",
            "tmh_scratch_bytes", "tmh_engine_scratch_bytes", "tmh_workspace_bytes", "tmh_engine_create", "tmh_engine_destroy", "tmh_engine_path",
            "tmh_init", "tmh_run", "tmh_plan", "tmh_step", "tmh_probe", "tmh_profile_enable", "tmh_profile_read",
@@ -79,13 +86,15 @@ EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_by
            "tmh_walk_part", "tmh_expand_part", "tmh_set_clock", "tmh_test_set_segment_capacity",
            "tmh_set_walk_chains_per_row", "tmh_set_walk_lanes", "tmh_set_chain_ids", "tmh_live_chains", "tmh_state_move",
            "tmh_stream_create_cus", "tmh_stream_destroy", "tmh_set_walk_order", "tmh_engine_last_expand",
-           "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals"]
+           "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals",
+           "tmh_set_registers"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
 EXPAND_KERNEL, EXPAND_COMMIT, EXPAND_MINUTES, EXPAND_NO_MINUTES = 1, 2, 4, 8
 OUT_ANY, OUT_TRACE3, OUT_STATS, OUT_SITES, OUT_FP64 = 0, 1, 2, 16, 32   # tmh_engine_last_expand
 OUT_SERIES = 3
 OUT_INTERVALS = 4
+OUT_REGISTERS = 5
 
 _lib = None
 
@@ -179,6 +188,8 @@ def load():
     L.tmh_set_series.restype = C.c_int
     L.tmh_set_intervals.argtypes = [p, C.POINTER(Intervals)]
     L.tmh_set_intervals.restype = C.c_int
+    L.tmh_set_registers.argtypes = [p, C.POINTER(Registers)]
+    L.tmh_set_registers.restype = C.c_int
     L.tmh_series_frac_bits.restype = C.c_int
     L.tmh_series_max_w.restype = C.c_double
     L.tmh_test_guard_records.argtypes = [p, p, u32, u32]

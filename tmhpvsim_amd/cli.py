@@ -13,6 +13,8 @@ tmhpvsim/metersim.py:79-95).
                                           [--start T --seconds S --seed K]
     python -m tmhpvsim_amd.cli intervals FILE --batch N --no-realtime --interval S [--all-chains NPZ]
                                               [--precision fp32|fp64] [--start T --seconds S --seed K]
+    python -m tmhpvsim_amd.cli registers FILE --batch N --no-realtime --interval S [--all-chains NPZ]
+                                              [--precision fp32|fp64] [--start T --seconds S --seed K]
 
 Without --batch the commands are the reference's AMQP pipelines (a fanout
 exchange carrying one JSON float per second, pvsim.py:43-84, metersim.py:13-62):
@@ -36,6 +38,12 @@ chain's exact energy per metering interval of --interval seconds; no per-second 
 leaves the GPU) and writes the reference's CSV columns `time,meter,pv,residual load` as
 interval means for chain 0, one row per interval stamped with the interval's start;
 --all-chains writes every chain's raw table and its watt / watt-hour arrays to an .npz.
+`registers` runs N chains with the import / export registers only (tmhpvsim_amd.registers:
+what each chain's bidirectional meter reads per interval of --interval seconds) and writes
+chain 0's intervals: header `time,import_wh,export_wh,pv_wh,meter_wh,self_wh,n_ok` -- the
+interval's start, the energy drawn from the grid, fed in, produced, consumed and
+self-consumed (Wh) and the ok seconds; --all-chains writes every chain's raw table and
+its watt / watt-hour arrays and ratios to an .npz.
 There is no CPU fallback: the batch mode fails if the engine cannot run.
 """
 from __future__ import annotations
@@ -101,6 +109,24 @@ def _intervals_run(n, start, seconds, seed, precision, interval_s):
     bad = int((sim.status() != 0).sum())
     if bad:
         logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their intervals hold the seconds before the fault")
+    return raw.cpu().numpy(), out
+
+
+def _registers_run(n, start, seconds, seed, precision, interval_s):
+    from .engine import BatchedSim
+    from .params import ModelParams
+    import torch
+    if not torch.cuda.is_available():
+        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
+    params = ModelParams(seed=int(seed))
+    sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
+                     horizon=int(seconds))
+    raw = sim.enable_registers(int(seconds), int(interval_s))
+    sim.run(int(seconds), trace=())
+    out = sim.registers()
+    bad = int((sim.status() != 0).sum())
+    if bad:
+        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their registers hold the seconds before the fault")
     return raw.cpu().numpy(), out
 
 
@@ -226,6 +252,32 @@ def intervals(file, amqp_url, exchange, verbose, realtime, batch, start, seconds
         for k in range(rows):
             w.writerow([t0 + dt.timedelta(seconds=k * interval_s), float(out["meter"][k, 0]), float(out["pv"][k, 0]),
                         float(out["residual"][k, 0])])
+    if all_chains:
+        import numpy as np
+        np.savez(all_chains, raw=raw, interval_s=interval_s, **out)
+    click.echo(f"wrote {rows} rows to {file}" + (f" and {batch} chains to {all_chains}" if all_chains else ""))
+
+
+@main.command()
+@click.argument("file")
+@common
+@click.option("--precision", type=click.Choice(["fp64", "fp32"]), default="fp32", help="batch mode arithmetic")
+@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
+              help="seconds per metering interval (a last partial interval is kept)")
+@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
+def registers(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, interval_s, all_chains):
+    """Import / export registers of chain 0 over --batch chains to FILE (CSV; registers-only engine run)."""
+    logging.basicConfig(level=logging.WARN - 10 * verbose)
+    _need_batch(realtime, batch, "registers")
+    raw, out = _registers_run(batch, start, seconds, seed, precision, interval_s)
+    t0 = dt.datetime.fromisoformat(str(start))
+    rows = raw.shape[0]
+    keys = ("energy_wh_import", "energy_wh_export", "energy_wh_pv", "energy_wh_meter", "energy_wh_self", "n_ok")
+    with open(file, mode="w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(["time", "import_wh", "export_wh", "pv_wh", "meter_wh", "self_wh", "n_ok"])
+        for k in range(rows):
+            w.writerow([t0 + dt.timedelta(seconds=k * interval_s)] + [float(out[key][k, 0]) for key in keys])
     if all_chains:
         import numpy as np
         np.savez(all_chains, raw=raw, interval_s=interval_s, **out)

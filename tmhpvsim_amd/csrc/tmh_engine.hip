@@ -47,7 +47,8 @@
 
 using namespace tmh;
 static_assert(OUT_ANY == TMH_OUT_ANY && OUT_TRACE3 == TMH_OUT_TRACE3 && OUT_STATS == TMH_OUT_STATS &&
-                  OUT_SERIES == TMH_OUT_SERIES && OUT_INTERVALS == TMH_OUT_INTERVALS,
+                  OUT_SERIES == TMH_OUT_SERIES && OUT_INTERVALS == TMH_OUT_INTERVALS &&
+                  OUT_REGISTERS == TMH_OUT_REGISTERS,
               "expansion variants: tmh_model.h and include/tmhpvsim.h agree");
 
 namespace {
@@ -2105,7 +2106,11 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                             const IntervalsView& ivv)
 {
     constexpr bool SER = out_base(OUT) == OUT_SERIES;
-    constexpr bool IVL = out_base(OUT) == OUT_INTERVALS;
+    // REG: the import / export registers -- the intervals' pieces, accumulators and flush, with
+    // one more accumulator and IVC = 6 columns per cell instead of 4
+    constexpr bool REG = out_base(OUT) == OUT_REGISTERS;
+    constexpr bool IVL = out_base(OUT) == OUT_INTERVALS || REG;
+    constexpr int IVC = interval_cols(OUT);
     const uint32_t c = cblk * blockDim.x + threadIdx.x;
     const bool live = c < n;
     const uint32_t j0 = b * BLOCK_STEPS, j1 = min(j0 + (uint32_t)BLOCK_STEPS, nsteps);
@@ -2267,7 +2272,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // 64-bit atomics, zeros skipped.  The two count columns come from what the block holds
     // already: ok seconds = the piece's overlap with [j0, fault_eff), covered seconds = the
     // popcount of the staged covered words over that overlap.
-    long long iv_pv = 0, iv_m = 0;
+    // The registers (REG) add one accumulator, the piece's export = sum of max(q(pv) - q(meter), 0)
+    // over its ok seconds; the import needs none: per second max(d, 0) - max(-d, 0) = d, so the
+    // piece's import is its export + (iv_m - iv_pv), exact in integers.
+    long long iv_pv = 0, iv_m = 0, iv_ex = 0;
     uint32_t iv_k = 0, iv_next = j1;
     if constexpr (IVL) {
         iv_k = __builtin_amdgcn_readfirstlane((ivv.rel0 + j0) / ivv.interval_s);
@@ -2276,9 +2284,14 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     }
     auto iv_flush = [&](uint32_t pa, uint32_t pb) __attribute__((always_inline)) {
         if (live) {
-            unsigned long long* cell = ivv.sum + (size_t)iv_k * 4 * ivv.ld + gid(kp.ids, c);
+            unsigned long long* cell = ivv.sum + (size_t)iv_k * IVC * ivv.ld + gid(kp.ids, c);
             if (iv_pv) atomicAdd(cell, (unsigned long long)iv_pv);
             if (iv_m) atomicAdd(cell + ivv.ld, (unsigned long long)iv_m);
+            if constexpr (REG) {
+                const long long im = iv_ex + (iv_m - iv_pv);
+                if (im) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)im);
+                if (iv_ex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)iv_ex);
+            }
             const int32_t lo = (int32_t)(pa - j0), hi = min((int32_t)pb, fault_eff) - (int32_t)j0;
             if (hi > lo) {
                 atomicAdd(cell + 2 * ivv.ld, (unsigned long long)(hi - lo));
@@ -2294,6 +2307,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         }
         iv_pv = 0;
         iv_m = 0;
+        if constexpr (REG) iv_ex = 0;
         ++iv_k;
     };
     // the second's outputs: NaN on a faulted lane, the guard-band bit, the trace stores or
@@ -2322,8 +2336,20 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         if constexpr (IVL) {
             // the lane's own sums of the piece; a second that is not ok adds 0, a night second's
             // literal pv = 0 nothing (lanes past the last chain are never flushed)
-            if (!(__builtin_constant_p(pv) && pv == R(0))) iv_pv += (long long)(ok ? series_q<R>(pv) : 0);
-            iv_m += (long long)(ok ? series_q<R>(meter) : 0);
+            if constexpr (!REG) {
+                if (!(__builtin_constant_p(pv) && pv == R(0))) iv_pv += (long long)(ok ? series_q<R>(pv) : 0);
+                iv_m += (long long)(ok ? series_q<R>(meter) : 0);
+            } else {
+                // the registers: the export beside them, from the same two integers; a night second's
+                // literal pv = 0 exports nothing (q(meter) >= 0: the meter is never negative)
+                const int qm = ok ? series_q<R>(meter) : 0;
+                iv_m += (long long)qm;
+                if (!(__builtin_constant_p(pv) && pv == R(0))) {
+                    const int qp = ok ? series_q<R>(pv) : 0;
+                    iv_pv += (long long)qp;
+                    iv_ex += (long long)max(qp - qm, 0);
+                }
+            }
         }
         if constexpr (!FF) {
             csi = ok ? csi : R(NAN);
@@ -2549,7 +2575,8 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
 // the expansion's output argument: the traces, or the series / the intervals for the variants that write no trace
 template <int OUT>
 using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView,
-                                   std::conditional_t<out_base(OUT) == OUT_INTERVALS, IntervalsView, TraceView>>;
+                                   std::conditional_t<out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS,
+                                                      IntervalsView, TraceView>>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
                                                      uint32_t n, int64_t W0, uint32_t nsteps, int64_t utc0,
@@ -2567,7 +2594,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     SeriesView se{};
     IntervalsView ivv{};
     if constexpr (out_base(OUT) == OUT_SERIES) se = ov;
-    else if constexpr (out_base(OUT) == OUT_INTERVALS) ivv = ov;
+    else if constexpr (out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS) ivv = ov;
     else tr = ov;
     SeriesLds* const ser_lds = series_lds<out_base(OUT) == OUT_SERIES>();
     if constexpr (out_base(OUT) == OUT_SERIES) {
@@ -2742,6 +2769,11 @@ constexpr uint32_t FIX_RPW = 16;
 // count are final already
 // IVL: the engine has interval metering (no traces either): the same difference goes to
 // column 0 of the cell (interval of the second, chain)
+// SER and IVL both (the third output without traces; the existing instantiations keep their
+// names): the import / export registers, REG below -- the intervals' view of cells of 6
+// columns: the held second's export changes by dex = max(q(pv) - q(meter), 0) -
+// max(q(pv32) - q(meter), 0) (column 5) and its import by dex - dq (column 4: import -
+// export = q(meter) - q(pv) per second)
 template <bool SITES, bool SER = false, bool IVL = false>
 __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0, uint32_t n,
                                                     int64_t W0, uint32_t nsteps, int64_t utc0,
@@ -2750,13 +2782,14 @@ __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kerne
                                                     const int2* __restrict__ events,
                                                     const uint32_t* __restrict__ n_events,
                                                     const BlockDesc* __restrict__ desc, SegView sg,
-                                                    std::conditional_t<SER, SeriesView, std::conditional_t<IVL, IntervalsView, TraceView>> ov,
+                                                    std::conditional_t<SER && !IVL, SeriesView, std::conditional_t<IVL, IntervalsView, TraceView>> ov,
                                                     StatsView sv)
 {
+    constexpr bool REG = SER && IVL;
     TraceView tr{};
     SeriesView se{};
     IntervalsView ivv{};
-    if constexpr (SER) se = ov;
+    if constexpr (SER && !IVL) se = ov;
     else if constexpr (IVL) ivv = ov;
     else tr = ov;
     const uint32_t nrec = min(*sg.nfix, sg.fixcap);
@@ -2806,7 +2839,7 @@ __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kerne
             const size_t o = (size_t)j * tr.ld + c;
             if (tr.pv) reinterpret_cast<float*>(tr.pv)[o] = pv;
             if (tr.residual) reinterpret_cast<float*>(tr.residual)[o] = res;
-            if constexpr (SER) {
+            if constexpr (SER && !IVL) {
                 const long long dq = (long long)series_q<float>(pv) - (long long)series_q<float>(pv32);
                 const uint32_t g = se.group_chains ? c / se.group_chains : 0u;
                 if (dq) atomicAdd(se.sum + (size_t)g * se.gstride + (size_t)j * 4, (unsigned long long)dq);
@@ -2814,7 +2847,16 @@ __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kerne
             if constexpr (IVL) {
                 const long long dq = (long long)series_q<float>(pv) - (long long)series_q<float>(pv32);
                 const uint32_t k = (ivv.rel0 + j) / ivv.interval_s;
-                if (dq) atomicAdd(ivv.sum + (size_t)k * 4 * ivv.ld + gid(kp.ids, c), (unsigned long long)dq);
+                if constexpr (!REG) {
+                    if (dq) atomicAdd(ivv.sum + (size_t)k * 4 * ivv.ld + gid(kp.ids, c), (unsigned long long)dq);
+                } else {
+                    const int qm = series_q<float>(meter);
+                    const long long dex = (long long)max(series_q<float>(pv) - qm, 0) - (long long)max(series_q<float>(pv32) - qm, 0);
+                    unsigned long long* cell = ivv.sum + (size_t)k * TMH_REGISTERS_COLS * ivv.ld + gid(kp.ids, c);
+                    if (dq) atomicAdd(cell, (unsigned long long)dq);
+                    if (dex - dq) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)(dex - dq));
+                    if (dex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)dex);
+                }
             }
             if (sv.acc) {
                 atomicAdd(&sg.corr[c], (double)pv - (double)pv32);
@@ -3146,6 +3188,8 @@ struct tmh_engine {
     tmh_series series{};
     bool has_intervals = false;   // tmh_set_intervals: every expansion adds its window to `intervals`
     tmh_intervals intervals{};
+    bool has_registers = false;   // tmh_set_registers: every expansion adds its window to `registers`
+    tmh_registers registers{};
     // expansion tiles daylight blocks first (env TMH_EXP_COST_ORDER=1, A/B; measured slower in the C2
     // pipeline, round 6: 1.55 against 1.42-1.45 ms per step, same box -- launch order mixes the
     // store-bound night tiles with the VALU-bound day tiles over the launch)
@@ -3606,23 +3650,47 @@ int tmh_set_intervals(struct tmh_engine* eng, const tmh_intervals* iv)
     return TMH_OK;
 }
 
-// A step / expansion with interval metering set: everything the kernels assume, checked
-// on the host before any launch (tmhpvsim.h, tmh_set_intervals).
-static int check_intervals(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps, const tmh_trace* trace)
+int tmh_set_registers(struct tmh_engine* eng, const tmh_registers* rg)
 {
-    const tmh_intervals& iv = eng->intervals;
+    if (rg) {   // (the struct first, as tmh_set_intervals)
+        if (!rg->sum || rg->n_steps == 0 || rg->ld == 0)
+            return fail(TMH_E_INVAL, "registers need a buffer, n_steps > 0 and ld > 0");
+        if ((uintptr_t)rg->sum & 7) return fail(TMH_E_INVAL, "registers buffer must be 8-byte aligned");
+        if (rg->interval_s == 0) return fail(TMH_E_INVAL, "registers: interval_s must be >= 1");
+    }
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (!rg) {
+        eng->has_registers = false;
+        eng->registers = tmh_registers{};
+        return TMH_OK;
+    }
+    eng->registers = *rg;
+    eng->has_registers = true;
+    return TMH_OK;
+}
+
+// A step / expansion with interval metering or the import / export registers set (`what`
+// names the table, `iv` describes it: the two structs have the same fields): everything
+// the kernels assume, checked on the host before any launch (tmhpvsim.h,
+// tmh_set_intervals, tmh_set_registers).
+static int check_interval_table(const tmh_engine* eng, const char* what, const tmh_intervals& iv, uint32_t n_chains,
+                                int64_t step0, uint32_t n_steps, const tmh_trace* trace)
+{
     if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
-        return fail(TMH_E_INVAL, "intervals are set: no traces in the same call (a caller with traces can sum them)");
-    if (eng->has_series) return fail(TMH_E_INVAL, "intervals and a fleet series are both set: one of the two per engine");
+        return fail(TMH_E_INVAL, "%s are set: no traces in the same call (a caller with traces can sum them)", what);
+    if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
+    if (eng->has_intervals && eng->has_registers)
+        return fail(TMH_E_INVAL, "registers and intervals are both set: one of the two per engine (the registers table holds "
+                                 "the intervals' columns)");
     if (eng->path != TMH_PATH_TIME_PARALLEL || eng->kp.rng_mode != TMH_RNG_KEYED)
-        return fail(TMH_E_INVAL, "intervals need the time-parallel path (keyed draws, no injected uniforms)");
+        return fail(TMH_E_INVAL, "%s need the time-parallel path (keyed draws, no injected uniforms)", what);
     if (step0 < iv.step0 || step0 + (int64_t)n_steps > iv.step0 + (int64_t)iv.n_steps)
-        return fail(TMH_E_INVAL, "window [%lld, +%u) outside the intervals [%lld, +%u)", (long long)step0, n_steps,
+        return fail(TMH_E_INVAL, "window [%lld, +%u) outside the %s [%lld, +%u)", (long long)step0, n_steps, what,
                     (long long)iv.step0, iv.n_steps);
     const uint32_t need = eng->kp.ids ? std::max(n_chains, eng->kp.ids_n) : n_chains;   // compacted: the full batch
-    if (iv.ld < need) return fail(TMH_E_INVAL, "intervals ld %llu < the batch's %u chains", (unsigned long long)iv.ld, need);
+    if (iv.ld < need) return fail(TMH_E_INVAL, "%s ld %llu < the batch's %u chains", what, (unsigned long long)iv.ld, need);
     if (!iv.sum || ((uintptr_t)iv.sum & 7) || iv.interval_s == 0)
-        return fail(TMH_E_INVAL, "intervals need an 8-byte aligned buffer and interval_s >= 1");
+        return fail(TMH_E_INVAL, "%s need an 8-byte aligned buffer and interval_s >= 1", what);
     // q's int32 range, as for the series: |pv| <= max(Paco, |Pnt|) (fp32 engines: as rounded to fp32)
     const double paco = eng->kp.inverter[0], pnt = std::fabs(eng->kp.inverter[8]);
     if (eng->kp.with_pv && !(paco < TMH_SERIES_MAX_W && (double)(float)paco < TMH_SERIES_MAX_W &&
@@ -3630,6 +3698,16 @@ static int check_intervals(const tmh_engine* eng, uint32_t n_chains, int64_t ste
         return fail(TMH_E_INVAL, "inverter Paco %g W (|Pnt| %g W) not below TMH_SERIES_MAX_W %g W", paco, pnt,
                     (double)TMH_SERIES_MAX_W);
     return TMH_OK;
+}
+static int check_intervals(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps, const tmh_trace* trace)
+{
+    return check_interval_table(eng, "intervals", eng->intervals, n_chains, step0, n_steps, trace);
+}
+static int check_registers(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps, const tmh_trace* trace)
+{
+    const tmh_registers& rg = eng->registers;
+    return check_interval_table(eng, "registers", tmh_intervals{rg.sum, rg.step0, rg.n_steps, rg.interval_s, rg.ld}, n_chains,
+                                step0, n_steps, trace);
 }
 
 static int check_tables(const tmh_engine* eng, uint32_t n_chains)
@@ -3843,6 +3921,7 @@ struct StepCtx {
     bool f64() const { return eng->kp.precision == TMH_FP64; }
     bool series() const { return eng->has_series; }
     bool intervals() const { return eng->has_intervals; }
+    bool registers() const { return eng->has_registers; }   // (ivv is their view then: never both, check_registers)
     uint32_t cb() const { return (n_chains + 255) / 256; }   // 256-chain blocks
     int64_t utc0() const { return eng->gp.clock.utc0; }
 };
@@ -3926,7 +4005,8 @@ static int phase_expand(const StepCtx& c)
     const StatsView& sv = c.sv;
     hipEvent_t t_exp = eng->mark(c.s);
     const bool f64 = c.f64(), sites = eng->kp.sites != nullptr, no_stats = !sv.hist && !sv.acc;
-    int out = c.intervals() ? OUT_INTERVALS   // (no trace pointers, no series: check_intervals)
+    int out = c.registers() ? OUT_REGISTERS   // (no trace pointers, no series, no intervals: check_registers)
+              : c.intervals() ? OUT_INTERVALS   // (no trace pointers, no series: check_intervals)
               : c.series() ? OUT_SERIES   // (no trace pointers: check_series)
               : (no_stats && tv.pv && tv.meter && tv.residual && !tv.csi && !tv.covered) ? OUT_TRACE3
                     : (!tv.pv && !tv.meter && !tv.residual && !tv.csi && !tv.covered) ? OUT_STATS
@@ -3956,7 +4036,11 @@ static int phase_expand(const StepCtx& c)
             constexpr bool F32 = sizeof(r) == 4, S = decltype(st)::value;
             auto traces = [&](auto okind) { launch(r, okind, st, tv); };
             auto ivl = [&](auto okind) { launch(r, okind, st, c.ivv); };
-            if (c.intervals()) {
+            if (c.registers()) {
+                // the import / export registers: instantiated as the intervals are
+                if constexpr (F32) with_value<OUT_REGISTERS, OUT_REGISTERS | OUT_B64>(OUT_REGISTERS | (b64 ? OUT_B64 : 0), ivl);
+                else ivl(std::integral_constant<int, OUT_REGISTERS>{});
+            } else if (c.intervals()) {
                 // interval metering (+ statistics when given, binned as the statistics-only kernel of the
                 // same histogram spec bins them: no per-second run-time choice)
                 if constexpr (F32) with_value<OUT_INTERVALS, OUT_INTERVALS | OUT_B64>(OUT_INTERVALS | (b64 ? OUT_B64 : 0), ivl);
@@ -3992,7 +4076,8 @@ static int phase_commit(const StepCtx& c, hipEvent_t t_step)
                                    eng->kp, eng->dp, c.v, c.chain0, c.n_chains, c.step0, c.n_steps, c.utc0(), c.pv.tab64,
                                    c.pv.tab32, c.pv.sun, c.pv.events, c.pv.n_events, c.pv.desc, c.sg, view, c.sv);
             };
-            if (c.intervals()) launch(std::false_type{}, std::true_type{}, c.ivv);
+            if (c.registers()) launch(std::true_type{}, std::true_type{}, c.ivv);   // (both: the registers)
+            else if (c.intervals()) launch(std::false_type{}, std::true_type{}, c.ivv);
             else if (c.series()) launch(std::true_type{}, std::false_type{}, c.sev);
             else launch(std::false_type{}, std::false_type{}, c.tv);
         });
@@ -4031,6 +4116,8 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
         if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
     if (eng->has_intervals)   // (a walk of a refused window is refused too)
         if (int rc = check_intervals(eng, n_chains, step0, n_steps, trace)) return rc;
+    if (eng->has_registers)
+        if (int rc = check_registers(eng, n_chains, step0, n_steps, trace)) return rc;
     const bool tp = eng->path == TMH_PATH_TIME_PARALLEL;
     if (tp && (!scratch || scratch_bytes < tmh_engine_scratch_bytes(eng, n_chains, n_steps)))
         return fail(TMH_E_INVAL, "scratch too small: %zu < %zu", scratch_bytes, tmh_engine_scratch_bytes(eng, n_chains, n_steps));
@@ -4061,6 +4148,9 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     if (eng->has_intervals)   // the whole table; the window's first step from the intervals' origin
         c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(eng->intervals.sum), eng->intervals.ld,
                               (uint32_t)(step0 - eng->intervals.step0), eng->intervals.interval_s};
+    if (eng->has_registers)   // likewise (cells of TMH_REGISTERS_COLS columns: the kernels' compile-time constant)
+        c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(eng->registers.sum), eng->registers.ld,
+                              (uint32_t)(step0 - eng->registers.step0), eng->registers.interval_s};
     if (!tp) {   // sequential path: one kernel, run by the expand phase (LDS: the histogram's 32-bit bins)
         if (!(phases & PH_EXPAND)) return TMH_OK;
         with_real(c.f64(), [&](auto r) {
@@ -4157,6 +4247,8 @@ int tmh_run(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_cha
         if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
     if (eng->has_intervals)
         if (int rc = check_intervals(eng, n_chains, step0, n_steps, trace)) return rc;
+    if (eng->has_registers)
+        if (int rc = check_registers(eng, n_chains, step0, n_steps, trace)) return rc;
     if (int rc = tmh_plan(eng, step0, n_steps, workspace, stream)) return rc;
     return tmh_step(eng, state, chain0, n_chains, step0, n_steps, inj, trace, stats, workspace,
                     (char*)workspace + pb, workspace_bytes - pb, stream);

@@ -125,6 +125,8 @@ class BatchedSim:
         self._series = None
         self.intervals_raw = None    # int64 [n_intervals, 4, n] (enable_intervals)
         self._intervals = None
+        self.registers_raw = None    # int64 [n_intervals, 6, n] (enable_registers)
+        self._registers = None
         self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
@@ -228,6 +230,9 @@ class BatchedSim:
             _lib.check(self.L.tmh_set_intervals(self._eng, None))
             self.intervals_raw, self._intervals = None, None
             return None
+        if self._registers is not None:
+            raise ValueError("the import / export registers are enabled: their table holds the intervals' columns "
+                             "(registers.to_intervals); one of the two per sim")
         n_steps, interval_s = int(n_steps), int(interval_s)
         if n_steps < 1 or interval_s < 1:
             raise ValueError("enable_intervals: n_steps >= 1 and interval_s >= 1")
@@ -253,6 +258,53 @@ class BatchedSim:
             raise ValueError("no intervals: call enable_intervals first")
         _torch().cuda.synchronize(self.device)
         return to_watts(self.intervals_raw, self._intervals.interval_s, n_steps=self._intervals.n_steps)
+
+    # ------------------------------------------------------------------ import / export registers
+    def enable_registers(self, n_steps, interval_s=900, step0=None, buffer=None):
+        """Accumulate every chain's bidirectional meter (tmhpvsim_amd.registers: the interval
+        meter's four columns plus the import and export registers -- the exact integer sums
+        of max(meter - pv, 0) and max(pv - meter, 0) -- per metering interval of interval_s
+        seconds) over steps [step0, step0 + n_steps) in every later run; step0 defaults to
+        the current step.  Returns the raw int64 tensor [n_intervals, 6, n].  buffer: an int64
+        device tensor of that shape to add into; it may be a view with strides (6 ld, ld, 1)
+        -- a column slice big[:, :, a:b] of a contiguous table (ld is read from the strides);
+        by default a zeroed one.  Runs with registers take no traces (trace=()), no fleet
+        series and no interval metering beside them; compaction is allowed.  n_steps=None
+        switches the output off."""
+        from .registers import COLUMNS, n_intervals
+        torch = _torch()
+        if n_steps is None:
+            _lib.check(self.L.tmh_set_registers(self._eng, None))
+            self.registers_raw, self._registers = None, None
+            return None
+        if self._intervals is not None:
+            raise ValueError("interval metering is enabled: the registers table holds the intervals' columns "
+                             "(registers.to_intervals); one of the two per sim")
+        n_steps, interval_s, nc = int(n_steps), int(interval_s), len(COLUMNS)
+        if n_steps < 1 or interval_s < 1:
+            raise ValueError("enable_registers: n_steps >= 1 and interval_s >= 1")
+        nk = n_intervals(n_steps, interval_s)
+        if buffer is None:
+            buffer = torch.zeros(nk, nc, self.n, dtype=torch.int64, device=self.device)
+        elif (buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (nk, nc, self.n)):
+            raise ValueError(f"registers buffer must be an int64 [{nk}, {nc}, {self.n}] tensor on {self.device}")
+        ld = int(buffer.stride(1))
+        if ld < self.n or (self.n > 1 and buffer.stride(2) != 1) or (nk > 1 and buffer.stride(0) != nc * ld):
+            raise ValueError(f"registers buffer strides {tuple(buffer.stride())}: need ({nc} ld, ld, 1) with ld >= {self.n}")
+        st = _lib.Registers(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
+        _lib.check(self.L.tmh_set_registers(self._eng, C.byref(st)))
+        self.registers_raw, self._registers = buffer, st
+        return buffer
+
+    def registers(self):
+        """The registers table in watts and watt-hours (registers.to_watts of registers_raw): the
+        intervals' keys plus energy_wh_import, energy_wh_export, energy_wh_self and the
+        self_consumption and self_sufficiency ratios, [n_intervals, n] each."""
+        from .registers import to_watts
+        if self.registers_raw is None:
+            raise ValueError("no registers: call enable_registers first")
+        _torch().cuda.synchronize(self.device)
+        return to_watts(self.registers_raw, self._registers.interval_s, n_steps=self._registers.n_steps)
 
     def guard_records(self):
         """Tests: the fp32 guard-band records (chain, 128-s block) of the last window that run()
@@ -307,6 +359,17 @@ class BatchedSim:
             s0, sn = self._intervals.step0, self._intervals.n_steps
             if self.step < s0 or self.step + n_steps > s0 + sn:
                 raise ValueError(f"steps [{self.step}, +{n_steps}) outside the intervals [{s0}, +{sn})")
+        if self._registers is not None:   # (likewise; compact=True is allowed)
+            if self._series is not None:
+                raise ValueError("the registers and a fleet series are both enabled: one of the two per sim")
+            if self._intervals is not None:
+                raise ValueError("the registers and interval metering are both enabled: one of the two per sim")
+            if trace:
+                raise ValueError("a registers run takes no traces (trace=()): sum the traces instead "
+                                 "(registers.from_traces)")
+            s0, sn = self._registers.step0, self._registers.n_steps
+            if self.step < s0 or self.step + n_steps > s0 + sn:
+                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the registers [{s0}, +{sn})")
         if n_steps > ROLL_MAX:   # one rolling clock covers at most ROLL_MAX steps: run in pieces (same bits)
             res = out if out is not None else self._alloc(n_steps, trace)
             done = 0
