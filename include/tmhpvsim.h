@@ -28,7 +28,9 @@
  *    seconds of each metering interval -- what a household's 15-minute or hourly
  *    meter reads; exact integer sums, compacted windows included) or, in its place,
  *    the import / export registers (tmh_registers: the intervals' columns plus what
- *    the chain drew from the grid and what it fed in, per interval).
+ *    the chain drew from the grid and what it fed in, per interval) or the demand
+ *    registers (tmh_demand: the registers' columns plus the peak import and the peak
+ *    feed-in of each interval and the second of each).
  *  - `stream` is a hipStream_t (NULL = default stream); all work is enqueued
  *    asynchronously on it.  One engine per device; not re-entrant per engine.
  */
@@ -208,6 +210,33 @@ typedef struct tmh_registers {
     uint64_t ld;         /* >= the batch's chains (>= n_full under tmh_set_chain_ids) */
 } tmh_registers;
 
+/* Demand registers: a meter's maximum-demand registers beside the import / export registers
+ * -- per chain and metering interval, the highest power drawn from the grid and the highest
+ * power fed in, and when each happened (what sizing a feeder, a transformer or an inverter
+ * asks for; a maximum is non-linear, so no other table gives it).  sum: device int64
+ * [n_intervals][TMH_DEMAND_COLS][ld]; cell (k, col, i) sits at sum[(k*8 + col)*ld + i]; the
+ * caller zero-initialises.  Columns 0-5 are tmh_registers' exactly (same q,
+ * TMH_SERIES_FRAC_BITS, ok rule, chain index, partial last interval and identity
+ * [4] - [5] == [1] - [0]).  Columns 6 and 7 are packed keys combined by maximum, within a call
+ * and across calls: for an ok second s of interval k, o = s - step0 - k * interval_s and
+ *   key(v, o) = (v << 32) | (0xFFFFFFFF - o)
+ *   [6] peak import: v = max(q(meter) - q(pv), 0)   [7] peak export: v = max(q(pv) - q(meter), 0)
+ * on the quantised integers (fp32 engines: the value after the fixup).  The cell is the
+ * maximum key over the interval's ok seconds: its high word is the peak in units of
+ * 2^-TMH_SERIES_FRAC_BITS W, its low word gives the earliest second at which it occurred
+ * (o = 0xFFFFFFFF - low word).  v < 2^27 and o < interval_s <= 2^32 - 1, so every ok second's
+ * key is positive (signed and unsigned maxima agree) and 0 means "no ok second": zero is the
+ * identity of the maximum.  An interval without feed-in has [7] = key(0, its first ok second):
+ * one rule, no special cases. */
+#define TMH_DEMAND_COLS 8
+typedef struct tmh_demand {
+    int64_t* sum;        /* device int64 [n_intervals][8][ld], accumulated / maximised; the caller zero-initialises */
+    int64_t step0;       /* origin: step s belongs to interval (s - step0) / interval_s */
+    uint32_t n_steps;    /* steps covered; n_intervals = ceil(n_steps / interval_s); a last partial interval is kept */
+    uint32_t interval_s; /* >= 1, any value */
+    uint64_t ld;         /* >= the batch's chains (>= n_full under tmh_set_chain_ids) */
+} tmh_demand;
+
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
 /* TMH_SERIES_FRAC_BITS and TMH_SERIES_MAX_W as the library was built with them */
@@ -368,6 +397,15 @@ int tmh_set_intervals(struct tmh_engine* eng, const tmh_intervals* iv);
  * accumulated beside the registers when tmh_stats gives them.  The table is final after
  * the TMH_EXPAND_COMMIT half. */
 int tmh_set_registers(struct tmh_engine* eng, const tmh_registers* rg);
+/* Demand registers (tmh_demand above): every later expansion of this engine adds its window
+ * to dm->sum (columns 0-5 by addition, 6 and 7 by maximum); NULL switches them off.  A setter
+ * like tmh_set_registers, with the same refusals here and at a step / expansion call or a
+ * walk of that window (TMH_E_INVAL, before any launch; the messages name "demand"), and also:
+ * a fleet series, interval metering or the import / export registers set too, in either
+ * order (the demand table holds their columns).  Compacted windows are accepted.  Statistics
+ * and the histogram are accumulated beside the table when tmh_stats gives them.  The table
+ * is final after the TMH_EXPAND_COMMIT half. */
+int tmh_set_demand(struct tmh_engine* eng, const tmh_demand* dm);
 /* Tests only: the fp32 guard-band records (chain, block) the last expansion on
  * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
  * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
@@ -473,7 +511,8 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * meter, residual, no statistics: the trace-mode hot path), TMH_OUT_STATS
  * (statistics only), TMH_OUT_SERIES (a fleet series, with or without statistics),
  * TMH_OUT_INTERVALS (interval metering, with or without statistics),
- * TMH_OUT_REGISTERS (import / export registers, with or without statistics), plus
+ * TMH_OUT_REGISTERS (import / export registers, with or without statistics),
+ * TMH_OUT_DEMAND (demand registers, with or without statistics), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
@@ -482,6 +521,7 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
 #define TMH_OUT_SERIES 3
 #define TMH_OUT_INTERVALS 4
 #define TMH_OUT_REGISTERS 5
+#define TMH_OUT_DEMAND 6
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

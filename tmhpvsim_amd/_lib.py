@@ -79,6 +79,13 @@ class Registers(C.Structure):
                 ("ld", C.c_uint64)]
 
 
+class Demand(C.Structure):
+    """tmh_demand: int64 [n_intervals][8][ld] per-chain registers with the peak import and peak export keys
+    (tmh_set_demand); the fields of tmh_registers."""
+    _fields_ = [("sum", C.c_void_p), ("step0", C.c_int64), ("n_steps", C.c_uint32), ("interval_s", C.c_uint32),
+                ("ld", C.c_uint64)]
+
+
 EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_bytes", "tmh_state_offsets", "tmh_plan_bytes",
            "tmh_scratch_bytes", "tmh_engine_scratch_bytes", "tmh_workspace_bytes", "tmh_engine_create", "tmh_engine_destroy", "tmh_engine_path",
            "tmh_init", "tmh_run", "tmh_plan", "tmh_step", "tmh_probe", "tmh_profile_enable", "tmh_profile_read",
@@ -87,7 +94,7 @@ EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_by
            "tmh_set_walk_chains_per_row", "tmh_set_walk_lanes", "tmh_set_chain_ids", "tmh_live_chains", "tmh_state_move",
            "tmh_stream_create_cus", "tmh_stream_destroy", "tmh_set_walk_order", "tmh_engine_last_expand",
            "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals",
-           "tmh_set_registers"]
+           "tmh_set_registers", "tmh_set_demand"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
 EXPAND_KERNEL, EXPAND_COMMIT, EXPAND_MINUTES, EXPAND_NO_MINUTES = 1, 2, 4, 8
@@ -95,6 +102,7 @@ OUT_ANY, OUT_TRACE3, OUT_STATS, OUT_SITES, OUT_FP64 = 0, 1, 2, 16, 32   # tmh_en
 OUT_SERIES = 3
 OUT_INTERVALS = 4
 OUT_REGISTERS = 5
+OUT_DEMAND = 6
 
 _lib = None
 
@@ -190,6 +198,8 @@ def load():
     L.tmh_set_intervals.restype = C.c_int
     L.tmh_set_registers.argtypes = [p, C.POINTER(Registers)]
     L.tmh_set_registers.restype = C.c_int
+    L.tmh_set_demand.argtypes = [p, C.POINTER(Demand)]
+    L.tmh_set_demand.restype = C.c_int
     L.tmh_series_frac_bits.restype = C.c_int
     L.tmh_series_max_w.restype = C.c_double
     L.tmh_test_guard_records.argtypes = [p, p, u32, u32]

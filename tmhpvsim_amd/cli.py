@@ -15,6 +15,8 @@ tmhpvsim/metersim.py:79-95).
                                               [--precision fp32|fp64] [--start T --seconds S --seed K]
     python -m tmhpvsim_amd.cli registers FILE --batch N --no-realtime --interval S [--all-chains NPZ]
                                               [--precision fp32|fp64] [--start T --seconds S --seed K]
+    python -m tmhpvsim_amd.cli demand FILE --batch N --no-realtime --interval S [--all-chains NPZ]
+                                           [--precision fp32|fp64] [--start T --seconds S --seed K]
 
 Without --batch the commands are the reference's AMQP pipelines (a fanout
 exchange carrying one JSON float per second, pvsim.py:43-84, metersim.py:13-62):
@@ -44,6 +46,12 @@ chain 0's intervals: header `time,import_wh,export_wh,pv_wh,meter_wh,self_wh,n_o
 interval's start, the energy drawn from the grid, fed in, produced, consumed and
 self-consumed (Wh) and the ok seconds; --all-chains writes every chain's raw table and
 its watt / watt-hour arrays and ratios to an .npz.
+`demand` runs N chains with the demand registers only (tmhpvsim_amd.demand: the registers
+plus each interval's peak import and peak feed-in and when each happened) and writes chain
+0's intervals: the `registers` columns plus `peak_import_w,t_peak_import_s,peak_export_w,
+t_peak_export_s` -- the highest power drawn from the grid and fed in (W) and the earliest
+second of the interval at which each occurred; --all-chains writes every chain's raw table
+and its arrays to an .npz.
 There is no CPU fallback: the batch mode fails if the engine cannot run.
 """
 from __future__ import annotations
@@ -124,6 +132,24 @@ def _registers_run(n, start, seconds, seed, precision, interval_s):
     raw = sim.enable_registers(int(seconds), int(interval_s))
     sim.run(int(seconds), trace=())
     out = sim.registers()
+    bad = int((sim.status() != 0).sum())
+    if bad:
+        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their registers hold the seconds before the fault")
+    return raw.cpu().numpy(), out
+
+
+def _demand_run(n, start, seconds, seed, precision, interval_s):
+    from .engine import BatchedSim
+    from .params import ModelParams
+    import torch
+    if not torch.cuda.is_available():
+        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
+    params = ModelParams(seed=int(seed))
+    sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
+                     horizon=int(seconds))
+    raw = sim.enable_demand(int(seconds), int(interval_s))
+    sim.run(int(seconds), trace=())
+    out = sim.demand()
     bad = int((sim.status() != 0).sum())
     if bad:
         logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their registers hold the seconds before the fault")
@@ -278,6 +304,37 @@ def registers(file, amqp_url, exchange, verbose, realtime, batch, start, seconds
         w.writerow(["time", "import_wh", "export_wh", "pv_wh", "meter_wh", "self_wh", "n_ok"])
         for k in range(rows):
             w.writerow([t0 + dt.timedelta(seconds=k * interval_s)] + [float(out[key][k, 0]) for key in keys])
+    if all_chains:
+        import numpy as np
+        np.savez(all_chains, raw=raw, interval_s=interval_s, **out)
+    click.echo(f"wrote {rows} rows to {file}" + (f" and {batch} chains to {all_chains}" if all_chains else ""))
+
+
+DEMAND_CSV = (("import_wh", "energy_wh_import"), ("export_wh", "energy_wh_export"), ("pv_wh", "energy_wh_pv"),
+              ("meter_wh", "energy_wh_meter"), ("self_wh", "energy_wh_self"), ("n_ok", "n_ok"),
+              ("peak_import_w", "peak_import"), ("t_peak_import_s", "t_peak_import"), ("peak_export_w", "peak_export"),
+              ("t_peak_export_s", "t_peak_export"))
+
+
+@main.command()
+@click.argument("file")
+@common
+@click.option("--precision", type=click.Choice(["fp64", "fp32"]), default="fp32", help="batch mode arithmetic")
+@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
+              help="seconds per metering interval (a last partial interval is kept)")
+@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
+def demand(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, interval_s, all_chains):
+    """Demand registers of chain 0 over --batch chains to FILE (CSV; demand-only engine run)."""
+    logging.basicConfig(level=logging.WARN - 10 * verbose)
+    _need_batch(realtime, batch, "demand")
+    raw, out = _demand_run(batch, start, seconds, seed, precision, interval_s)
+    t0 = dt.datetime.fromisoformat(str(start))
+    rows = raw.shape[0]
+    with open(file, mode="w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(["time"] + [name for name, _ in DEMAND_CSV])
+        for k in range(rows):
+            w.writerow([t0 + dt.timedelta(seconds=k * interval_s)] + [float(out[key][k, 0]) for _, key in DEMAND_CSV])
     if all_chains:
         import numpy as np
         np.savez(all_chains, raw=raw, interval_s=interval_s, **out)

@@ -48,7 +48,7 @@
 using namespace tmh;
 static_assert(OUT_ANY == TMH_OUT_ANY && OUT_TRACE3 == TMH_OUT_TRACE3 && OUT_STATS == TMH_OUT_STATS &&
                   OUT_SERIES == TMH_OUT_SERIES && OUT_INTERVALS == TMH_OUT_INTERVALS &&
-                  OUT_REGISTERS == TMH_OUT_REGISTERS,
+                  OUT_REGISTERS == TMH_OUT_REGISTERS && OUT_DEMAND == TMH_OUT_DEMAND,
               "expansion variants: tmh_model.h and include/tmhpvsim.h agree");
 
 namespace {
@@ -73,7 +73,12 @@ constexpr int EXP_WG_STATS = 512;
 //    round-4 PV-constant and table changes; 5 waves = 96 VGPRs spill 14 and run 6 % slower, round 5);
 //  per-chain sites (C5): 3 = at most 168 VGPRs (12-18 spilled): C5 5.36 against 4.47e10 at 2 (206 VGPRs,
 //    round 6, same box) and 4.37e10 at 4 (79 spilled); 2 was 35 % faster than 1 (round 2)
-constexpr int EXP_WAVES_TRACE = 7, EXP_WAVES_STATS = 6, EXP_WAVES_F64 = 4, EXP_WAVES_SITES = 3;
+//  fp32 single-site demand registers: 4 = at most 128 VGPRs (121 taken, no VGPR spills).  The two running
+//    peaks and their seconds are four more registers live across the piece loop; at 6 waves (80
+//    VGPRs) they turn 86 VGPR spill instructions into 234, inside the per-second loops, and the
+//    kernel ran 2.4 x the registers kernel (Demand registers).  512-chain workgroups are
+//    two waves per SIMD each, so 5 waves (96 VGPRs) would hold no more workgroups than 4.
+constexpr int EXP_WAVES_TRACE = 7, EXP_WAVES_STATS = 6, EXP_WAVES_F64 = 4, EXP_WAVES_SITES = 3, EXP_WAVES_DEMAND = 4;
 constexpr int FIX_WAVES_SITES = 1;   // min waves per SIMD of the per-site fixup (its fp64 redo recomputes the site's geometry)
 
 struct BlockDesc {                 // as of the step before the block start; -1 = none in the window
@@ -2025,7 +2030,11 @@ constexpr bool exp_hist_pack()
 template <typename R, int OUT, bool SITES>
 constexpr int exp_waves()
 {
-    return SITES ? EXP_WAVES_SITES : (sizeof(R) == 8 ? EXP_WAVES_F64 : (out_base(OUT) == OUT_TRACE3 ? EXP_WAVES_TRACE : EXP_WAVES_STATS));
+    return SITES                             ? EXP_WAVES_SITES
+           : sizeof(R) == 8                   ? EXP_WAVES_F64
+           : out_base(OUT) == OUT_TRACE3      ? EXP_WAVES_TRACE
+           : out_base(OUT) == OUT_DEMAND      ? EXP_WAVES_DEMAND
+                                              : EXP_WAVES_STATS;
 }
 // The fleet series' workgroup accumulator (OUT_SERIES only; a function-local LDS array,
 // so the other instantiations allocate none): per second of the tile the 64-bit sums of
@@ -2108,7 +2117,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     constexpr bool SER = out_base(OUT) == OUT_SERIES;
     // REG: the import / export registers -- the intervals' pieces, accumulators and flush, with
     // one more accumulator and IVC = 6 columns per cell instead of 4
-    constexpr bool REG = out_base(OUT) == OUT_REGISTERS;
+    // DEM: the demand registers -- the registers' six columns and two more per cell, the
+    // peak import and the peak export as packed keys (demand_key), combined by maximum
+    constexpr bool DEM = out_base(OUT) == OUT_DEMAND;
+    constexpr bool REG = out_base(OUT) == OUT_REGISTERS || DEM;
     constexpr bool IVL = out_base(OUT) == OUT_INTERVALS || REG;
     constexpr int IVC = interval_cols(OUT);
     const uint32_t c = cblk * blockDim.x + threadIdx.x;
@@ -2275,7 +2287,15 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // The registers (REG) add one accumulator, the piece's export = sum of max(q(pv) - q(meter), 0)
     // over its ok seconds; the import needs none: per second max(d, 0) - max(-d, 0) = d, so the
     // piece's import is its export + (iv_m - iv_pv), exact in integers.
+    // The demand registers (DEM) add the piece's largest import and largest export, each with the
+    // first second jb of the block that reached it (jb is wave-uniform: updated on strict >).
+    // Seconds that are not ok or are held (fixup_kernel issues their keys) count as 0, and 0 is
+    // also "none yet": a piece whose maximum stays 0 flushes key(0, its first ok second), which
+    // is that second's key if it is not held and below its final key if it is -- never above
+    // the cell's maximum.
     long long iv_pv = 0, iv_m = 0, iv_ex = 0;
+    int dm_im = 0, dm_ex = 0;
+    uint32_t dm_imj = 0, dm_exj = 0;
     uint32_t iv_k = 0, iv_next = j1;
     if constexpr (IVL) {
         iv_k = __builtin_amdgcn_readfirstlane((ivv.rel0 + j0) / ivv.interval_s);
@@ -2295,6 +2315,15 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             const int32_t lo = (int32_t)(pa - j0), hi = min((int32_t)pb, fault_eff) - (int32_t)j0;
             if (hi > lo) {
                 atomicAdd(cell + 2 * ivv.ld, (unsigned long long)(hi - lo));
+                if constexpr (DEM) {
+                    // offset of the block's first second in interval iv_k (mod 2^32: the piece's
+                    // seconds lie in the interval, so ob + jb is their offset)
+                    const uint32_t ob = ivv.rel0 + j0 - iv_k * ivv.interval_s;
+                    const unsigned long long kim = demand_key((uint32_t)dm_im, ob + (dm_im > 0 ? dm_imj : (uint32_t)lo));
+                    const unsigned long long kex = demand_key((uint32_t)dm_ex, ob + (dm_ex > 0 ? dm_exj : (uint32_t)lo));
+                    __hip_atomic_fetch_max(cell + 6 * ivv.ld, kim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_max(cell + 7 * ivv.ld, kex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
                 uint32_t nc = 0;
 #pragma unroll
                 for (int w = 0; w < 4; ++w) {
@@ -2308,6 +2337,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         iv_pv = 0;
         iv_m = 0;
         if constexpr (REG) iv_ex = 0;
+        if constexpr (DEM) {
+            dm_im = 0;
+            dm_ex = 0;
+        }
         ++iv_k;
     };
     // the second's outputs: NaN on a faulted lane, the guard-band bit, the trace stores or
@@ -2348,6 +2381,16 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                     const int qp = ok ? series_q<R>(pv) : 0;
                     iv_pv += (long long)qp;
                     iv_ex += (long long)max(qp - qm, 0);
+                    if constexpr (DEM) {   // the second's import and export (0 when held or not ok)
+                        const int vi = held ? 0 : max(qm - qp, 0), ve = held ? 0 : max(qp - qm, 0);
+                        dm_imj = vi > dm_im ? jb : dm_imj;
+                        dm_im = max(vi, dm_im);
+                        dm_exj = ve > dm_ex ? jb : dm_exj;
+                        dm_ex = max(ve, dm_ex);
+                    }
+                } else if constexpr (DEM) {   // night: the import is the meter, never held; no export
+                    dm_imj = qm > dm_im ? jb : dm_imj;
+                    dm_im = max(qm, dm_im);
                 }
             }
         }
@@ -2575,7 +2618,8 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
 // the expansion's output argument: the traces, or the series / the intervals for the variants that write no trace
 template <int OUT>
 using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView,
-                                   std::conditional_t<out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS,
+                                   std::conditional_t<out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS ||
+                                                          out_base(OUT) == OUT_DEMAND,
                                                       IntervalsView, TraceView>>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
@@ -2594,7 +2638,8 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     SeriesView se{};
     IntervalsView ivv{};
     if constexpr (out_base(OUT) == OUT_SERIES) se = ov;
-    else if constexpr (out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS) ivv = ov;
+    else if constexpr (out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS || out_base(OUT) == OUT_DEMAND)
+        ivv = ov;
     else tr = ov;
     SeriesLds* const ser_lds = series_lds<out_base(OUT) == OUT_SERIES>();
     if constexpr (out_base(OUT) == OUT_SERIES) {
@@ -2774,6 +2819,12 @@ constexpr uint32_t FIX_RPW = 16;
 // columns: the held second's export changes by dex = max(q(pv) - q(meter), 0) -
 // max(q(pv32) - q(meter), 0) (column 5) and its import by dex - dq (column 4: import -
 // export = q(meter) - q(pv) per second)
+// DEM (fixup_demand_kernel, with SER and IVL: the existing kernels keep their names): the
+// demand registers -- the registers' three corrections on cells of 8 columns, and the held
+// second's two keys (the expansion left held seconds out of the peaks) by atomic maximum,
+// unconditionally: a held second may be its interval's first ok second, or the only one
+template <bool SER, bool IVL>
+using FixView = std::conditional_t<SER && !IVL, SeriesView, std::conditional_t<IVL, IntervalsView, TraceView>>;
 template <bool SITES, bool SER = false, bool IVL = false>
 __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0, uint32_t n,
                                                     int64_t W0, uint32_t nsteps, int64_t utc0,
@@ -2782,92 +2833,24 @@ __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kerne
                                                     const int2* __restrict__ events,
                                                     const uint32_t* __restrict__ n_events,
                                                     const BlockDesc* __restrict__ desc, SegView sg,
-                                                    std::conditional_t<SER && !IVL, SeriesView, std::conditional_t<IVL, IntervalsView, TraceView>> ov,
-                                                    StatsView sv)
+                                                    FixView<SER, IVL> ov, StatsView sv)
 {
-    constexpr bool REG = SER && IVL;
-    TraceView tr{};
-    SeriesView se{};
-    IntervalsView ivv{};
-    if constexpr (SER && !IVL) se = ov;
-    else if constexpr (IVL) ivv = ov;
-    else tr = ov;
-    const uint32_t nrec = min(*sg.nfix, sg.fixcap);
-    const int ne = (int)min(*n_events, ev_cap_dev(nsteps));
-    const uint32_t lane = threadIdx.x;   // one wave per workgroup
-    for (uint32_t r0 = blockIdx.x * FIX_RPW; r0 < nrec; r0 += gridDim.x * FIX_RPW) {   // wave-uniform
-        const uint32_t rw = r0 + (lane >> 2);
-        uint32_t word = 0;
-        if (rw < nrec) {
-            const uint4 m = sg.fix[rw].mask;
-            const uint32_t w = lane & 3;
-            word = w == 0 ? m.x : (w == 1 ? m.y : (w == 2 ? m.z : m.w));
-        }
-        uint32_t cum = __popc(word);   // inclusive prefix sum over the wave's words
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t u = __shfl_up(cum, d, 64);
-            if (lane >= (uint32_t)d) cum += u;
-        }
-        const uint32_t total = __builtin_amdgcn_readfirstlane(__shfl(cum, 63, 64));
-        for (uint32_t k0 = 0; k0 < total; k0 += 64) {   // wave-uniform
-            const uint32_t k = k0 + lane;
-            // the word holding flagged second k: the first q with cum[q] > k (every lane
-            // takes part in the shuffles; lanes past the total search for nothing)
-            uint32_t lo = 0;
-#pragma unroll
-            for (uint32_t h = 32; h; h >>= 1)
-                if (__shfl(cum, (int)(lo + h - 1), 64) <= k) lo += h;
-            const uint32_t wq = __shfl(word, (int)lo, 64);
-            const uint32_t cq = __shfl(cum, (int)lo, 64);
-            if (k >= total) continue;
-            uint32_t m = wq;
-            for (uint32_t rank = k - (cq - __popc(wq)); rank; --rank) m &= m - 1;   // drop the lower set bits
-            const uint32_t i = (lo & 3) * 32 + (uint32_t)(__ffs(m) - 1);   // second of the record's block
-            const FixRec& fr = sg.fix[r0 + (lo >> 2)];
-            const uint32_t c = fr.c;
-            if (c >= n || fr.b >= sg.nblk) continue;   // (never appended: the expansion records live chains only)
-            const BlockDesc db = desc[fr.b];
-            const uint32_t j = fr.b * BLOCK_STEPS + i;
-            const uint32_t cw = (lo & 3) == 0 ? fr.cov.x : ((lo & 3) == 1 ? fr.cov.y : ((lo & 3) == 2 ? fr.cov.z : fr.cov.w));
-            const bool covered = (cw >> (i & 31)) & 1u;
-            float pv32, meter, pv;
-            if (!redo_second<SITES>(kp, dp, st, sg, n, c, chain0, W0, utc0, j, db, covered, SER || IVL || sv.acc != nullptr, events, ne,
-                                    tab64, tab32, sun, pv32, meter, pv))
-                continue;
-            const float res = meter - pv, res32 = meter - pv32;   // second_body's residual
-            const size_t o = (size_t)j * tr.ld + c;
-            if (tr.pv) reinterpret_cast<float*>(tr.pv)[o] = pv;
-            if (tr.residual) reinterpret_cast<float*>(tr.residual)[o] = res;
-            if constexpr (SER && !IVL) {
-                const long long dq = (long long)series_q<float>(pv) - (long long)series_q<float>(pv32);
-                const uint32_t g = se.group_chains ? c / se.group_chains : 0u;
-                if (dq) atomicAdd(se.sum + (size_t)g * se.gstride + (size_t)j * 4, (unsigned long long)dq);
-            }
-            if constexpr (IVL) {
-                const long long dq = (long long)series_q<float>(pv) - (long long)series_q<float>(pv32);
-                const uint32_t k = (ivv.rel0 + j) / ivv.interval_s;
-                if constexpr (!REG) {
-                    if (dq) atomicAdd(ivv.sum + (size_t)k * 4 * ivv.ld + gid(kp.ids, c), (unsigned long long)dq);
-                } else {
-                    const int qm = series_q<float>(meter);
-                    const long long dex = (long long)max(series_q<float>(pv) - qm, 0) - (long long)max(series_q<float>(pv32) - qm, 0);
-                    unsigned long long* cell = ivv.sum + (size_t)k * TMH_REGISTERS_COLS * ivv.ld + gid(kp.ids, c);
-                    if (dq) atomicAdd(cell, (unsigned long long)dq);
-                    if (dex - dq) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)(dex - dq));
-                    if (dex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)dex);
-                }
-            }
-            if (sv.acc) {
-                atomicAdd(&sg.corr[c], (double)pv - (double)pv32);
-                atomicAdd(&sg.corr[(size_t)n + c], (double)res - (double)res32);
-                __hip_atomic_fetch_max(sg.acc_mx + c, max_key((double)res), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (sv.hist) {
-                atomicAdd((unsigned long long*)&sv.hist[hist_bin_rt<float>(sv, res)], 1ull);
-            }
-        }
-    }
+    constexpr bool DEM = false;
+#include "tmh_fixup_body.inc"
+}
+// (SER, IVL, DEM: always true -- template parameters so that the body's discarded branches stay uninstantiated)
+template <bool SITES, bool SER = true, bool IVL = true, bool DEM = true>
+__global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_demand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0, uint32_t n,
+                                                    int64_t W0, uint32_t nsteps, int64_t utc0,
+                                                    const double* __restrict__ tab64, const float* __restrict__ tab32,
+                                                    const double* __restrict__ sun,
+                                                    const int2* __restrict__ events,
+                                                    const uint32_t* __restrict__ n_events,
+                                                    const BlockDesc* __restrict__ desc, SegView sg,
+                                                    FixView<SER, IVL> ov, StatsView sv)
+{
+    static_assert(SER && IVL && DEM, "the demand registers' fixup");
+#include "tmh_fixup_body.inc"
 }
 
 // The window's end, one work-item per chain, after the expansion (and the fixup):
@@ -3190,6 +3173,8 @@ struct tmh_engine {
     tmh_intervals intervals{};
     bool has_registers = false;   // tmh_set_registers: every expansion adds its window to `registers`
     tmh_registers registers{};
+    bool has_demand = false;      // tmh_set_demand: every expansion adds its window to `demand`
+    tmh_demand demand{};
     // expansion tiles daylight blocks first (env TMH_EXP_COST_ORDER=1, A/B; measured slower in the C2
     // pipeline, round 6: 1.55 against 1.42-1.45 ms per step, same box -- launch order mixes the
     // store-bound night tiles with the VALU-bound day tiles over the launch)
@@ -3669,6 +3654,25 @@ int tmh_set_registers(struct tmh_engine* eng, const tmh_registers* rg)
     return TMH_OK;
 }
 
+int tmh_set_demand(struct tmh_engine* eng, const tmh_demand* dm)
+{
+    if (dm) {   // (the struct first, as tmh_set_intervals)
+        if (!dm->sum || dm->n_steps == 0 || dm->ld == 0)
+            return fail(TMH_E_INVAL, "demand registers need a buffer, n_steps > 0 and ld > 0");
+        if ((uintptr_t)dm->sum & 7) return fail(TMH_E_INVAL, "demand registers buffer must be 8-byte aligned");
+        if (dm->interval_s == 0) return fail(TMH_E_INVAL, "demand registers: interval_s must be >= 1");
+    }
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (!dm) {
+        eng->has_demand = false;
+        eng->demand = tmh_demand{};
+        return TMH_OK;
+    }
+    eng->demand = *dm;
+    eng->has_demand = true;
+    return TMH_OK;
+}
+
 // A step / expansion with interval metering or the import / export registers set (`what`
 // names the table, `iv` describes it: the two structs have the same fields): everything
 // the kernels assume, checked on the host before any launch (tmhpvsim.h,
@@ -3682,6 +3686,10 @@ static int check_interval_table(const tmh_engine* eng, const char* what, const t
     if (eng->has_intervals && eng->has_registers)
         return fail(TMH_E_INVAL, "registers and intervals are both set: one of the two per engine (the registers table holds "
                                  "the intervals' columns)");
+    if (eng->has_demand && (eng->has_intervals || eng->has_registers))
+        return fail(TMH_E_INVAL, "demand registers and %s are both set: one of the two per engine (the demand table holds "
+                                 "the registers' and the intervals' columns)",
+                    eng->has_registers ? "the import / export registers" : "interval metering");
     if (eng->path != TMH_PATH_TIME_PARALLEL || eng->kp.rng_mode != TMH_RNG_KEYED)
         return fail(TMH_E_INVAL, "%s need the time-parallel path (keyed draws, no injected uniforms)", what);
     if (step0 < iv.step0 || step0 + (int64_t)n_steps > iv.step0 + (int64_t)iv.n_steps)
@@ -3707,6 +3715,13 @@ static int check_registers(const tmh_engine* eng, uint32_t n_chains, int64_t ste
 {
     const tmh_registers& rg = eng->registers;
     return check_interval_table(eng, "registers", tmh_intervals{rg.sum, rg.step0, rg.n_steps, rg.interval_s, rg.ld}, n_chains,
+                                step0, n_steps, trace);
+}
+
+static int check_demand(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps, const tmh_trace* trace)
+{
+    const tmh_demand& dm = eng->demand;
+    return check_interval_table(eng, "demand registers", tmh_intervals{dm.sum, dm.step0, dm.n_steps, dm.interval_s, dm.ld}, n_chains,
                                 step0, n_steps, trace);
 }
 
@@ -3922,6 +3937,7 @@ struct StepCtx {
     bool series() const { return eng->has_series; }
     bool intervals() const { return eng->has_intervals; }
     bool registers() const { return eng->has_registers; }   // (ivv is their view then: never both, check_registers)
+    bool demand() const { return eng->has_demand; }         // (likewise: check_demand)
     uint32_t cb() const { return (n_chains + 255) / 256; }   // 256-chain blocks
     int64_t utc0() const { return eng->gp.clock.utc0; }
 };
@@ -4005,7 +4021,8 @@ static int phase_expand(const StepCtx& c)
     const StatsView& sv = c.sv;
     hipEvent_t t_exp = eng->mark(c.s);
     const bool f64 = c.f64(), sites = eng->kp.sites != nullptr, no_stats = !sv.hist && !sv.acc;
-    int out = c.registers() ? OUT_REGISTERS   // (no trace pointers, no series, no intervals: check_registers)
+    int out = c.demand() ? OUT_DEMAND   // (no trace pointers, no series, intervals or registers: check_demand)
+              : c.registers() ? OUT_REGISTERS   // (no trace pointers, no series, no intervals: check_registers)
               : c.intervals() ? OUT_INTERVALS   // (no trace pointers, no series: check_intervals)
               : c.series() ? OUT_SERIES   // (no trace pointers: check_series)
               : (no_stats && tv.pv && tv.meter && tv.residual && !tv.csi && !tv.covered) ? OUT_TRACE3
@@ -4036,7 +4053,11 @@ static int phase_expand(const StepCtx& c)
             constexpr bool F32 = sizeof(r) == 4, S = decltype(st)::value;
             auto traces = [&](auto okind) { launch(r, okind, st, tv); };
             auto ivl = [&](auto okind) { launch(r, okind, st, c.ivv); };
-            if (c.registers()) {
+            if (c.demand()) {
+                // the demand registers: instantiated as the registers are
+                if constexpr (F32) with_value<OUT_DEMAND, OUT_DEMAND | OUT_B64>(OUT_DEMAND | (b64 ? OUT_B64 : 0), ivl);
+                else ivl(std::integral_constant<int, OUT_DEMAND>{});
+            } else if (c.registers()) {
                 // the import / export registers: instantiated as the intervals are
                 if constexpr (F32) with_value<OUT_REGISTERS, OUT_REGISTERS | OUT_B64>(OUT_REGISTERS | (b64 ? OUT_B64 : 0), ivl);
                 else ivl(std::integral_constant<int, OUT_REGISTERS>{});
@@ -4076,7 +4097,11 @@ static int phase_commit(const StepCtx& c, hipEvent_t t_step)
                                    eng->kp, eng->dp, c.v, c.chain0, c.n_chains, c.step0, c.n_steps, c.utc0(), c.pv.tab64,
                                    c.pv.tab32, c.pv.sun, c.pv.events, c.pv.n_events, c.pv.desc, c.sg, view, c.sv);
             };
-            if (c.registers()) launch(std::true_type{}, std::true_type{}, c.ivv);   // (both: the registers)
+            if (c.demand())
+                hipLaunchKernelGGL((fixup_demand_kernel<decltype(st)::value>), dim3(gx), dim3(64), 0, c.s, eng->kp, eng->dp, c.v,
+                                   c.chain0, c.n_chains, c.step0, c.n_steps, c.utc0(), c.pv.tab64, c.pv.tab32, c.pv.sun,
+                                   c.pv.events, c.pv.n_events, c.pv.desc, c.sg, c.ivv, c.sv);
+            else if (c.registers()) launch(std::true_type{}, std::true_type{}, c.ivv);   // (both: the registers)
             else if (c.intervals()) launch(std::false_type{}, std::true_type{}, c.ivv);
             else if (c.series()) launch(std::true_type{}, std::false_type{}, c.sev);
             else launch(std::false_type{}, std::false_type{}, c.tv);
@@ -4118,6 +4143,8 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
         if (int rc = check_intervals(eng, n_chains, step0, n_steps, trace)) return rc;
     if (eng->has_registers)
         if (int rc = check_registers(eng, n_chains, step0, n_steps, trace)) return rc;
+    if (eng->has_demand)
+        if (int rc = check_demand(eng, n_chains, step0, n_steps, trace)) return rc;
     const bool tp = eng->path == TMH_PATH_TIME_PARALLEL;
     if (tp && (!scratch || scratch_bytes < tmh_engine_scratch_bytes(eng, n_chains, n_steps)))
         return fail(TMH_E_INVAL, "scratch too small: %zu < %zu", scratch_bytes, tmh_engine_scratch_bytes(eng, n_chains, n_steps));
@@ -4151,6 +4178,9 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     if (eng->has_registers)   // likewise (cells of TMH_REGISTERS_COLS columns: the kernels' compile-time constant)
         c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(eng->registers.sum), eng->registers.ld,
                               (uint32_t)(step0 - eng->registers.step0), eng->registers.interval_s};
+    if (eng->has_demand)      // likewise (cells of TMH_DEMAND_COLS columns)
+        c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(eng->demand.sum), eng->demand.ld,
+                              (uint32_t)(step0 - eng->demand.step0), eng->demand.interval_s};
     if (!tp) {   // sequential path: one kernel, run by the expand phase (LDS: the histogram's 32-bit bins)
         if (!(phases & PH_EXPAND)) return TMH_OK;
         with_real(c.f64(), [&](auto r) {
@@ -4249,6 +4279,8 @@ int tmh_run(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_cha
         if (int rc = check_intervals(eng, n_chains, step0, n_steps, trace)) return rc;
     if (eng->has_registers)
         if (int rc = check_registers(eng, n_chains, step0, n_steps, trace)) return rc;
+    if (eng->has_demand)
+        if (int rc = check_demand(eng, n_chains, step0, n_steps, trace)) return rc;
     if (int rc = tmh_plan(eng, step0, n_steps, workspace, stream)) return rc;
     return tmh_step(eng, state, chain0, n_chains, step0, n_steps, inj, trace, stats, workspace,
                     (char*)workspace + pb, workspace_bytes - pb, stream);

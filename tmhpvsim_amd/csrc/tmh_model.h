@@ -1526,6 +1526,7 @@ enum OutKind : int {
     OUT_SERIES = 3,   // the fleet series (per-second integer sums over the chains), statistics if given, no trace
     OUT_INTERVALS = 4,   // interval metering (per-chain integer sums per metering interval), statistics if given, no trace
     OUT_REGISTERS = 5,   // import / export registers (the intervals' columns + import and export per interval), likewise
+    OUT_DEMAND = 6,      // demand registers (the registers' columns + the peak import and peak export keys), likewise
     // flags on OUT_ANY / OUT_STATS (fp32 kernels): OUT_B64 bins in fp64 (a histogram spec whose
     // fp32 bin position is not accurate enough, StatsView::bin64); OUT_BRT decides at run time
     OUT_B64 = 8, OUT_BRT = 16
@@ -1535,7 +1536,7 @@ constexpr int out_base(int out) { return out & 7; }
 constexpr bool out_no_trace(int out)
 {
     return out_base(out) == OUT_STATS || out_base(out) == OUT_SERIES || out_base(out) == OUT_INTERVALS ||
-           out_base(out) == OUT_REGISTERS;
+           out_base(out) == OUT_REGISTERS || out_base(out) == OUT_DEMAND;
 }
 
 // The fleet series of a window (tmh_series): rows of 4 int64 per step, `sum` at the
@@ -1549,13 +1550,24 @@ struct SeriesView {
 // k = (rel0 + j) / interval_s for the window's step j (rel0: the window's first step from
 // the intervals' origin), i the chain's index in the full batch (gid).  The import / export
 // registers (tmh_registers) take the same view of their table, whose cells have
-// TMH_REGISTERS_COLS columns instead of 4: interval_cols(OUT), a compile-time constant.
+// TMH_REGISTERS_COLS columns instead of 4 and the demand registers' (tmh_demand) TMH_DEMAND_COLS:
+// interval_cols(OUT), a compile-time constant.
 struct IntervalsView {
     unsigned long long* sum;
     uint64_t ld;
     uint32_t rel0, interval_s;
 };
-constexpr int interval_cols(int out) { return out_base(out) == OUT_REGISTERS ? TMH_REGISTERS_COLS : 4; }
+constexpr int interval_cols(int out)
+{
+    return out_base(out) == OUT_DEMAND ? TMH_DEMAND_COLS : out_base(out) == OUT_REGISTERS ? TMH_REGISTERS_COLS : 4;
+}
+// The demand registers' packed key of a second (tmh_demand): the quantised power v (0 <= v < 2^27)
+// above the complement of the second's offset o in its interval, so the maximum key is the
+// largest power at its earliest second; > 0 for every second.
+constexpr unsigned long long demand_key(uint32_t v, uint32_t o)
+{
+    return ((unsigned long long)v << 32) | (0xFFFFFFFFu - o);
+}
 constexpr int SERIES_FRAC_BITS = TMH_SERIES_FRAC_BITS;
 // q(v): v in units of 2^-SERIES_FRAC_BITS W, rounded half to even (|v| < TMH_SERIES_MAX_W: |q| < 2^26)
 template <typename R>

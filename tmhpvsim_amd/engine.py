@@ -127,6 +127,8 @@ class BatchedSim:
         self._intervals = None
         self.registers_raw = None    # int64 [n_intervals, 6, n] (enable_registers)
         self._registers = None
+        self.demand_raw = None       # int64 [n_intervals, 8, n] (enable_demand)
+        self._demand = None
         self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
@@ -233,6 +235,8 @@ class BatchedSim:
         if self._registers is not None:
             raise ValueError("the import / export registers are enabled: their table holds the intervals' columns "
                              "(registers.to_intervals); one of the two per sim")
+        if self._demand is not None:
+            raise ValueError("the demand registers are enabled: their table holds the intervals' columns; one of the two per sim")
         n_steps, interval_s = int(n_steps), int(interval_s)
         if n_steps < 1 or interval_s < 1:
             raise ValueError("enable_intervals: n_steps >= 1 and interval_s >= 1")
@@ -280,6 +284,9 @@ class BatchedSim:
         if self._intervals is not None:
             raise ValueError("interval metering is enabled: the registers table holds the intervals' columns "
                              "(registers.to_intervals); one of the two per sim")
+        if self._demand is not None:
+            raise ValueError("the demand registers are enabled: their table holds the registers' columns "
+                             "(demand.to_registers); one of the two per sim")
         n_steps, interval_s, nc = int(n_steps), int(interval_s), len(COLUMNS)
         if n_steps < 1 or interval_s < 1:
             raise ValueError("enable_registers: n_steps >= 1 and interval_s >= 1")
@@ -305,6 +312,57 @@ class BatchedSim:
             raise ValueError("no registers: call enable_registers first")
         _torch().cuda.synchronize(self.device)
         return to_watts(self.registers_raw, self._registers.interval_s, n_steps=self._registers.n_steps)
+
+    # ------------------------------------------------------------------ demand registers
+    def enable_demand(self, n_steps, interval_s=900, step0=None, buffer=None):
+        """Keep every chain's demand registers (tmhpvsim_amd.demand: the import / export
+        registers' six columns plus the peak import and the peak export of each metering
+        interval of interval_s seconds as packed keys -- the quantised power above the
+        complement of the second's offset, combined by maximum, so the earliest second at the
+        peak wins) over steps [step0, step0 + n_steps) in every later run; step0 defaults to
+        the current step.  Returns the raw int64 tensor [n_intervals, 8, n].  buffer: an int64
+        device tensor of that shape to accumulate into; it may be a view with strides
+        (8 ld, ld, 1) -- a column slice big[:, :, a:b] of a contiguous table (ld is read from
+        the strides); by default a zeroed one.  Runs with demand registers take no traces
+        (trace=()), no fleet series, no interval metering and no import / export registers
+        beside them (the table holds their columns); compaction is allowed.  n_steps=None
+        switches the output off."""
+        from .demand import COLUMNS, n_intervals
+        torch = _torch()
+        if n_steps is None:
+            _lib.check(self.L.tmh_set_demand(self._eng, None))
+            self.demand_raw, self._demand = None, None
+            return None
+        for other, what in ((self._series, "a fleet series"), (self._intervals, "interval metering"),
+                            (self._registers, "the import / export registers")):
+            if other is not None:
+                raise ValueError(f"{what} is enabled: one table output per sim (the demand table holds the registers' "
+                                 "and the intervals' columns, demand.to_registers)")
+        n_steps, interval_s, nc = int(n_steps), int(interval_s), len(COLUMNS)
+        if n_steps < 1 or interval_s < 1:
+            raise ValueError("enable_demand: n_steps >= 1 and interval_s >= 1")
+        nk = n_intervals(n_steps, interval_s)
+        if buffer is None:
+            buffer = torch.zeros(nk, nc, self.n, dtype=torch.int64, device=self.device)
+        elif (buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (nk, nc, self.n)):
+            raise ValueError(f"demand buffer must be an int64 [{nk}, {nc}, {self.n}] tensor on {self.device}")
+        ld = int(buffer.stride(1))
+        if ld < self.n or (self.n > 1 and buffer.stride(2) != 1) or (nk > 1 and buffer.stride(0) != nc * ld):
+            raise ValueError(f"demand buffer strides {tuple(buffer.stride())}: need ({nc} ld, ld, 1) with ld >= {self.n}")
+        st = _lib.Demand(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
+        _lib.check(self.L.tmh_set_demand(self._eng, C.byref(st)))
+        self.demand_raw, self._demand = buffer, st
+        return buffer
+
+    def demand(self):
+        """The demand table in watts and watt-hours (demand.to_watts of demand_raw): the
+        registers' keys plus peak_import, peak_export, t_peak_import, t_peak_export and
+        load_factor, [n_intervals, n] each."""
+        from .demand import to_watts
+        if self.demand_raw is None:
+            raise ValueError("no demand registers: call enable_demand first")
+        _torch().cuda.synchronize(self.device)
+        return to_watts(self.demand_raw, self._demand.interval_s, n_steps=self._demand.n_steps)
 
     def guard_records(self):
         """Tests: the fp32 guard-band records (chain, 128-s block) of the last window that run()
@@ -370,6 +428,18 @@ class BatchedSim:
             s0, sn = self._registers.step0, self._registers.n_steps
             if self.step < s0 or self.step + n_steps > s0 + sn:
                 raise ValueError(f"steps [{self.step}, +{n_steps}) outside the registers [{s0}, +{sn})")
+        if self._demand is not None:   # (likewise; compact=True is allowed)
+            if self._series is not None:
+                raise ValueError("the demand registers and a fleet series are both enabled: one of the two per sim")
+            if self._intervals is not None or self._registers is not None:
+                raise ValueError("the demand registers and interval metering or the import / export registers are both "
+                                 "enabled: one of them per sim")
+            if trace:
+                raise ValueError("a demand run takes no traces (trace=()): take the peaks of the traces instead "
+                                 "(demand.from_traces)")
+            s0, sn = self._demand.step0, self._demand.n_steps
+            if self.step < s0 or self.step + n_steps > s0 + sn:
+                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the demand registers [{s0}, +{sn})")
         if n_steps > ROLL_MAX:   # one rolling clock covers at most ROLL_MAX steps: run in pieces (same bits)
             res = out if out is not None else self._alloc(n_steps, trace)
             done = 0
