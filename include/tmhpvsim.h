@@ -530,7 +530,8 @@ int tmh_engine_last_expand(const struct tmh_engine* eng);
  * f = 0 ndtri, 1 gammaincinv, 2 stdtrit, 3 al_ppf, 4 ndtri (fp32 path),
  * 8 ocml's ndtri (the fp64 noise quantile's tails), 9 / 10 the fp32 PV chain's
  * v_med3_f32 clamps med3(x, 0, a) / med3(x, -inf, a), and the fp64 PV chain's
- * table functions: 11 the noise quantile of the 32-bit word x[i], 12 log, 13 exp. */
+ * table functions: 11 the noise quantile of the 32-bit word x[i], 12 log, 13 exp;
+ * 17 the segment walk's cloud-length power pow(x[i], a) as the walk calls it. */
 int tmh_probe(int fn, double a, const double* x, double* out, uint32_t n, void* stream);
 
 #ifdef __cplusplus

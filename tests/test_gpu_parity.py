@@ -93,6 +93,14 @@ def test_probe_math():
     # round 6: the fp32 kernels' min(csi, csimax) as a plain v_min_f32 with the bound in an SGPR
     # (pv_power_f<true>): the same results, csimax on a NaN csi
     np.testing.assert_array_equal(probe(16, 1.25, x), [1.25, -5.0, 0.5, 1.25, 1.25])
+    # the segment walk's cloud-length power pow_d(alpha + delta u, expo) (cloud_cover_binary.py:35-40) over the
+    # keyed uniforms' form (2 k + 1) 2^-53 and both ends of their range: test_functions_fixture's bar for
+    # this quantity.  tests/test_gpu_walk_planted.py takes its candidate lengths from this probe.
+    alpha, delta, expo, _ = O.constants()
+    k52 = np.random.default_rng(17).integers(0, 2 ** 52, 20000, dtype=np.uint64)
+    k52 = np.concatenate([k52, np.array([0, 2 ** 52 - 1], dtype=np.uint64)])
+    arg = alpha + delta * ((2 * k52 + 1).astype(np.float64) * 2.0 ** -53)
+    np.testing.assert_allclose(probe(17, expo, arg), arg ** expo, rtol=1e-14)
 
 
 def test_probe_noise_table_quantile():

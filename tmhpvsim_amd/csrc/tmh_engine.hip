@@ -2967,6 +2967,9 @@ __global__ void probe_kernel(int fn, double a, const double* x, double* out, uin
             v = (double)c;
             break;
         }
+        // the walk's cloud-length power (cloud_cover_binary.py:35-40): x = alpha + delta u, a = expo, through
+        // the out-of-line pow_d the candidate table and segments_kernel call
+        case 17: v = pow_d(x[i], a); break;
         default: v = NAN;
     }
     out[i] = v;

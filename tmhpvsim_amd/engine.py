@@ -660,7 +660,8 @@ def torch_uint8():
 
 
 def probe(fn, a, x, device="cuda"):
-    """Device math probe (parity tests): fn 0 ndtri, 1 gammaincinv, 2 stdtrit, 3 al_ppf, 4 ndtri fp32."""
+    """Device math probe (parity tests): fn 0 ndtri, 1 gammaincinv, 2 stdtrit, 3 al_ppf, 4 ndtri fp32,
+    17 the segment walk's cloud-length power pow_d(x, a) (x = alpha + delta u, a = the exponent)."""
     torch = _torch()
     L = _lib.load()
     xt = torch.as_tensor(np.asarray(x, dtype=np.float64), device=device)
