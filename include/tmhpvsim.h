@@ -202,13 +202,7 @@ typedef struct tmh_intervals {
  * every cell [4] - [5] == [1] - [0] bit for bit, and the self-consumed energy is
  * [0] - [5] == [1] - [4].  Integer sums, as the intervals'. */
 #define TMH_REGISTERS_COLS 6
-typedef struct tmh_registers {
-    int64_t* sum;        /* device int64 [n_intervals][6][ld], accumulated; the caller zero-initialises */
-    int64_t step0;       /* origin: step s belongs to interval (s - step0) / interval_s */
-    uint32_t n_steps;    /* steps covered; n_intervals = ceil(n_steps / interval_s); a last partial interval is kept */
-    uint32_t interval_s; /* >= 1, any value */
-    uint64_t ld;         /* >= the batch's chains (>= n_full under tmh_set_chain_ids) */
-} tmh_registers;
+typedef struct tmh_intervals tmh_registers;   /* the same descriptor: sum is [n_intervals][6][ld] */
 
 /* Demand registers: a meter's maximum-demand registers beside the import / export registers
  * -- per chain and metering interval, the highest power drawn from the grid and the highest
@@ -229,13 +223,7 @@ typedef struct tmh_registers {
  * identity of the maximum.  An interval without feed-in has [7] = key(0, its first ok second):
  * one rule, no special cases. */
 #define TMH_DEMAND_COLS 8
-typedef struct tmh_demand {
-    int64_t* sum;        /* device int64 [n_intervals][8][ld], accumulated / maximised; the caller zero-initialises */
-    int64_t step0;       /* origin: step s belongs to interval (s - step0) / interval_s */
-    uint32_t n_steps;    /* steps covered; n_intervals = ceil(n_steps / interval_s); a last partial interval is kept */
-    uint32_t interval_s; /* >= 1, any value */
-    uint64_t ld;         /* >= the batch's chains (>= n_full under tmh_set_chain_ids) */
-} tmh_demand;
+typedef struct tmh_intervals tmh_demand;      /* the same descriptor: sum is [n_intervals][8][ld], accumulated / maximised */
 
 int tmh_abi_version(void);
 const char* tmh_last_error(void);

@@ -17,6 +17,6 @@ for l in sys.stdin:
 if cur: out.append((cur,row))
 names=subprocess.run(['c++filt'],input='\n'.join(c for c,_ in out),capture_output=True,text=True).stdout.split('\n')
 for (c,r),nm in zip(out,names):
-    nm=nm.replace('(anonymous namespace)::','').split('(')[0]
+    nm=re.sub(r'\(\w+\)(?=\d)','',nm.replace('(anonymous namespace)::','')).split('(')[0]   # (an enum argument prints as (Type)N)
     print(f'{nm[:44]:44s} ' + ' '.join(f'{k}={v}' for k,v in r.items()))
 "

@@ -1,0 +1,133 @@
+#!/usr/bin/env python
+"""Cost of an interval table: TMH_K_EXPAND (tmh_profile_*: HIP events around the expansion
+kernel) of the statistics-only expansion and of the expansions with a table, same chains,
+same window, same process, the runs alternating.
+
+    python scripts/table_cost.py --kind intervals|registers|demand [--chains 65536] [--steps 86400]
+                                 [--interval 900] [--rounds 5] [--precision fp32]
+                                 [--start "2019-09-05 00:00:00"] [--out FILE.json]
+
+The runs of a kind, each with the same statistics beside its table:
+  intervals: OUT_STATS and OUT_INTERVALS;
+  registers: OUT_STATS, OUT_INTERVALS and OUT_REGISTERS -- the registers' first four columns
+             are the intervals' table and import - export == meter - pv in every cell;
+  demand:    OUT_STATS, OUT_REGISTERS and OUT_DEMAND -- the demand table's first six columns
+             are the registers' table and every cell with an ok second has both keys (offset
+             inside the interval, peak x n_ok >= the sum).
+The script checks each run's variant, these identities (on the warm-up round's tables), that
+the statistics of all runs agree bit for bit and that every table's ok seconds equal the
+histogram's count.  One warm-up round, then --rounds timed ones.  Prints one JSON line: the
+per-run milliseconds, their medians and ranges, the ratios between the runs and the device's
+name.  Needs a GPU (no fallback).  The script sets no time limit of its own: all runs share
+one process (same code objects, same allocator), so the caller wraps it, e.g. `timeout -k 10
+300 python scripts/table_cost.py --kind demand`; a run that hangs ends the measurement,
+nothing is retried."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+# per kind: the runs as (label in the JSON keys, table enabled or None)
+RUNS = {
+    "intervals": (("stats_only", None), ("with_intervals", "intervals")),
+    "registers": (("stats_only", None), ("intervals", "intervals"), ("registers", "registers")),
+    "demand": (("stats_only", None), ("registers", "registers"), ("demand", "demand")),
+}
+
+
+def check_tables(kind, tables, interval_s):
+    """The kind's identities between the warm-up tables; the cells with feed-in (None: not counted)."""
+    import torch
+    if kind == "registers":
+        rg, iv = tables["registers"], tables["intervals"]
+        assert torch.equal(rg[:, :4], iv) and torch.equal(rg[:, 4] - rg[:, 5], rg[:, 1] - rg[:, 0])
+        return int((rg[:, 5] > 0).sum())
+    if kind == "demand":
+        dm, rg = tables["demand"], tables["registers"]
+        assert torch.equal(dm[:, :6], rg)
+        for col, reg in ((6, 4), (7, 5)):
+            key, n_ok = dm[:, col], dm[:, 2]
+            assert torch.equal(key != 0, n_ok > 0)
+            off = torch.where(key != 0, 0xFFFFFFFF - (key & 0xFFFFFFFF), torch.zeros_like(key))
+            assert int(off.max()) < interval_s and bool(((key >> 32) * n_ok >= dm[:, reg]).all())
+        return int((dm[:, 7] >> 32 > 0).sum())
+    return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", choices=tuple(RUNS), required=True)
+    ap.add_argument("--chains", type=int, default=65536)
+    ap.add_argument("--steps", type=int, default=86400)
+    ap.add_argument("--interval", type=int, default=900)
+    ap.add_argument("--rounds", "--pairs", type=int, default=5)
+    ap.add_argument("--precision", default="fp32")
+    ap.add_argument("--start", default="2019-09-05 00:00:00")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    from tmhpvsim_amd import _lib
+    from tmhpvsim_amd.engine import BatchedSim
+    from tmhpvsim_amd.params import ModelParams
+    if not torch.cuda.is_available():
+        sys.exit("table_cost.py needs a GPU")
+    out_of = {None: _lib.OUT_STATS, "intervals": _lib.OUT_INTERVALS, "registers": _lib.OUT_REGISTERS,
+              "demand": _lib.OUT_DEMAND}
+    runs = RUNS[a.kind]
+    labels = [label for label, _ in runs]
+
+    def one(table):
+        sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=ModelParams(), precision=a.precision,
+                         device="cuda:0", horizon=a.steps)
+        sim.enable_stats()
+        raw = getattr(sim, "enable_" + table)(a.steps, a.interval) if table else None
+        _lib.check(sim.L.tmh_profile_enable(sim._eng, 1))
+        sim.run(a.steps, trace=(), window=a.steps)
+        torch.cuda.synchronize()
+        ms, launches = _lib.profile_read(sim._eng, _lib.K_EXPAND)
+        want = out_of[table] | (_lib.OUT_FP64 if a.precision == "fp64" else 0)
+        assert launches == 1 and sim.L.tmh_engine_last_expand(sim._eng) == want, (launches, want)
+        if raw is not None:
+            assert int(raw[:, 2].sum()) == int(sim.hist.sum()) > 0
+        return ms, sim.hist.clone(), sim.chain_acc.clone(), raw
+
+    tables = {table: one(table)[3] for _, table in runs}   # warm-up: code objects, allocator
+    export_cells = check_tables(a.kind, tables, a.interval)
+    del tables
+    t = {label: [] for label in labels}
+    ref = None
+    for _ in range(a.rounds):
+        for label, table in runs:
+            ms, hist, acc, _raw = one(table)
+            t[label].append(ms)
+            if ref is None:
+                ref = (hist, acc)
+            assert torch.equal(hist, ref[0]) and torch.equal(acc.view(torch.int64), ref[1].view(torch.int64))
+    med = {label: statistics.median(t[label]) for label in labels}
+    ns = {label: 1e6 * med[label] / (a.chains * a.steps) for label in labels}
+    res = dict(device=torch.cuda.get_device_name(0), chains=a.chains, steps=a.steps, interval_s=a.interval,
+               precision=a.precision, start=a.start,
+               **{f"{k}_ms": t[k] for k in labels}, **{f"{k}_median_ms": med[k] for k in labels},
+               **{f"{k}_range_ms": [min(t[k]), max(t[k])] for k in labels})
+    if a.kind == "intervals":
+        res.update(ratio=med["with_intervals"] / med["stats_only"], ns_per_chain_second=[ns[k] for k in labels])
+    else:   # the kind over the statistics, the kind over the table below it, that table over the statistics
+        below = labels[1]
+        res.update(rounds=a.rounds, export_cells=export_cells,
+                   **{f"ratio_{a.kind}_stats": med[a.kind] / med["stats_only"],
+                      f"ratio_{a.kind}_{below}": med[a.kind] / med[below],
+                      f"ratio_{below}_stats": med[below] / med["stats_only"]},
+                   ns_per_chain_second=ns)
+    res["build_stamp"] = _lib.loaded_stamp()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

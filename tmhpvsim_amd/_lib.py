@@ -67,23 +67,14 @@ class Series(C.Structure):
 
 
 class Intervals(C.Structure):
-    """tmh_intervals: int64 [n_intervals][4][ld] per-chain interval sums from step0 on (tmh_set_intervals)."""
+    """tmh_intervals: int64 [n_intervals][cols][ld] per-chain interval sums from step0 on -- the one descriptor of
+    the interval tables: 4 columns (tmh_set_intervals), 6 with the import and export registers (tmh_registers,
+    tmh_set_registers), 8 with the peak import and peak export keys (tmh_demand, tmh_set_demand)."""
     _fields_ = [("sum", C.c_void_p), ("step0", C.c_int64), ("n_steps", C.c_uint32), ("interval_s", C.c_uint32),
                 ("ld", C.c_uint64)]
 
 
-class Registers(C.Structure):
-    """tmh_registers: int64 [n_intervals][6][ld] per-chain interval sums with the import and export registers
-    (tmh_set_registers); the fields of tmh_intervals."""
-    _fields_ = [("sum", C.c_void_p), ("step0", C.c_int64), ("n_steps", C.c_uint32), ("interval_s", C.c_uint32),
-                ("ld", C.c_uint64)]
-
-
-class Demand(C.Structure):
-    """tmh_demand: int64 [n_intervals][8][ld] per-chain registers with the peak import and peak export keys
-    (tmh_set_demand); the fields of tmh_registers."""
-    _fields_ = [("sum", C.c_void_p), ("step0", C.c_int64), ("n_steps", C.c_uint32), ("interval_s", C.c_uint32),
-                ("ld", C.c_uint64)]
+Registers = Demand = Intervals   # typedefs of tmh_intervals in the header
 
 
 EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_bytes", "tmh_state_offsets", "tmh_plan_bytes",

@@ -102,7 +102,9 @@ def _fleet_run(n, start, seconds, seed, precision, bin_s):
     return {k: v[0] for k, v in out.items()}
 
 
-def _intervals_run(n, start, seconds, seed, precision, interval_s):
+def _table_run(kind, n, start, seconds, seed, precision, interval_s):
+    """An engine run with the interval table `kind` ("intervals", "registers" or "demand") only:
+    the raw table and its watt / watt-hour arrays."""
     from .engine import BatchedSim
     from .params import ModelParams
     import torch
@@ -111,48 +113,13 @@ def _intervals_run(n, start, seconds, seed, precision, interval_s):
     params = ModelParams(seed=int(seed))
     sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
                      horizon=int(seconds))
-    raw = sim.enable_intervals(int(seconds), int(interval_s))
+    raw = getattr(sim, "enable_" + kind)(int(seconds), int(interval_s))
     sim.run(int(seconds), trace=())
-    out = sim.intervals()
+    out = getattr(sim, kind)()
     bad = int((sim.status() != 0).sum())
     if bad:
-        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their intervals hold the seconds before the fault")
-    return raw.cpu().numpy(), out
-
-
-def _registers_run(n, start, seconds, seed, precision, interval_s):
-    from .engine import BatchedSim
-    from .params import ModelParams
-    import torch
-    if not torch.cuda.is_available():
-        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
-    params = ModelParams(seed=int(seed))
-    sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
-                     horizon=int(seconds))
-    raw = sim.enable_registers(int(seconds), int(interval_s))
-    sim.run(int(seconds), trace=())
-    out = sim.registers()
-    bad = int((sim.status() != 0).sum())
-    if bad:
-        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their registers hold the seconds before the fault")
-    return raw.cpu().numpy(), out
-
-
-def _demand_run(n, start, seconds, seed, precision, interval_s):
-    from .engine import BatchedSim
-    from .params import ModelParams
-    import torch
-    if not torch.cuda.is_available():
-        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
-    params = ModelParams(seed=int(seed))
-    sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
-                     horizon=int(seconds))
-    raw = sim.enable_demand(int(seconds), int(interval_s))
-    sim.run(int(seconds), trace=())
-    out = sim.demand()
-    bad = int((sim.status() != 0).sum())
-    if bad:
-        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their registers hold the seconds before the fault")
+        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their "
+                       f"{'intervals' if kind == 'intervals' else 'registers'} hold the seconds before the fault")
     return raw.cpu().numpy(), out
 
 
@@ -258,87 +225,73 @@ def fleet(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, se
     click.echo(f"wrote {len(out['n_ok'])} rows to {file}")
 
 
+REGISTERS_CSV = (("import_wh", "energy_wh_import"), ("export_wh", "energy_wh_export"), ("pv_wh", "energy_wh_pv"),
+                 ("meter_wh", "energy_wh_meter"), ("self_wh", "energy_wh_self"), ("n_ok", "n_ok"))
+# chain 0's CSV columns per interval table: (header, key of the table's watt / watt-hour arrays)
+TABLE_CSV = {
+    "intervals": (("meter", "meter"), ("pv", "pv"), ("residual load", "residual")),
+    "registers": REGISTERS_CSV,
+    "demand": REGISTERS_CSV + (("peak_import_w", "peak_import"), ("t_peak_import_s", "t_peak_import"),
+                               ("peak_export_w", "peak_export"), ("t_peak_export_s", "t_peak_export")),
+}
+
+
+def _table_command(kind, file, batch, start, seconds, seed, precision, interval_s, all_chains):
+    """The `intervals`, `registers` and `demand` commands: chain 0's rows to FILE, every chain to the .npz."""
+    raw, out = _table_run(kind, batch, start, seconds, seed, precision, interval_s)
+    t0 = dt.datetime.fromisoformat(str(start))
+    rows = raw.shape[0]
+    with open(file, mode="w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(["time"] + [name for name, _ in TABLE_CSV[kind]])
+        for k in range(rows):
+            w.writerow([t0 + dt.timedelta(seconds=k * interval_s)] + [float(out[key][k, 0]) for _, key in TABLE_CSV[kind]])
+    if all_chains:
+        import numpy as np
+        np.savez(all_chains, raw=raw, interval_s=interval_s, **out)
+    click.echo(f"wrote {rows} rows to {file}" + (f" and {batch} chains to {all_chains}" if all_chains else ""))
+
+
+def table_options(f):
+    for opt in (click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz"),
+                click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
+                             help="seconds per metering interval (a last partial interval is kept)"),
+                click.option("--precision", type=click.Choice(["fp64", "fp32"]), default="fp32", help="batch mode arithmetic")):
+        f = opt(f)
+    return f
+
+
 @main.command()
 @click.argument("file")
 @common
-@click.option("--precision", type=click.Choice(["fp64", "fp32"]), default="fp32", help="batch mode arithmetic")
-@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
-              help="seconds per metering interval (a last partial interval is kept)")
-@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
+@table_options
 def intervals(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, interval_s, all_chains):
     """Interval means of chain 0 over --batch chains to FILE (CSV; interval-metering engine run)."""
     logging.basicConfig(level=logging.WARN - 10 * verbose)
     _need_batch(realtime, batch, "intervals")
-    raw, out = _intervals_run(batch, start, seconds, seed, precision, interval_s)
-    t0 = dt.datetime.fromisoformat(str(start))
-    rows = raw.shape[0]
-    with open(file, mode="w", newline="") as fh:
-        w = csv.writer(fh)
-        w.writerow(["time", "meter", "pv", "residual load"])
-        for k in range(rows):
-            w.writerow([t0 + dt.timedelta(seconds=k * interval_s), float(out["meter"][k, 0]), float(out["pv"][k, 0]),
-                        float(out["residual"][k, 0])])
-    if all_chains:
-        import numpy as np
-        np.savez(all_chains, raw=raw, interval_s=interval_s, **out)
-    click.echo(f"wrote {rows} rows to {file}" + (f" and {batch} chains to {all_chains}" if all_chains else ""))
+    _table_command("intervals", file, batch, start, seconds, seed, precision, interval_s, all_chains)
 
 
 @main.command()
 @click.argument("file")
 @common
-@click.option("--precision", type=click.Choice(["fp64", "fp32"]), default="fp32", help="batch mode arithmetic")
-@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
-              help="seconds per metering interval (a last partial interval is kept)")
-@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
+@table_options
 def registers(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, interval_s, all_chains):
     """Import / export registers of chain 0 over --batch chains to FILE (CSV; registers-only engine run)."""
     logging.basicConfig(level=logging.WARN - 10 * verbose)
     _need_batch(realtime, batch, "registers")
-    raw, out = _registers_run(batch, start, seconds, seed, precision, interval_s)
-    t0 = dt.datetime.fromisoformat(str(start))
-    rows = raw.shape[0]
-    keys = ("energy_wh_import", "energy_wh_export", "energy_wh_pv", "energy_wh_meter", "energy_wh_self", "n_ok")
-    with open(file, mode="w", newline="") as fh:
-        w = csv.writer(fh)
-        w.writerow(["time", "import_wh", "export_wh", "pv_wh", "meter_wh", "self_wh", "n_ok"])
-        for k in range(rows):
-            w.writerow([t0 + dt.timedelta(seconds=k * interval_s)] + [float(out[key][k, 0]) for key in keys])
-    if all_chains:
-        import numpy as np
-        np.savez(all_chains, raw=raw, interval_s=interval_s, **out)
-    click.echo(f"wrote {rows} rows to {file}" + (f" and {batch} chains to {all_chains}" if all_chains else ""))
-
-
-DEMAND_CSV = (("import_wh", "energy_wh_import"), ("export_wh", "energy_wh_export"), ("pv_wh", "energy_wh_pv"),
-              ("meter_wh", "energy_wh_meter"), ("self_wh", "energy_wh_self"), ("n_ok", "n_ok"),
-              ("peak_import_w", "peak_import"), ("t_peak_import_s", "t_peak_import"), ("peak_export_w", "peak_export"),
-              ("t_peak_export_s", "t_peak_export"))
+    _table_command("registers", file, batch, start, seconds, seed, precision, interval_s, all_chains)
 
 
 @main.command()
 @click.argument("file")
 @common
-@click.option("--precision", type=click.Choice(["fp64", "fp32"]), default="fp32", help="batch mode arithmetic")
-@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
-              help="seconds per metering interval (a last partial interval is kept)")
-@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
+@table_options
 def demand(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, interval_s, all_chains):
     """Demand registers of chain 0 over --batch chains to FILE (CSV; demand-only engine run)."""
     logging.basicConfig(level=logging.WARN - 10 * verbose)
     _need_batch(realtime, batch, "demand")
-    raw, out = _demand_run(batch, start, seconds, seed, precision, interval_s)
-    t0 = dt.datetime.fromisoformat(str(start))
-    rows = raw.shape[0]
-    with open(file, mode="w", newline="") as fh:
-        w = csv.writer(fh)
-        w.writerow(["time"] + [name for name, _ in DEMAND_CSV])
-        for k in range(rows):
-            w.writerow([t0 + dt.timedelta(seconds=k * interval_s)] + [float(out[key][k, 0]) for _, key in DEMAND_CSV])
-    if all_chains:
-        import numpy as np
-        np.savez(all_chains, raw=raw, interval_s=interval_s, **out)
-    click.echo(f"wrote {rows} rows to {file}" + (f" and {batch} chains to {all_chains}" if all_chains else ""))
+    _table_command("demand", file, batch, start, seconds, seed, precision, interval_s, all_chains)
 
 
 if __name__ == "__main__":

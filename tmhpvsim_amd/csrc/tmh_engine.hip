@@ -2809,23 +2809,26 @@ __global__ __launch_bounds__(256) void state_move_kernel(StateView src, StateVie
 // (record, second) a work-item: ~1 flagged second in 20 per wave, 95 us per C2 batch.)
 // Grid-stride over the record groups.
 constexpr uint32_t FIX_RPW = 16;
-// SER: the engine has a fleet series (no traces then): column 0 of the second's row gets
+// FIX: what the engine's expansion wrote, and so what a redone second corrects:
+// FIX_TRACES: the trace's pv and residual are overwritten
+// FIX_SERIES: a fleet series (no traces then): column 0 of the second's row gets
 // q(pv fixed) - q(pv32), a two's-complement 64-bit add -- the meter, n_ok and the covered
 // count are final already
-// IVL: the engine has interval metering (no traces either): the same difference goes to
+// FIX_INTERVALS: interval metering (no traces either): the same difference goes to
 // column 0 of the cell (interval of the second, chain)
-// SER and IVL both (the third output without traces; the existing instantiations keep their
-// names): the import / export registers, REG below -- the intervals' view of cells of 6
+// FIX_REGISTERS: the import / export registers, REG below -- the intervals' view of cells of 6
 // columns: the held second's export changes by dex = max(q(pv) - q(meter), 0) -
 // max(q(pv32) - q(meter), 0) (column 5) and its import by dex - dq (column 4: import -
 // export = q(meter) - q(pv) per second)
-// DEM (fixup_demand_kernel, with SER and IVL: the existing kernels keep their names): the
-// demand registers -- the registers' three corrections on cells of 8 columns, and the held
-// second's two keys (the expansion left held seconds out of the peaks) by atomic maximum,
-// unconditionally: a held second may be its interval's first ok second, or the only one
-template <bool SER, bool IVL>
-using FixView = std::conditional_t<SER && !IVL, SeriesView, std::conditional_t<IVL, IntervalsView, TraceView>>;
-template <bool SITES, bool SER = false, bool IVL = false>
+// FIX_DEMAND: the demand registers -- the registers' three corrections on cells of 8 columns,
+// and the held second's two keys (the expansion left held seconds out of the peaks) by atomic
+// maximum, unconditionally: a held second may be its interval's first ok second, or the only one
+// (One kernel body for the five, inline: a function shared between the instantiations changed
+// their SGPR spills.)
+enum FixKind : int { FIX_TRACES, FIX_SERIES, FIX_INTERVALS, FIX_REGISTERS, FIX_DEMAND };   // (the tables' in TableKind order)
+template <FixKind FIX>
+using FixView = std::conditional_t<FIX == FIX_SERIES, SeriesView, std::conditional_t<FIX >= FIX_INTERVALS, IntervalsView, TraceView>>;
+template <bool SITES, FixKind FIX>
 __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0, uint32_t n,
                                                     int64_t W0, uint32_t nsteps, int64_t utc0,
                                                     const double* __restrict__ tab64, const float* __restrict__ tab32,
@@ -2833,24 +2836,101 @@ __global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_kerne
                                                     const int2* __restrict__ events,
                                                     const uint32_t* __restrict__ n_events,
                                                     const BlockDesc* __restrict__ desc, SegView sg,
-                                                    FixView<SER, IVL> ov, StatsView sv)
+                                                    FixView<FIX> ov, StatsView sv)
 {
-    constexpr bool DEM = false;
-#include "tmh_fixup_body.inc"
-}
-// (SER, IVL, DEM: always true -- template parameters so that the body's discarded branches stay uninstantiated)
-template <bool SITES, bool SER = true, bool IVL = true, bool DEM = true>
-__global__ __launch_bounds__(64, (SITES ? FIX_WAVES_SITES : 1)) void fixup_demand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0, uint32_t n,
-                                                    int64_t W0, uint32_t nsteps, int64_t utc0,
-                                                    const double* __restrict__ tab64, const float* __restrict__ tab32,
-                                                    const double* __restrict__ sun,
-                                                    const int2* __restrict__ events,
-                                                    const uint32_t* __restrict__ n_events,
-                                                    const BlockDesc* __restrict__ desc, SegView sg,
-                                                    FixView<SER, IVL> ov, StatsView sv)
-{
-    static_assert(SER && IVL && DEM, "the demand registers' fixup");
-#include "tmh_fixup_body.inc"
+    constexpr bool SER = FIX == FIX_SERIES, DEM = FIX == FIX_DEMAND, REG = FIX == FIX_REGISTERS || DEM,
+                   IVL = FIX == FIX_INTERVALS || REG;
+    constexpr int RC = DEM ? TMH_DEMAND_COLS : TMH_REGISTERS_COLS;
+    TraceView tr{};
+    SeriesView se{};
+    IntervalsView ivv{};
+    if constexpr (SER) se = ov;
+    else if constexpr (IVL) ivv = ov;
+    else tr = ov;
+    const uint32_t nrec = min(*sg.nfix, sg.fixcap);
+    const int ne = (int)min(*n_events, ev_cap_dev(nsteps));
+    const uint32_t lane = threadIdx.x;   // one wave per workgroup
+    for (uint32_t r0 = blockIdx.x * FIX_RPW; r0 < nrec; r0 += gridDim.x * FIX_RPW) {   // wave-uniform
+        const uint32_t rw = r0 + (lane >> 2);
+        uint32_t word = 0;
+        if (rw < nrec) {
+            const uint4 m = sg.fix[rw].mask;
+            const uint32_t w = lane & 3;
+            word = w == 0 ? m.x : (w == 1 ? m.y : (w == 2 ? m.z : m.w));
+        }
+        uint32_t cum = __popc(word);   // inclusive prefix sum over the wave's words
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t u = __shfl_up(cum, d, 64);
+            if (lane >= (uint32_t)d) cum += u;
+        }
+        const uint32_t total = __builtin_amdgcn_readfirstlane(__shfl(cum, 63, 64));
+        for (uint32_t k0 = 0; k0 < total; k0 += 64) {   // wave-uniform
+            const uint32_t k = k0 + lane;
+            // the word holding flagged second k: the first q with cum[q] > k (every lane
+            // takes part in the shuffles; lanes past the total search for nothing)
+            uint32_t lo = 0;
+#pragma unroll
+            for (uint32_t h = 32; h; h >>= 1)
+                if (__shfl(cum, (int)(lo + h - 1), 64) <= k) lo += h;
+            const uint32_t wq = __shfl(word, (int)lo, 64);
+            const uint32_t cq = __shfl(cum, (int)lo, 64);
+            if (k >= total) continue;
+            uint32_t m = wq;
+            for (uint32_t rank = k - (cq - __popc(wq)); rank; --rank) m &= m - 1;   // drop the lower set bits
+            const uint32_t i = (lo & 3) * 32 + (uint32_t)(__ffs(m) - 1);   // second of the record's block
+            const FixRec& fr = sg.fix[r0 + (lo >> 2)];
+            const uint32_t c = fr.c;
+            if (c >= n || fr.b >= sg.nblk) continue;   // (never appended: the expansion records live chains only)
+            const BlockDesc db = desc[fr.b];
+            const uint32_t j = fr.b * BLOCK_STEPS + i;
+            const uint32_t cw = (lo & 3) == 0 ? fr.cov.x : ((lo & 3) == 1 ? fr.cov.y : ((lo & 3) == 2 ? fr.cov.z : fr.cov.w));
+            const bool covered = (cw >> (i & 31)) & 1u;
+            float pv32, meter, pv;
+            if (!redo_second<SITES>(kp, dp, st, sg, n, c, chain0, W0, utc0, j, db, covered, SER || IVL || sv.acc != nullptr, events, ne,
+                                    tab64, tab32, sun, pv32, meter, pv))
+                continue;
+            const float res = meter - pv, res32 = meter - pv32;   // second_body's residual
+            const size_t o = (size_t)j * tr.ld + c;
+            if (tr.pv) reinterpret_cast<float*>(tr.pv)[o] = pv;
+            if (tr.residual) reinterpret_cast<float*>(tr.residual)[o] = res;
+            if constexpr (SER) {
+                const long long dq = (long long)series_q<float>(pv) - (long long)series_q<float>(pv32);
+                const uint32_t g = se.group_chains ? c / se.group_chains : 0u;
+                if (dq) atomicAdd(se.sum + (size_t)g * se.gstride + (size_t)j * 4, (unsigned long long)dq);
+            }
+            if constexpr (IVL) {
+                const long long dq = (long long)series_q<float>(pv) - (long long)series_q<float>(pv32);
+                const uint32_t k = (ivv.rel0 + j) / ivv.interval_s;
+                if constexpr (!REG) {
+                    if (dq) atomicAdd(ivv.sum + (size_t)k * 4 * ivv.ld + gid(kp.ids, c), (unsigned long long)dq);
+                } else {
+                    const int qm = series_q<float>(meter);
+                    const long long dex = (long long)max(series_q<float>(pv) - qm, 0) - (long long)max(series_q<float>(pv32) - qm, 0);
+                    unsigned long long* cell = ivv.sum + (size_t)k * RC * ivv.ld + gid(kp.ids, c);
+                    if (dq) atomicAdd(cell, (unsigned long long)dq);
+                    if (dex - dq) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)(dex - dq));
+                    if (dex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)dex);
+                    if constexpr (DEM) {
+                        const int d = qm - series_q<float>(pv);
+                        const uint32_t o = ivv.rel0 + j - k * ivv.interval_s;
+                        __hip_atomic_fetch_max(cell + 6 * ivv.ld, demand_key((uint32_t)max(d, 0), o), __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_fetch_max(cell + 7 * ivv.ld, demand_key((uint32_t)max(-d, 0), o), __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+            }
+            if (sv.acc) {
+                atomicAdd(&sg.corr[c], (double)pv - (double)pv32);
+                atomicAdd(&sg.corr[(size_t)n + c], (double)res - (double)res32);
+                __hip_atomic_fetch_max(sg.acc_mx + c, max_key((double)res), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (sv.hist) {
+                atomicAdd((unsigned long long*)&sv.hist[hist_bin_rt<float>(sv, res)], 1ull);
+            }
+        }
+    }
 }
 
 // The window's end, one work-item per chain, after the expansion (and the fixup):
@@ -3155,6 +3235,26 @@ void with_real(bool f64, F&& f)
     else f(float{});
 }
 
+// The interval tables (tmh_intervals and its typedefs): per-chain cells per metering interval,
+// one kind per engine at a step.  A kind is its column count, the expansion's and the fixup's
+// output, and the words the refusals name it by; a new kind is a row here, its columns in
+// expand_tile and the fixup, and its exported setter.
+enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_KINDS };
+struct TableKindInfo {
+    int cols, out;
+    const char* what;   // in the setter's and the checks' messages
+    const char* name;   // as the other table of a both-set refusal
+};
+constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
+    {4, OUT_INTERVALS, "intervals", "interval metering"},
+    {TMH_REGISTERS_COLS, OUT_REGISTERS, "registers", "the import / export registers"},
+    {TMH_DEMAND_COLS, OUT_DEMAND, "demand registers", "the demand registers"},
+};
+static_assert(interval_cols(OUT_INTERVALS) == TABLE_KINDS[TBL_INTERVALS].cols &&
+                  interval_cols(OUT_REGISTERS) == TABLE_KINDS[TBL_REGISTERS].cols &&
+                  interval_cols(OUT_DEMAND) == TABLE_KINDS[TBL_DEMAND].cols,
+              "the kernels' cells");
+
 }  // namespace
 
 struct tmh_engine {
@@ -3172,12 +3272,17 @@ struct tmh_engine {
     int last_expand = -1;     // TMH_OUT_* of the last expansion launched (tmh_engine_last_expand)
     bool has_series = false;  // tmh_set_series: every expansion adds its window to `series`
     tmh_series series{};
-    bool has_intervals = false;   // tmh_set_intervals: every expansion adds its window to `intervals`
-    tmh_intervals intervals{};
-    bool has_registers = false;   // tmh_set_registers: every expansion adds its window to `registers`
-    tmh_registers registers{};
-    bool has_demand = false;      // tmh_set_demand: every expansion adds its window to `demand`
-    tmh_demand demand{};
+    struct {
+        bool set = false;   // tmh_set_intervals / _registers / _demand: every expansion adds its window to `t`
+        tmh_intervals t{};
+    } tables[TBL_KINDS];
+    // the first set kind (TBL_KINDS: none); a step is refused unless it is the only one (check_interval_tables)
+    int table_kind() const
+    {
+        int k = 0;
+        while (k < TBL_KINDS && !tables[k].set) ++k;
+        return k;
+    }
     // expansion tiles daylight blocks first (env TMH_EXP_COST_ORDER=1, A/B; measured slower in the C2
     // pipeline, round 6: 1.55 against 1.42-1.45 ms per step, same box -- launch order mixes the
     // store-bound night tiles with the VALU-bound day tiles over the launch)
@@ -3619,80 +3724,48 @@ static int check_series(const tmh_engine* eng, uint32_t n_chains, int64_t step0,
     return TMH_OK;
 }
 
-int tmh_set_intervals(struct tmh_engine* eng, const tmh_intervals* iv)
+// tmh_set_intervals, tmh_set_registers and tmh_set_demand (tmhpvsim.h): one descriptor, `kind` names it
+static int set_interval_table(tmh_engine* eng, TableKind kind, const tmh_intervals* iv)
 {
+    const char* what = TABLE_KINDS[kind].what;
     if (iv) {   // (the struct first: a bad one is named whatever the engine)
         if (!iv->sum || iv->n_steps == 0 || iv->ld == 0)
-            return fail(TMH_E_INVAL, "intervals need a buffer, n_steps > 0 and ld > 0");
-        if ((uintptr_t)iv->sum & 7) return fail(TMH_E_INVAL, "intervals buffer must be 8-byte aligned");
-        if (iv->interval_s == 0) return fail(TMH_E_INVAL, "intervals: interval_s must be >= 1");
+            return fail(TMH_E_INVAL, "%s need a buffer, n_steps > 0 and ld > 0", what);
+        if ((uintptr_t)iv->sum & 7) return fail(TMH_E_INVAL, "%s buffer must be 8-byte aligned", what);
+        if (iv->interval_s == 0) return fail(TMH_E_INVAL, "%s: interval_s must be >= 1", what);
     }
     if (!eng) return fail(TMH_E_INVAL, "NULL engine");
-    if (!iv) {
-        eng->has_intervals = false;
-        eng->intervals = tmh_intervals{};
-        return TMH_OK;
-    }
-    eng->intervals = *iv;
-    eng->has_intervals = true;
+    eng->tables[kind].set = iv != nullptr;
+    eng->tables[kind].t = iv ? *iv : tmh_intervals{};
     return TMH_OK;
 }
+int tmh_set_intervals(struct tmh_engine* eng, const tmh_intervals* iv) { return set_interval_table(eng, TBL_INTERVALS, iv); }
+int tmh_set_registers(struct tmh_engine* eng, const tmh_registers* rg) { return set_interval_table(eng, TBL_REGISTERS, rg); }
+int tmh_set_demand(struct tmh_engine* eng, const tmh_demand* dm) { return set_interval_table(eng, TBL_DEMAND, dm); }
 
-int tmh_set_registers(struct tmh_engine* eng, const tmh_registers* rg)
+// A step / expansion with an interval table set (nothing to check without one): everything the
+// kernels assume, checked on the host before any launch (tmhpvsim.h, tmh_set_intervals,
+// tmh_set_registers, tmh_set_demand).  The messages name the first set kind; with two kinds set
+// the step is refused whichever they are.
+static int check_interval_tables(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps,
+                                 const tmh_trace* trace)
 {
-    if (rg) {   // (the struct first, as tmh_set_intervals)
-        if (!rg->sum || rg->n_steps == 0 || rg->ld == 0)
-            return fail(TMH_E_INVAL, "registers need a buffer, n_steps > 0 and ld > 0");
-        if ((uintptr_t)rg->sum & 7) return fail(TMH_E_INVAL, "registers buffer must be 8-byte aligned");
-        if (rg->interval_s == 0) return fail(TMH_E_INVAL, "registers: interval_s must be >= 1");
-    }
-    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
-    if (!rg) {
-        eng->has_registers = false;
-        eng->registers = tmh_registers{};
-        return TMH_OK;
-    }
-    eng->registers = *rg;
-    eng->has_registers = true;
-    return TMH_OK;
-}
-
-int tmh_set_demand(struct tmh_engine* eng, const tmh_demand* dm)
-{
-    if (dm) {   // (the struct first, as tmh_set_intervals)
-        if (!dm->sum || dm->n_steps == 0 || dm->ld == 0)
-            return fail(TMH_E_INVAL, "demand registers need a buffer, n_steps > 0 and ld > 0");
-        if ((uintptr_t)dm->sum & 7) return fail(TMH_E_INVAL, "demand registers buffer must be 8-byte aligned");
-        if (dm->interval_s == 0) return fail(TMH_E_INVAL, "demand registers: interval_s must be >= 1");
-    }
-    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
-    if (!dm) {
-        eng->has_demand = false;
-        eng->demand = tmh_demand{};
-        return TMH_OK;
-    }
-    eng->demand = *dm;
-    eng->has_demand = true;
-    return TMH_OK;
-}
-
-// A step / expansion with interval metering or the import / export registers set (`what`
-// names the table, `iv` describes it: the two structs have the same fields): everything
-// the kernels assume, checked on the host before any launch (tmhpvsim.h,
-// tmh_set_intervals, tmh_set_registers).
-static int check_interval_table(const tmh_engine* eng, const char* what, const tmh_intervals& iv, uint32_t n_chains,
-                                int64_t step0, uint32_t n_steps, const tmh_trace* trace)
-{
+    const int kind = eng->table_kind();
+    if (kind == TBL_KINDS) return TMH_OK;
+    const char* what = TABLE_KINDS[kind].what;
+    const tmh_intervals& iv = eng->tables[kind].t;
+    const bool has_intervals = eng->tables[TBL_INTERVALS].set, has_registers = eng->tables[TBL_REGISTERS].set,
+               has_demand = eng->tables[TBL_DEMAND].set;
     if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
         return fail(TMH_E_INVAL, "%s are set: no traces in the same call (a caller with traces can sum them)", what);
     if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
-    if (eng->has_intervals && eng->has_registers)
+    if (has_intervals && has_registers)
         return fail(TMH_E_INVAL, "registers and intervals are both set: one of the two per engine (the registers table holds "
                                  "the intervals' columns)");
-    if (eng->has_demand && (eng->has_intervals || eng->has_registers))
+    if (has_demand && (has_intervals || has_registers))
         return fail(TMH_E_INVAL, "demand registers and %s are both set: one of the two per engine (the demand table holds "
                                  "the registers' and the intervals' columns)",
-                    eng->has_registers ? "the import / export registers" : "interval metering");
+                    TABLE_KINDS[has_registers ? TBL_REGISTERS : TBL_INTERVALS].name);
     if (eng->path != TMH_PATH_TIME_PARALLEL || eng->kp.rng_mode != TMH_RNG_KEYED)
         return fail(TMH_E_INVAL, "%s need the time-parallel path (keyed draws, no injected uniforms)", what);
     if (step0 < iv.step0 || step0 + (int64_t)n_steps > iv.step0 + (int64_t)iv.n_steps)
@@ -3709,23 +3782,6 @@ static int check_interval_table(const tmh_engine* eng, const char* what, const t
         return fail(TMH_E_INVAL, "inverter Paco %g W (|Pnt| %g W) not below TMH_SERIES_MAX_W %g W", paco, pnt,
                     (double)TMH_SERIES_MAX_W);
     return TMH_OK;
-}
-static int check_intervals(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps, const tmh_trace* trace)
-{
-    return check_interval_table(eng, "intervals", eng->intervals, n_chains, step0, n_steps, trace);
-}
-static int check_registers(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps, const tmh_trace* trace)
-{
-    const tmh_registers& rg = eng->registers;
-    return check_interval_table(eng, "registers", tmh_intervals{rg.sum, rg.step0, rg.n_steps, rg.interval_s, rg.ld}, n_chains,
-                                step0, n_steps, trace);
-}
-
-static int check_demand(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps, const tmh_trace* trace)
-{
-    const tmh_demand& dm = eng->demand;
-    return check_interval_table(eng, "demand registers", tmh_intervals{dm.sum, dm.step0, dm.n_steps, dm.interval_s, dm.ld}, n_chains,
-                                step0, n_steps, trace);
 }
 
 static int check_tables(const tmh_engine* eng, uint32_t n_chains)
@@ -3938,9 +3994,7 @@ struct StepCtx {
     IntervalsView ivv;
     bool f64() const { return eng->kp.precision == TMH_FP64; }
     bool series() const { return eng->has_series; }
-    bool intervals() const { return eng->has_intervals; }
-    bool registers() const { return eng->has_registers; }   // (ivv is their view then: never both, check_registers)
-    bool demand() const { return eng->has_demand; }         // (likewise: check_demand)
+    int table() const { return eng->table_kind(); }   // the interval table ivv views (the only one set: check_interval_tables), or TBL_KINDS
     uint32_t cb() const { return (n_chains + 255) / 256; }   // 256-chain blocks
     int64_t utc0() const { return eng->gp.clock.utc0; }
 };
@@ -4024,9 +4078,8 @@ static int phase_expand(const StepCtx& c)
     const StatsView& sv = c.sv;
     hipEvent_t t_exp = eng->mark(c.s);
     const bool f64 = c.f64(), sites = eng->kp.sites != nullptr, no_stats = !sv.hist && !sv.acc;
-    int out = c.demand() ? OUT_DEMAND   // (no trace pointers, no series, intervals or registers: check_demand)
-              : c.registers() ? OUT_REGISTERS   // (no trace pointers, no series, no intervals: check_registers)
-              : c.intervals() ? OUT_INTERVALS   // (no trace pointers, no series: check_intervals)
+    const int table = c.table();
+    int out = table != TBL_KINDS ? TABLE_KINDS[table].out   // (no trace pointers, no series, no other table: check_interval_tables)
               : c.series() ? OUT_SERIES   // (no trace pointers: check_series)
               : (no_stats && tv.pv && tv.meter && tv.residual && !tv.csi && !tv.covered) ? OUT_TRACE3
                     : (!tv.pv && !tv.meter && !tv.residual && !tv.csi && !tv.covered) ? OUT_STATS
@@ -4056,19 +4109,14 @@ static int phase_expand(const StepCtx& c)
             constexpr bool F32 = sizeof(r) == 4, S = decltype(st)::value;
             auto traces = [&](auto okind) { launch(r, okind, st, tv); };
             auto ivl = [&](auto okind) { launch(r, okind, st, c.ivv); };
-            if (c.demand()) {
-                // the demand registers: instantiated as the registers are
-                if constexpr (F32) with_value<OUT_DEMAND, OUT_DEMAND | OUT_B64>(OUT_DEMAND | (b64 ? OUT_B64 : 0), ivl);
-                else ivl(std::integral_constant<int, OUT_DEMAND>{});
-            } else if (c.registers()) {
-                // the import / export registers: instantiated as the intervals are
-                if constexpr (F32) with_value<OUT_REGISTERS, OUT_REGISTERS | OUT_B64>(OUT_REGISTERS | (b64 ? OUT_B64 : 0), ivl);
-                else ivl(std::integral_constant<int, OUT_REGISTERS>{});
-            } else if (c.intervals()) {
-                // interval metering (+ statistics when given, binned as the statistics-only kernel of the
+            if (table != TBL_KINDS) {
+                // an interval table (+ statistics when given, binned as the statistics-only kernel of the
                 // same histogram spec bins them: no per-second run-time choice)
-                if constexpr (F32) with_value<OUT_INTERVALS, OUT_INTERVALS | OUT_B64>(OUT_INTERVALS | (b64 ? OUT_B64 : 0), ivl);
-                else ivl(std::integral_constant<int, OUT_INTERVALS>{});
+                with_value<OUT_INTERVALS, OUT_REGISTERS, OUT_DEMAND>(out, [&](auto o) {
+                    constexpr int O = decltype(o)::value;
+                    if constexpr (F32) with_value<O, O | OUT_B64>(O | (b64 ? OUT_B64 : 0), ivl);
+                    else ivl(o);
+                });
             } else if (c.series()) {
                 // the fleet series (+ statistics when given; the histogram bins as hist_bin_rt decides)
                 launch(r, std::integral_constant<int, OUT_SERIES | OUT_BRT>{}, st, c.sev);
@@ -4094,20 +4142,18 @@ static int phase_commit(const StepCtx& c, hipEvent_t t_step)
         // groups in a row -- 2.0e-3 are recorded, ~1 flagged second each, diagnostic run r05 --
         // and the kernel two redo latencies long.)
         const uint32_t gx = (uint32_t)std::min<uint64_t>(65535, ((uint64_t)c.sg.fixcap + FIX_RPW - 1) / FIX_RPW);
+        const int fix = c.table() != TBL_KINDS ? FIX_INTERVALS + c.table() : c.series() ? FIX_SERIES : FIX_TRACES;
         with_value<0, 1>(eng->kp.sites != nullptr, [&](auto st) {
-            auto launch = [&](auto ser, auto ivl, const auto& view) {   // the series or the intervals (no traces then), or the traces
-                hipLaunchKernelGGL((fixup_kernel<decltype(st)::value, decltype(ser)::value, decltype(ivl)::value>), dim3(gx), dim3(64), 0, c.s,
-                                   eng->kp, eng->dp, c.v, c.chain0, c.n_chains, c.step0, c.n_steps, c.utc0(), c.pv.tab64,
-                                   c.pv.tab32, c.pv.sun, c.pv.events, c.pv.n_events, c.pv.desc, c.sg, view, c.sv);
-            };
-            if (c.demand())
-                hipLaunchKernelGGL((fixup_demand_kernel<decltype(st)::value>), dim3(gx), dim3(64), 0, c.s, eng->kp, eng->dp, c.v,
+            with_value<FIX_TRACES, FIX_SERIES, FIX_INTERVALS, FIX_REGISTERS, FIX_DEMAND>(fix, [&](auto f) {
+                constexpr FixKind F = (FixKind)decltype(f)::value;
+                const FixView<F>* view;   // the series or the table (no traces then), or the traces
+                if constexpr (F == FIX_SERIES) view = &c.sev;
+                else if constexpr (F >= FIX_INTERVALS) view = &c.ivv;
+                else view = &c.tv;
+                hipLaunchKernelGGL((fixup_kernel<decltype(st)::value, F>), dim3(gx), dim3(64), 0, c.s, eng->kp, eng->dp, c.v,
                                    c.chain0, c.n_chains, c.step0, c.n_steps, c.utc0(), c.pv.tab64, c.pv.tab32, c.pv.sun,
-                                   c.pv.events, c.pv.n_events, c.pv.desc, c.sg, c.ivv, c.sv);
-            else if (c.registers()) launch(std::true_type{}, std::true_type{}, c.ivv);   // (both: the registers)
-            else if (c.intervals()) launch(std::false_type{}, std::true_type{}, c.ivv);
-            else if (c.series()) launch(std::true_type{}, std::false_type{}, c.sev);
-            else launch(std::false_type{}, std::false_type{}, c.tv);
+                                   c.pv.events, c.pv.n_events, c.pv.desc, c.sg, *view, c.sv);
+            });
         });
         if (int rc = hip_check(hipGetLastError(), "fixup_kernel launch")) return rc;
     }
@@ -4142,12 +4188,7 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     const bool series = eng->has_series;   // (checked for a walk too: nothing of a refused window is launched)
     if (series)
         if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
-    if (eng->has_intervals)   // (a walk of a refused window is refused too)
-        if (int rc = check_intervals(eng, n_chains, step0, n_steps, trace)) return rc;
-    if (eng->has_registers)
-        if (int rc = check_registers(eng, n_chains, step0, n_steps, trace)) return rc;
-    if (eng->has_demand)
-        if (int rc = check_demand(eng, n_chains, step0, n_steps, trace)) return rc;
+    if (int rc = check_interval_tables(eng, n_chains, step0, n_steps, trace)) return rc;   // (a walk of a refused window is refused too)
     const bool tp = eng->path == TMH_PATH_TIME_PARALLEL;
     if (tp && (!scratch || scratch_bytes < tmh_engine_scratch_bytes(eng, n_chains, n_steps)))
         return fail(TMH_E_INVAL, "scratch too small: %zu < %zu", scratch_bytes, tmh_engine_scratch_bytes(eng, n_chains, n_steps));
@@ -4175,15 +4216,10 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     if (series)   // the window's first row of group 0
         c.sev = SeriesView{reinterpret_cast<unsigned long long*>(eng->series.sum) + (size_t)(step0 - eng->series.step0) * 4,
                            (uint64_t)eng->series.n_steps * 4, eng->series.group_chains, 0u};
-    if (eng->has_intervals)   // the whole table; the window's first step from the intervals' origin
-        c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(eng->intervals.sum), eng->intervals.ld,
-                              (uint32_t)(step0 - eng->intervals.step0), eng->intervals.interval_s};
-    if (eng->has_registers)   // likewise (cells of TMH_REGISTERS_COLS columns: the kernels' compile-time constant)
-        c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(eng->registers.sum), eng->registers.ld,
-                              (uint32_t)(step0 - eng->registers.step0), eng->registers.interval_s};
-    if (eng->has_demand)      // likewise (cells of TMH_DEMAND_COLS columns)
-        c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(eng->demand.sum), eng->demand.ld,
-                              (uint32_t)(step0 - eng->demand.step0), eng->demand.interval_s};
+    if (c.table() != TBL_KINDS) {   // the whole table; the window's first step from its origin (the cells' columns:
+        const tmh_intervals& t = eng->tables[c.table()].t;   // the kernels' compile-time constant)
+        c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(t.sum), t.ld, (uint32_t)(step0 - t.step0), t.interval_s};
+    }
     if (!tp) {   // sequential path: one kernel, run by the expand phase (LDS: the histogram's 32-bit bins)
         if (!(phases & PH_EXPAND)) return TMH_OK;
         with_real(c.f64(), [&](auto r) {
@@ -4278,12 +4314,7 @@ int tmh_run(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_cha
         return fail(TMH_E_INVAL, "workspace too small: %zu < %zu", workspace_bytes, need);
     if (eng->has_series)   // before the plan's launches
         if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
-    if (eng->has_intervals)
-        if (int rc = check_intervals(eng, n_chains, step0, n_steps, trace)) return rc;
-    if (eng->has_registers)
-        if (int rc = check_registers(eng, n_chains, step0, n_steps, trace)) return rc;
-    if (eng->has_demand)
-        if (int rc = check_demand(eng, n_chains, step0, n_steps, trace)) return rc;
+    if (int rc = check_interval_tables(eng, n_chains, step0, n_steps, trace)) return rc;
     if (int rc = tmh_plan(eng, step0, n_steps, workspace, stream)) return rc;
     return tmh_step(eng, state, chain0, n_chains, step0, n_steps, inj, trace, stats, workspace,
                     (char*)workspace + pb, workspace_bytes - pb, stream);

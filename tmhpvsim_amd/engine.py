@@ -8,6 +8,7 @@ time-major [step, chain] tensors; statistics are accumulated on the GPU.
 from __future__ import annotations
 
 import ctypes as C
+import importlib
 
 import numpy as np
 
@@ -27,6 +28,42 @@ def _torch():
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+# The interval tables (tmh_intervals and its typedefs): per-chain cells per metering interval, one kind
+# per sim.  Per kind: its module (COLUMNS, to_watts; the C setter is tmh_set_<kind>), the noun of its
+# messages, and what it refuses beside it -- at enable_<kind> (attribute, message) and in run() (its name
+# beside a fleet series, the other kinds with their message, the message of a run with traces).  The sim
+# keeps kind's raw tensor in <kind>_raw and its descriptor in _<kind>.
+_TABLES = {
+    "intervals": dict(
+        noun="intervals", name="interval metering",
+        enable_excludes=(
+            ("_registers", "the import / export registers are enabled: their table holds the intervals' columns "
+                           "(registers.to_intervals); one of the two per sim"),
+            ("_demand", "the demand registers are enabled: their table holds the intervals' columns; one of the two per sim")),
+        run_excludes=(),
+        no_trace="an interval-metering run takes no traces (trace=()): sum the traces instead (intervals.from_traces)"),
+    "registers": dict(
+        noun="registers", name="the registers",
+        enable_excludes=(
+            ("_intervals", "interval metering is enabled: the registers table holds the intervals' columns "
+                           "(registers.to_intervals); one of the two per sim"),
+            ("_demand", "the demand registers are enabled: their table holds the registers' columns "
+                        "(demand.to_registers); one of the two per sim")),
+        run_excludes=(("_intervals",), "the registers and interval metering are both enabled: one of the two per sim"),
+        no_trace="a registers run takes no traces (trace=()): sum the traces instead (registers.from_traces)"),
+    "demand": dict(
+        noun="demand registers", name="the demand registers",
+        enable_excludes=tuple(
+            (attr, f"{what} is enabled: one table output per sim (the demand table holds the registers' "
+                   "and the intervals' columns, demand.to_registers)")
+            for attr, what in (("_series", "a fleet series"), ("_intervals", "interval metering"),
+                               ("_registers", "the import / export registers"))),
+        run_excludes=(("_intervals", "_registers"), "the demand registers and interval metering or the import / export "
+                                                    "registers are both enabled: one of them per sim"),
+        no_trace="a demand run takes no traces (trace=()): take the peaks of the traces instead (demand.from_traces)"),
+}
 
 
 class BatchedSim:
@@ -123,12 +160,9 @@ class BatchedSim:
         self._hist_spec = None
         self.series_raw = None    # int64 [n_groups, n_steps, 4] (enable_series)
         self._series = None
-        self.intervals_raw = None    # int64 [n_intervals, 4, n] (enable_intervals)
-        self._intervals = None
-        self.registers_raw = None    # int64 [n_intervals, 6, n] (enable_registers)
-        self._registers = None
-        self.demand_raw = None       # int64 [n_intervals, 8, n] (enable_demand)
-        self._demand = None
+        for kind in _TABLES:   # intervals_raw, registers_raw, demand_raw: int64 [n_intervals, 4 / 6 / 8, n] (enable_<kind>)
+            setattr(self, kind + "_raw", None)
+            setattr(self, "_" + kind, None)
         self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
@@ -215,6 +249,45 @@ class BatchedSim:
         _torch().cuda.synchronize(self.device)
         return to_watts(self.series_raw, bin_s=bin_s, mean=mean)
 
+    # ------------------------------------------------------------------ interval tables
+    def _enable_table(self, kind, n_steps, interval_s, step0, buffer):
+        """enable_intervals, enable_registers and enable_demand (_TABLES[kind])."""
+        torch = _torch()
+        setter = getattr(self.L, "tmh_set_" + kind)
+        if n_steps is None:
+            _lib.check(setter(self._eng, None))
+            setattr(self, kind + "_raw", None)
+            setattr(self, "_" + kind, None)
+            return None
+        for attr, message in _TABLES[kind]["enable_excludes"]:
+            if getattr(self, attr) is not None:
+                raise ValueError(message)
+        mod = importlib.import_module("." + kind, __package__)
+        n_steps, interval_s, nc = int(n_steps), int(interval_s), len(mod.COLUMNS)
+        if n_steps < 1 or interval_s < 1:
+            raise ValueError(f"enable_{kind}: n_steps >= 1 and interval_s >= 1")
+        nk = mod.n_intervals(n_steps, interval_s)
+        if buffer is None:
+            buffer = torch.zeros(nk, nc, self.n, dtype=torch.int64, device=self.device)
+        elif (buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (nk, nc, self.n)):
+            raise ValueError(f"{kind} buffer must be an int64 [{nk}, {nc}, {self.n}] tensor on {self.device}")
+        ld = int(buffer.stride(1))
+        if ld < self.n or (self.n > 1 and buffer.stride(2) != 1) or (nk > 1 and buffer.stride(0) != nc * ld):
+            raise ValueError(f"{kind} buffer strides {tuple(buffer.stride())}: need ({nc} ld, ld, 1) with ld >= {self.n}")
+        st = _lib.Intervals(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
+        _lib.check(setter(self._eng, C.byref(st)))
+        setattr(self, kind + "_raw", buffer)
+        setattr(self, "_" + kind, st)
+        return buffer
+
+    def _table_watts(self, kind):
+        """intervals(), registers() and demand(): <kind>.to_watts of the raw table."""
+        raw, st = getattr(self, kind + "_raw"), getattr(self, "_" + kind)
+        if raw is None:
+            raise ValueError(f"no {_TABLES[kind]['noun']}: call enable_{kind} first")
+        _torch().cuda.synchronize(self.device)
+        return importlib.import_module("." + kind, __package__).to_watts(raw, st.interval_s, n_steps=st.n_steps)
+
     # ------------------------------------------------------------------ interval metering
     def enable_intervals(self, n_steps, interval_s=900, step0=None, buffer=None):
         """Accumulate every chain's interval meter (tmhpvsim_amd.intervals: exact per-chain
@@ -226,42 +299,13 @@ class BatchedSim:
         table, so several batches or shards fill one table (ld is read from the strides); by
         default a zeroed one.  Runs with intervals take no traces (trace=()) and no fleet
         series; compaction is allowed.  n_steps=None switches the output off."""
-        from .intervals import n_intervals
-        torch = _torch()
-        if n_steps is None:
-            _lib.check(self.L.tmh_set_intervals(self._eng, None))
-            self.intervals_raw, self._intervals = None, None
-            return None
-        if self._registers is not None:
-            raise ValueError("the import / export registers are enabled: their table holds the intervals' columns "
-                             "(registers.to_intervals); one of the two per sim")
-        if self._demand is not None:
-            raise ValueError("the demand registers are enabled: their table holds the intervals' columns; one of the two per sim")
-        n_steps, interval_s = int(n_steps), int(interval_s)
-        if n_steps < 1 or interval_s < 1:
-            raise ValueError("enable_intervals: n_steps >= 1 and interval_s >= 1")
-        nk = n_intervals(n_steps, interval_s)
-        if buffer is None:
-            buffer = torch.zeros(nk, 4, self.n, dtype=torch.int64, device=self.device)
-        elif (buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (nk, 4, self.n)):
-            raise ValueError(f"intervals buffer must be an int64 [{nk}, 4, {self.n}] tensor on {self.device}")
-        ld = int(buffer.stride(1))
-        if ld < self.n or (self.n > 1 and buffer.stride(2) != 1) or (nk > 1 and buffer.stride(0) != 4 * ld):
-            raise ValueError(f"intervals buffer strides {tuple(buffer.stride())}: need (4 ld, ld, 1) with ld >= {self.n}")
-        st = _lib.Intervals(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
-        _lib.check(self.L.tmh_set_intervals(self._eng, C.byref(st)))
-        self.intervals_raw, self._intervals = buffer, st
-        return buffer
+        return self._enable_table("intervals", n_steps, interval_s, step0, buffer)
 
     def intervals(self):
         """The interval table in watts and watt-hours (intervals.to_watts of intervals_raw):
         pv, meter, residual (means over the ok seconds), energy_wh_*, n_ok and the covered
         fraction, [n_intervals, n] each."""
-        from .intervals import to_watts
-        if self.intervals_raw is None:
-            raise ValueError("no intervals: call enable_intervals first")
-        _torch().cuda.synchronize(self.device)
-        return to_watts(self.intervals_raw, self._intervals.interval_s, n_steps=self._intervals.n_steps)
+        return self._table_watts("intervals")
 
     # ------------------------------------------------------------------ import / export registers
     def enable_registers(self, n_steps, interval_s=900, step0=None, buffer=None):
@@ -275,43 +319,13 @@ class BatchedSim:
         by default a zeroed one.  Runs with registers take no traces (trace=()), no fleet
         series and no interval metering beside them; compaction is allowed.  n_steps=None
         switches the output off."""
-        from .registers import COLUMNS, n_intervals
-        torch = _torch()
-        if n_steps is None:
-            _lib.check(self.L.tmh_set_registers(self._eng, None))
-            self.registers_raw, self._registers = None, None
-            return None
-        if self._intervals is not None:
-            raise ValueError("interval metering is enabled: the registers table holds the intervals' columns "
-                             "(registers.to_intervals); one of the two per sim")
-        if self._demand is not None:
-            raise ValueError("the demand registers are enabled: their table holds the registers' columns "
-                             "(demand.to_registers); one of the two per sim")
-        n_steps, interval_s, nc = int(n_steps), int(interval_s), len(COLUMNS)
-        if n_steps < 1 or interval_s < 1:
-            raise ValueError("enable_registers: n_steps >= 1 and interval_s >= 1")
-        nk = n_intervals(n_steps, interval_s)
-        if buffer is None:
-            buffer = torch.zeros(nk, nc, self.n, dtype=torch.int64, device=self.device)
-        elif (buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (nk, nc, self.n)):
-            raise ValueError(f"registers buffer must be an int64 [{nk}, {nc}, {self.n}] tensor on {self.device}")
-        ld = int(buffer.stride(1))
-        if ld < self.n or (self.n > 1 and buffer.stride(2) != 1) or (nk > 1 and buffer.stride(0) != nc * ld):
-            raise ValueError(f"registers buffer strides {tuple(buffer.stride())}: need ({nc} ld, ld, 1) with ld >= {self.n}")
-        st = _lib.Registers(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
-        _lib.check(self.L.tmh_set_registers(self._eng, C.byref(st)))
-        self.registers_raw, self._registers = buffer, st
-        return buffer
+        return self._enable_table("registers", n_steps, interval_s, step0, buffer)
 
     def registers(self):
         """The registers table in watts and watt-hours (registers.to_watts of registers_raw): the
         intervals' keys plus energy_wh_import, energy_wh_export, energy_wh_self and the
         self_consumption and self_sufficiency ratios, [n_intervals, n] each."""
-        from .registers import to_watts
-        if self.registers_raw is None:
-            raise ValueError("no registers: call enable_registers first")
-        _torch().cuda.synchronize(self.device)
-        return to_watts(self.registers_raw, self._registers.interval_s, n_steps=self._registers.n_steps)
+        return self._table_watts("registers")
 
     # ------------------------------------------------------------------ demand registers
     def enable_demand(self, n_steps, interval_s=900, step0=None, buffer=None):
@@ -327,42 +341,13 @@ class BatchedSim:
         (trace=()), no fleet series, no interval metering and no import / export registers
         beside them (the table holds their columns); compaction is allowed.  n_steps=None
         switches the output off."""
-        from .demand import COLUMNS, n_intervals
-        torch = _torch()
-        if n_steps is None:
-            _lib.check(self.L.tmh_set_demand(self._eng, None))
-            self.demand_raw, self._demand = None, None
-            return None
-        for other, what in ((self._series, "a fleet series"), (self._intervals, "interval metering"),
-                            (self._registers, "the import / export registers")):
-            if other is not None:
-                raise ValueError(f"{what} is enabled: one table output per sim (the demand table holds the registers' "
-                                 "and the intervals' columns, demand.to_registers)")
-        n_steps, interval_s, nc = int(n_steps), int(interval_s), len(COLUMNS)
-        if n_steps < 1 or interval_s < 1:
-            raise ValueError("enable_demand: n_steps >= 1 and interval_s >= 1")
-        nk = n_intervals(n_steps, interval_s)
-        if buffer is None:
-            buffer = torch.zeros(nk, nc, self.n, dtype=torch.int64, device=self.device)
-        elif (buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (nk, nc, self.n)):
-            raise ValueError(f"demand buffer must be an int64 [{nk}, {nc}, {self.n}] tensor on {self.device}")
-        ld = int(buffer.stride(1))
-        if ld < self.n or (self.n > 1 and buffer.stride(2) != 1) or (nk > 1 and buffer.stride(0) != nc * ld):
-            raise ValueError(f"demand buffer strides {tuple(buffer.stride())}: need ({nc} ld, ld, 1) with ld >= {self.n}")
-        st = _lib.Demand(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
-        _lib.check(self.L.tmh_set_demand(self._eng, C.byref(st)))
-        self.demand_raw, self._demand = buffer, st
-        return buffer
+        return self._enable_table("demand", n_steps, interval_s, step0, buffer)
 
     def demand(self):
         """The demand table in watts and watt-hours (demand.to_watts of demand_raw): the
         registers' keys plus peak_import, peak_export, t_peak_import, t_peak_export and
         load_factor, [n_intervals, n] each."""
-        from .demand import to_watts
-        if self.demand_raw is None:
-            raise ValueError("no demand registers: call enable_demand first")
-        _torch().cuda.synchronize(self.device)
-        return to_watts(self.demand_raw, self._demand.interval_s, n_steps=self._demand.n_steps)
+        return self._table_watts("demand")
 
     def guard_records(self):
         """Tests: the fp32 guard-band records (chain, 128-s block) of the last window that run()
@@ -408,38 +393,18 @@ class BatchedSim:
             s0, sn = self._series.step0, self._series.n_steps
             if self.step < s0 or self.step + n_steps > s0 + sn:
                 raise ValueError(f"steps [{self.step}, +{n_steps}) outside the series [{s0}, +{sn})")
-        if self._intervals is not None:   # (likewise; compact=True is allowed)
+        for kind, t in _TABLES.items():   # (likewise; compact=True is allowed)
+            tb = getattr(self, "_" + kind)
+            if tb is None:
+                continue
             if self._series is not None:
-                raise ValueError("interval metering and a fleet series are both enabled: one of the two per sim")
+                raise ValueError(f"{t['name']} and a fleet series are both enabled: one of the two per sim")
+            if t["run_excludes"] and any(getattr(self, attr) is not None for attr in t["run_excludes"][0]):
+                raise ValueError(t["run_excludes"][1])
             if trace:
-                raise ValueError("an interval-metering run takes no traces (trace=()): sum the traces instead "
-                                 "(intervals.from_traces)")
-            s0, sn = self._intervals.step0, self._intervals.n_steps
-            if self.step < s0 or self.step + n_steps > s0 + sn:
-                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the intervals [{s0}, +{sn})")
-        if self._registers is not None:   # (likewise; compact=True is allowed)
-            if self._series is not None:
-                raise ValueError("the registers and a fleet series are both enabled: one of the two per sim")
-            if self._intervals is not None:
-                raise ValueError("the registers and interval metering are both enabled: one of the two per sim")
-            if trace:
-                raise ValueError("a registers run takes no traces (trace=()): sum the traces instead "
-                                 "(registers.from_traces)")
-            s0, sn = self._registers.step0, self._registers.n_steps
-            if self.step < s0 or self.step + n_steps > s0 + sn:
-                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the registers [{s0}, +{sn})")
-        if self._demand is not None:   # (likewise; compact=True is allowed)
-            if self._series is not None:
-                raise ValueError("the demand registers and a fleet series are both enabled: one of the two per sim")
-            if self._intervals is not None or self._registers is not None:
-                raise ValueError("the demand registers and interval metering or the import / export registers are both "
-                                 "enabled: one of them per sim")
-            if trace:
-                raise ValueError("a demand run takes no traces (trace=()): take the peaks of the traces instead "
-                                 "(demand.from_traces)")
-            s0, sn = self._demand.step0, self._demand.n_steps
-            if self.step < s0 or self.step + n_steps > s0 + sn:
-                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the demand registers [{s0}, +{sn})")
+                raise ValueError(t["no_trace"])
+            if self.step < tb.step0 or self.step + n_steps > tb.step0 + tb.n_steps:
+                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the {t['noun']} [{tb.step0}, +{tb.n_steps})")
         if n_steps > ROLL_MAX:   # one rolling clock covers at most ROLL_MAX steps: run in pieces (same bits)
             res = out if out is not None else self._alloc(n_steps, trace)
             done = 0
