@@ -420,22 +420,30 @@ __global__ __launch_bounds__(256, BUILD_WAVES) void geom_kernel(GParams gp, int6
 // The kind of each four-step group (first row j with (step0 + j) % 4 == 0, j + 3 < n) of a
 // window on the four-step grid, ORed into its first fp32 row's flags: FL_G_NIGHT (four night
 // seconds), FL_G_DAY (four daylight seconds with DISC valid); either only when seconds 1-3
-// carry no boundary event.  Other windows and partial groups get neither bit.
+// carry no boundary event.  Other windows and partial groups get neither bit.  A whole 128-step
+// block whose 32 groups are all night groups also gets FL_B_NIGHT on its first row.
 __global__ __launch_bounds__(256) void group_kind_kernel(int64_t step0, uint32_t n, float* tab32, double* tab64)
 {
+    static_assert(BLOCK_STEPS == 128, "a block's 32 groups are the 32 lanes of a half-wave");
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, j = 4 * g;
-    if ((step0 & 3) != 0 || j + 3 >= n) return;
-    uint32_t f[4], ev = 0, all = ~0u;
+    uint32_t f[4] = {0u, 0u, 0u, 0u}, k = 0;
+    if ((step0 & 3) == 0 && j + 3 < n) {
+        uint32_t ev = 0, all = ~0u;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        f[q] = __float_as_uint(tab32[(size_t)(j + q) * ROW32 + G_FLAGS + G32]);
-        all &= f[q];
-        if (q > 0) ev |= f[q] & (FL_DAY | FL_HOUR | FL_MIN);
+        for (int q = 0; q < 4; ++q) {
+            f[q] = __float_as_uint(tab32[(size_t)(j + q) * ROW32 + G_FLAGS + G32]);
+            all &= f[q];
+            if (q > 0) ev |= f[q] & (FL_DAY | FL_HOUR | FL_MIN);
+        }
+        const uint32_t anyn = (f[0] | f[1] | f[2] | f[3]) & FL_NIGHT;
+        if (!ev && (all & FL_NIGHT)) k = FL_G_NIGHT;
+        else if (!ev && !anyn && (all & FL_DISCOK)) k = FL_G_DAY;
     }
-    const uint32_t anyn = (f[0] | f[1] | f[2] | f[3]) & FL_NIGHT;
-    uint32_t k = 0;
-    if (!ev && (all & FL_NIGHT)) k = FL_G_NIGHT;
-    else if (!ev && !anyn && (all & FL_DISCOK)) k = FL_G_DAY;
+    // FL_B_NIGHT on the block's first row: all 32 groups of the block (one half-wave; each of
+    // them lies inside the window, so the block is a whole one) are night groups
+    const uint64_t ng = __builtin_amdgcn_ballot_w64(k == FL_G_NIGHT);
+    const uint32_t half = (threadIdx.x & 32u) ? (uint32_t)(ng >> 32) : (uint32_t)ng;
+    if ((threadIdx.x & 31u) == 0 && half == ~0u) k |= FL_B_NIGHT;
     if (k) {   // both rows: the fp32 and the fp64 single-site expansions read it
         tab32[(size_t)j * ROW32 + G_FLAGS + G32] = __uint_as_float(f[0] | k);
         tab64[(size_t)j * ROW + G_FLAGS] = (double)(f[0] | k);
@@ -446,8 +454,8 @@ __global__ __launch_bounds__(256) void group_kind_kernel(int64_t step0, uint32_t
 // blocks with a daylight second first, then the all-night blocks, each class in time order
 // (a stable partition; one workgroup).  A night tile costs a tenth of a daylight one, so the
 // expansion's last tiles are short ones and its tail no longer waits for late daylight tiles.
-// A block is all night when every four-step group of it carries FL_G_NIGHT; windows off the
-// four-step grid (no group kinds) keep the time order.
+// A block is all night when it carries FL_B_NIGHT (every four-step group of it FL_G_NIGHT);
+// windows off the four-step grid (no group kinds, no marks) keep the time order.
 __global__ __launch_bounds__(1024) void block_order_kernel(const float* __restrict__ tab32, int64_t step0, uint32_t n,
                                                            uint32_t* __restrict__ perm)
 {
@@ -455,12 +463,8 @@ __global__ __launch_bounds__(1024) void block_order_kernel(const float* __restri
     const uint32_t t = threadIdx.x, nb = (n + BLOCK_STEPS - 1) / BLOCK_STEPS;
     const uint32_t chunk = (nb + 1023) / 1024, lo = min(t * chunk, nb), hi = min(lo + chunk, nb);
     auto night = [&](uint32_t b) {
-        if ((step0 & 3) != 0) return false;
-        const uint32_t j0 = b * BLOCK_STEPS, j1 = min(j0 + (uint32_t)BLOCK_STEPS, n);
-        if (j1 - j0 < BLOCK_STEPS) return false;   // a short last block: its tail groups carry no kind
-        for (uint32_t j = j0; j < j1; j += 4)
-            if (!(__float_as_uint(tab32[(size_t)j * ROW32 + G_FLAGS + G32]) & FL_G_NIGHT)) return false;
-        return true;
+        // group_kind_kernel's mark (whole blocks of a window on the four-step grid only)
+        return (__float_as_uint(tab32[(size_t)b * BLOCK_STEPS * ROW32 + G_FLAGS + G32]) & FL_B_NIGHT) != 0;
     };
     uint32_t d = 0;
     for (uint32_t b = lo; b < hi; ++b) d += night(b) ? 0u : 1u;
@@ -2101,7 +2105,11 @@ __device__ __forceinline__ void series_flush(SeriesLds* sl, const SeriesView& se
 // One (128-second block b, chain block cblk) tile of the expansion: one work-item per
 // chain of the block (the expansion's unit of work, below).  The LDS staging areas are
 // the kernel's (one column per thread, so consecutive tiles need no barrier between them).
-template <typename R, int OUT, bool SITES, int WGT>
+// NIGHT: a tile whose every second is its meter alone (a block marked FL_B_NIGHT, or no PV), in
+// the kernels whose night second reads no covered bit (expand_kernel: the trace and the
+// statistics kernels): it loads the chain's status and fault step and nothing else -- no
+// samplers, no descriptor, no segment records, no minute draws, no staging, no guard-band record.
+template <typename R, int OUT, bool SITES, int WGT, bool NIGHT>
 __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KParams& kp, const DrawParams& dp,
                                             const StateView& st, uint64_t chain0, uint32_t n, int64_t W0,
                                             uint32_t nsteps, int64_t utc0, const double* __restrict__ tab64,
@@ -2127,6 +2135,8 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     const bool live = c < n;
     const uint32_t j0 = b * BLOCK_STEPS, j1 = min(j0 + (uint32_t)BLOCK_STEPS, nsteps);
     const uint64_t chain = chain0 + gid(kp.ids, c);
+    static_assert(!NIGHT || (!SITES && (out_base(OUT) == OUT_TRACE3 || out_base(OUT) == OUT_STATS)),
+                  "the other kernels' night seconds read the covered bits or a site's own geometry");
     const int64_t fm = first_minute(utc0, W0);
     PVF pkv = kp.pvf;   // the tile's own copy of the fp32 PV constants
     Acc acc{0.0, 0.0, 0.0, -INFINITY};
@@ -2148,17 +2158,19 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     if (live) {
         alive = st.status[c] == 0;
         fault = sg.fault[c];
-        Samp s;
+        if constexpr (!NIGHT) {
+            Samp s;
 #pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            s.b[k] = st.sb[k][c];
-            s.a[k] = st.sa[k][c];
+            for (int k = 0; k < 6; ++k) {
+                s.b[k] = st.sb[k][c];
+                s.a[k] = st.sa[k][c];
+            }
+            if constexpr (sizeof(R) == 4) load_fast_noise(st, c, s);
+            const BlockDesc d = desc[b];
+            evi = (uint32_t)d.evi;
+            if (alive && b > 0) samplers_at<R>(d, sg, n, c, s, mc, st);
+            to_real(fs, s);
         }
-        if constexpr (sizeof(R) == 4) load_fast_noise(st, c, s);
-        const BlockDesc d = desc[b];
-        evi = (uint32_t)d.evi;
-        if (alive && b > 0) samplers_at<R>(d, sg, n, c, s, mc, st);
-        to_real(fs, s);
     }
     // The block's covered bits and its minute draws staged in LDS before the loop:
     // the per-second loop then issues no vector loads, so no s_waitcnt vmcnt in it
@@ -2167,7 +2179,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // SQ_WAIT_ANY).  Word-major: lane-consecutive dwords, no bank conflicts.
     const int32_t s0i = (int32_t)(W0 + j0), s1i = (int32_t)(W0 + j1);
     const int32_t mA = (int32_t)j0 <= (int32_t)fm ? 0 : ((int32_t)j0 - (int32_t)fm + 59) / 60;
-    {
+    if constexpr (!NIGHT) {
         uint32_t cw[4] = {0u, 0u, 0u, 0u};
         if (alive) {   // segment containing the block start: first record with next-call step > start
             int lo = (int)sg.brec[(size_t)b * n + c];   // block_rec_kernel
@@ -2204,7 +2216,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     uint32_t cov_w = 0;
     const double* evd = sg.evd + c;
     // the guard-band seconds of the lane's block, a bit each, in LDS: no register carried through the loop
-    held_lds[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (!NIGHT) held_lds[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
     // Trace stores: one buffer resource per output for the block's rows (built here,
     // not per store) and one running per-lane byte offset; lanes past the last chain
     // start at 2^31, out of the resource's range, so the stores need no exec mask.
@@ -2513,6 +2525,17 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // costs a quarter of a block instead of half.
     auto loops = [&](auto ff) __attribute__((always_inline)) {
         uint32_t j = j0;
+        if constexpr (NIGHT) {   // the meter alone: four-second groups on the grid, single seconds off it
+            if (((W0 + j0) & 3) == 0)
+                for (; j + 4 <= j1; j += 4)
+                    night4(j, keyed_block(kp.seed, chain, (uint64_t)(W0 + j) >> 2, TAG_METER4, 0), ff);
+            for (; j < j1; ++j) {
+                const U4 pm = keyed_block(kp.seed, chain, (uint64_t)(W0 + j) >> 2, TAG_METER4, 0);
+                const R meter = meter_w<R>(word_of(pm, (uint32_t)(W0 + j) & 3u));
+                finish(j, j - j0, false, R(0), R(0), meter, meter, false, ff);
+            }
+            return;
+        }
         // the piece [pa, je) of the block that one metering interval covers (IVL; else the whole block)
         uint32_t pa = j0, je = IVL ? iv_next : j1;
         do {
@@ -2588,7 +2611,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // register bounds, the second copy adds spills)
     if (sizeof(R) == 4 && !SITES && wave_ok) loops(std::true_type{});
     else loops(std::false_type{});
-    if constexpr (sizeof(R) == 4) {
+    if constexpr (sizeof(R) == 4 && !NIGHT) {
         const uint4 hm = held_lds[threadIdx.x];
         const bool held_any = (hm.x | hm.y | hm.z | hm.w) != 0;
         if (live && held_any) {   // (chain, block, seconds) for fixup_kernel (outside the loop: no registers held across it)
@@ -2659,27 +2682,33 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     __shared__ __attribute__((aligned(16))) double pv_tab[sizeof(R) == 8 || SITES ? PV_TAB : 2];
     // fp32: the noise quantile's table (ndtri_t), 8 KB, copied once per workgroup
     __shared__ float4 nd_tab[sizeof(R) == 4 ? ND32_N : 1];
-    if constexpr (sizeof(R) == 8 || SITES) {
-        if (threadIdx.x < PV64_N) reinterpret_cast<double*>(pv_lds)[threadIdx.x] = reinterpret_cast<const double*>(&kp.pv64)[threadIdx.x];
-        for (uint32_t i = threadIdx.x; i < PV_TAB; i += blockDim.x) pv_tab[i] = g_pv_tab[i];
-    }
-    if constexpr (sizeof(R) == 4)
-        for (uint32_t i = threadIdx.x; i < ND32_N; i += blockDim.x) nd_tab[i] = g_nd32_tab[i];
-    __syncthreads();
     constexpr bool PACK = exp_hist_pack<R, OUT, SITES>();
     const uint32_t nw = PACK ? (sv.n_bins + 1) / 2 : sv.n_bins;   // 16-bit bin pairs, or bins
-    if (sv.hist) {
-        for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) lds_hist[i] = 0;
-        __syncthreads();
-    }
-    auto tile = [&](uint32_t b, uint32_t cblk) __attribute__((always_inline)) {
-        expand_tile<R, OUT, SITES, WGT>(b, cblk, kp, dp, st, chain0, n, W0, nsteps, utc0, tab64, tab32, sun, events,
-                                        n_events, desc, sg, tr, sv, lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab,
-                                        nd_tab, se, ser_lds, ivv);
+    auto tile = [&](uint32_t b, uint32_t cblk, auto night) __attribute__((always_inline)) {
+        expand_tile<R, OUT, SITES, WGT, decltype(night)::value>(
+            b, cblk, kp, dp, st, chain0, n, W0, nsteps, utc0, tab64, tab32, sun, events, n_events, desc, sg, tr, sv,
+            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv);
     };
-    {   // grid: x = time block, y = chain block; the workgroup's tile (bs, cs)
+    // the workgroup's LDS histogram into the device histogram
+    auto hist_flush = [&]() __attribute__((always_inline)) {
+        if (sv.hist) {
+            __syncthreads();
+            for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) {
+                const uint32_t w = lds_hist[i];
+                if constexpr (PACK) {
+                    const uint32_t lo = w & 0xFFFFu, hi = w >> 16;
+                    if (lo) atomicAdd((unsigned long long*)&sv.hist[2 * i], (unsigned long long)lo);
+                    if (hi) atomicAdd((unsigned long long*)&sv.hist[2 * i + 1], (unsigned long long)hi);   // hi = 0 past n_bins
+                } else if (w) {
+                    atomicAdd((unsigned long long*)&sv.hist[i], (unsigned long long)w);
+                }
+            }
+        }
+    };
+    // grid: x = time block, y = chain block; the workgroup's tile (bs, cs)
+    auto where = [&](uint32_t& bs, uint32_t& cs) __attribute__((always_inline)) {
         const uint32_t T = gridDim.x, CB = gridDim.y, L = blockIdx.x + T * blockIdx.y;
-        uint32_t bs = blockIdx.x, cs = blockIdx.y;   // launch order
+        bs = blockIdx.x, cs = blockIdx.y;   // launch order
         if constexpr (exp_tile_order<R, OUT, SITES>() == 1) {
             // XCD-aware tile order (speed only): the
             // hardware deals workgroups round-robin over the 8 XCDs in launch order (x fastest),
@@ -2710,21 +2739,45 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
             bs = bperm[ch * TCH + (rr - y * cc)];
             cs = y;
         }
-        tile(bs, cs);
-    }
-    if (sv.hist) {
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) {
-            const uint32_t w = lds_hist[i];
-            if constexpr (PACK) {
-                const uint32_t lo = w & 0xFFFFu, hi = w >> 16;
-                if (lo) atomicAdd((unsigned long long*)&sv.hist[2 * i], (unsigned long long)lo);
-                if (hi) atomicAdd((unsigned long long*)&sv.hist[2 * i + 1], (unsigned long long)hi);   // hi = 0 past n_bins
-            } else if (w) {
-                atomicAdd((unsigned long long*)&sv.hist[i], (unsigned long long)w);
+    };
+    // Night tiles (expand_tile's NIGHT), in the single-site kernels whose night second needs no
+    // covered bit: a block marked FL_B_NIGHT on its first row (group_kind_kernel), or any block
+    // without PV.  The block index is uniform over the workgroup, so the load and the branch are
+    // scalar.  The workgroup reads none of the LDS tables: it copies none, zeroes the histogram
+    // if there is one (waiting only then), runs its tile and ends.  A branch of its own ahead
+    // of the daylight path, which stays as it was.
+    if constexpr (!SITES && (out_base(OUT) == OUT_TRACE3 || out_base(OUT) == OUT_STATS)) {
+        uint32_t bs, cs;
+        where(bs, cs);
+        const uint32_t fl0 = sizeof(R) == 8 ? (uint32_t)tab64[(size_t)bs * BLOCK_STEPS * ROW + G_FLAGS]
+                                            : __float_as_uint(tab32[(size_t)bs * BLOCK_STEPS * ROW32 + G_FLAGS + G32]);
+        if (!kp.with_pv || (fl0 & FL_B_NIGHT)) {
+            if (sv.hist) {
+                for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) lds_hist[i] = 0;
+                __syncthreads();
             }
+            tile(bs, cs, std::true_type{});
+            hist_flush();
+            return;
         }
     }
+    if constexpr (sizeof(R) == 8 || SITES) {
+        if (threadIdx.x < PV64_N) reinterpret_cast<double*>(pv_lds)[threadIdx.x] = reinterpret_cast<const double*>(&kp.pv64)[threadIdx.x];
+        for (uint32_t i = threadIdx.x; i < PV_TAB; i += blockDim.x) pv_tab[i] = g_pv_tab[i];
+    }
+    if constexpr (sizeof(R) == 4)
+        for (uint32_t i = threadIdx.x; i < ND32_N; i += blockDim.x) nd_tab[i] = g_nd32_tab[i];
+    __syncthreads();
+    if (sv.hist) {
+        for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) lds_hist[i] = 0;
+        __syncthreads();
+    }
+    {
+        uint32_t bs, cs;
+        where(bs, cs);
+        tile(bs, cs, std::false_type{});
+    }
+    hist_flush();
 }
 
 // ------------------------------------------------------------ compaction

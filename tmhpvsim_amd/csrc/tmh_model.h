@@ -82,7 +82,12 @@ struct GParams {
 // start is on the four-step grid; group_kind_kernel): the group's four seconds are all night,
 // or all daylight with DISC valid, and its seconds 1-3 carry no boundary event, so the fp32
 // single-site expansion runs the group as straight-line code (expand_tile, FASTG)
-enum : uint32_t { FL_DAY = 1, FL_HOUR = 2, FL_MIN = 4, FL_NIGHT = 8, FL_DISCOK = 16, FL_G_NIGHT = 32, FL_G_DAY = 64 };
+// FL_B_NIGHT (on the first row of a whole 128-step block, beside FL_G_NIGHT): every four-step
+// group of the block carries FL_G_NIGHT, so the block's tile needs none of the chain's sampler
+// state (expand_kernel's night tile)
+enum : uint32_t {
+    FL_DAY = 1, FL_HOUR = 2, FL_MIN = 4, FL_NIGHT = 8, FL_DISCOK = 16, FL_G_NIGHT = 32, FL_G_DAY = 64, FL_B_NIGHT = 128
+};
 // clock/geometry table row (TMH_GEOM_FIELDS = 20)
 enum {
     G_MINF = 0, G_HOURF = 1, G_DAYF = 2, G_FLAGS = 3, G_COSZ = 4, G_CSIMAX = 5, G_GHICS = 6,
