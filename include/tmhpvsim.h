@@ -30,7 +30,9 @@
  *    the import / export registers (tmh_registers: the intervals' columns plus what
  *    the chain drew from the grid and what it fed in, per interval) or the demand
  *    registers (tmh_demand: the registers' columns plus the peak import and the peak
- *    feed-in of each interval and the second of each).
+ *    feed-in of each interval and the second of each) or battery storage (tmh_storage,
+ *    fp64 engines: the intervals' columns plus what the meter reads with a battery behind
+ *    it, what the battery took and gave and its state of charge at each interval's end).
  *  - `stream` is a hipStream_t (NULL = default stream); all work is enqueued
  *    asynchronously on it.  One engine per device; not re-entrant per engine.
  */
@@ -225,6 +227,48 @@ typedef struct tmh_intervals tmh_registers;   /* the same descriptor: sum is [n_
 #define TMH_DEMAND_COLS 8
 typedef struct tmh_intervals tmh_demand;      /* the same descriptor: sum is [n_intervals][8][ld], accumulated / maximised */
 
+/* Battery storage: a battery behind each chain's meter, charged from the PV surplus and
+ * discharged into the deficit (greedy self-consumption, lossless), and what the meter reads
+ * with it.  The state of charge (SoC) depends on every earlier second of the chain, so no
+ * other table can be post-processed into this one.  All quantities are integers in the
+ * series' units: powers in 2^-TMH_SERIES_FRAC_BITS W, energies and SoC in 2^-12 W s.
+ * capacity C (0 <= C < 2^40), p_charge Pc and p_discharge Pd (0 .. 2^27 each) are uniform
+ * over the batch; soc[i] is chain i's SoC x (i as tmh_intervals': ids[slot] under
+ * tmh_set_chain_ids), read at a window's start and written at its end.  For an ok second
+ * with d = q(pv) - q(meter):
+ *   a  = clamp(d, -Pd, Pc)      what the battery is asked to take (+) or give (-)
+ *   x' = clamp(x + a, 0, C)     (64-bit)
+ *   g  = x' - x                 what it took / gave
+ *   import_b = max(g - d, 0)    export_b = max(d - g, 0)
+ * A second that is not ok leaves x unchanged (a faulted or dead chain's battery holds its
+ * charge).  The initial x is taken as given; after the first ok second it lies in [0, C].
+ * table.sum: device int64 [n_intervals][TMH_STORAGE_COLS][ld], cell (k, col, i) at
+ * sum[(k*9 + col)*ld + i], zero-initialised by the caller.  Over the ok seconds of interval k:
+ *   [0..3] tmh_intervals' columns exactly          (added)
+ *   [4] sum of import_b   [5] sum of export_b      (added)
+ *   [6] sum of max(g, 0)  [7] sum of max(-g, 0)    (added: charged, discharged)
+ *   [8] the maximum of ((o + 1) << 40) | x'        (o: the second's offset in its interval)
+ * so [8] is the key of the interval's last ok second: its low 40 bits are the SoC at the end
+ * of the interval (or at the chain's fault); 0: no ok second.  Keys are positive and 0 is the
+ * identity of the maximum; interval_s <= 2^23 - 1.  For every cell [4] - [5] == [1] - [0] +
+ * [6] - [7], columns 4-7 are >= 0, and [6] - [7] is the interval's SoC change.  With C = 0 or
+ * Pc = Pd = 0 columns 4 and 5 are tmh_registers'.  The bits do not depend on windows,
+ * batches, shards or compaction and equal a sequential loop over the traces.
+ * fp64 engines only: an fp32 engine replaces its guard-band seconds after the expansion
+ * (fixup_kernel) -- an additive correction for a sum, but a changed second changes the SoC of
+ * every later second, so the expansion would need the fixed values before it runs.
+ * work: device scratch of the caller, >= tmh_storage_work_bytes(n_chains, n_steps) bytes for
+ * the largest window (three int64 per chain and 128-step block), 8-byte aligned; its
+ * contents mean nothing between calls. */
+#define TMH_STORAGE_COLS 9
+typedef struct tmh_storage {
+    tmh_intervals table;      /* sum is [n_intervals][9][ld] */
+    int64_t* soc;             /* device [ld]: per chain index, read at a window's start, written at its end */
+    void* work;               /* device scratch */
+    size_t work_bytes;        /* >= tmh_storage_work_bytes(n_chains, n_steps) of the largest window */
+    int64_t capacity, p_charge, p_discharge;
+} tmh_storage;
+
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
 /* TMH_SERIES_FRAC_BITS and TMH_SERIES_MAX_W as the library was built with them */
@@ -394,6 +438,21 @@ int tmh_set_registers(struct tmh_engine* eng, const tmh_registers* rg);
  * and the histogram are accumulated beside the table when tmh_stats gives them.  The table
  * is final after the TMH_EXPAND_COMMIT half. */
 int tmh_set_demand(struct tmh_engine* eng, const tmh_demand* dm);
+/* Battery storage (tmh_storage above): every later expansion of this engine advances
+ * st->soc over its window and adds the window to st->table.sum; NULL switches it off.  The
+ * expansion then runs three launches on its stream (TMH_EXPAND_KERNEL half): a map pass
+ * (each chain's 128-step blocks as composed SoC maps), a scan (each block's starting SoC) and
+ * the replay pass that writes the table; windows must run in order.  Refused here
+ * (TMH_E_INVAL, the messages name "storage"): tmh_set_intervals' bad-struct cases; a NULL or
+ * misaligned (8 bytes) soc or work; capacity outside [0, 2^40), p_charge or p_discharge
+ * outside [0, 2^27]; interval_s > 2^23 - 1; an fp32 engine.  Refused at a step / expansion
+ * call or a walk of that window, before any launch: everything tmh_set_registers refuses; any
+ * other interval table or a fleet series set too, in either order; work_bytes below
+ * tmh_storage_work_bytes of this window.  Compacted windows are accepted.  Statistics and the
+ * histogram are accumulated beside the table when tmh_stats gives them.  tmh_scratch_bytes
+ * and tmh_engine_scratch_bytes do not change: the caller owns every buffer. */
+size_t tmh_storage_work_bytes(uint32_t n_chains, uint32_t n_steps);
+int tmh_set_storage(struct tmh_engine* eng, const tmh_storage* st);
 /* Tests only: the fp32 guard-band records (chain, block) the last expansion on
  * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
  * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
@@ -488,8 +547,10 @@ int tmh_expand_part(struct tmh_engine* eng, void* state, uint64_t chain0, uint32
  * milliseconds and launch count of one kernel since the last read, then resets
  * it.  kernel: TMH_K_EXPAND (P2 trace/stats expansion), TMH_K_SEGMENTS (P1
  * segment walk), TMH_K_CANDIDATES (P1's candidate table), TMH_K_STEP (the
- * whole tmh_step). */
-enum { TMH_K_EXPAND = 0, TMH_K_SEGMENTS = 1, TMH_K_CANDIDATES = 2, TMH_K_STEP = 3, TMH_K_COUNT = 4 };
+ * whole tmh_step); with battery storage set, TMH_K_EXPAND spans the kind's three launches
+ * and TMH_K_STORAGE_MAP, TMH_K_STORAGE_SCAN and TMH_K_STORAGE_REPLAY time each of them. */
+enum { TMH_K_EXPAND = 0, TMH_K_SEGMENTS = 1, TMH_K_CANDIDATES = 2, TMH_K_STEP = 3, TMH_K_STORAGE_MAP = 4,
+       TMH_K_STORAGE_SCAN = 5, TMH_K_STORAGE_REPLAY = 6, TMH_K_COUNT = 7 };
 int tmh_profile_enable(struct tmh_engine* eng, int on);
 int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* launches);
 
@@ -500,7 +561,8 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * (statistics only), TMH_OUT_SERIES (a fleet series, with or without statistics),
  * TMH_OUT_INTERVALS (interval metering, with or without statistics),
  * TMH_OUT_REGISTERS (import / export registers, with or without statistics),
- * TMH_OUT_DEMAND (demand registers, with or without statistics), plus
+ * TMH_OUT_DEMAND (demand registers, with or without statistics), TMH_OUT_STORAGE (battery
+ * storage: the replay pass, the last of the kind's three launches, with or without statistics), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
@@ -510,6 +572,7 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
 #define TMH_OUT_INTERVALS 4
 #define TMH_OUT_REGISTERS 5
 #define TMH_OUT_DEMAND 6
+#define TMH_OUT_STORAGE 7
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

@@ -3,9 +3,10 @@
 kernel) of the statistics-only expansion and of the expansions with a table, same chains,
 same window, same process, the runs alternating.
 
-    python scripts/table_cost.py --kind intervals|registers|demand [--chains 65536] [--steps 86400]
+    python scripts/table_cost.py --kind intervals|registers|demand|storage [--chains 65536] [--steps 86400]
                                  [--interval 900] [--rounds 5] [--precision fp32]
                                  [--start "2019-09-05 00:00:00"] [--out FILE.json]
+                                 [--modules 1 --capacity-wh 5000 --charge-w 2500 --discharge-w 2500]
 
 The runs of a kind, each with the same statistics beside its table:
   intervals: OUT_STATS and OUT_INTERVALS;
@@ -13,7 +14,12 @@ The runs of a kind, each with the same statistics beside its table:
              are the intervals' table and import - export == meter - pv in every cell;
   demand:    OUT_STATS, OUT_REGISTERS and OUT_DEMAND -- the demand table's first six columns
              are the registers' table and every cell with an ok second has both keys (offset
-             inside the interval, peak x n_ok >= the sum).
+             inside the interval, peak x n_ok >= the sum);
+  storage:   OUT_STATS, OUT_REGISTERS and OUT_STORAGE, on an fp64 engine (the script sets the precision) --
+             the storage table's first four columns are the registers' and [4] - [5] == [1] - [0] + [6] - [7]
+             in every cell; its three launches (map pass, scan, replay) are timed separately as well
+             (TMH_K_STORAGE_*), inside the TMH_K_EXPAND span.  --modules k scales the PV system (k modules) so
+             that the battery of --capacity-wh / --charge-w / --discharge-w charges and discharges.
 The script checks each run's variant, these identities (on the warm-up round's tables), that
 the statistics of all runs agree bit for bit and that every table's ok seconds equal the
 histogram's count.  One warm-up round, then --rounds timed ones.  Prints one JSON line: the
@@ -35,6 +41,7 @@ RUNS = {
     "intervals": (("stats_only", None), ("with_intervals", "intervals")),
     "registers": (("stats_only", None), ("intervals", "intervals"), ("registers", "registers")),
     "demand": (("stats_only", None), ("registers", "registers"), ("demand", "demand")),
+    "storage": (("stats_only", None), ("registers", "registers"), ("storage", "storage")),
 }
 
 
@@ -54,6 +61,12 @@ def check_tables(kind, tables, interval_s):
             off = torch.where(key != 0, 0xFFFFFFFF - (key & 0xFFFFFFFF), torch.zeros_like(key))
             assert int(off.max()) < interval_s and bool(((key >> 32) * n_ok >= dm[:, reg]).all())
         return int((dm[:, 7] >> 32 > 0).sum())
+    if kind == "storage":
+        st, rg = tables["storage"], tables["registers"]
+        assert torch.equal(st[:, :4], rg[:, :4]) and bool((st[:, 4:8] >= 0).all())
+        assert torch.equal(st[:, 4] - st[:, 5], st[:, 1] - st[:, 0] + st[:, 6] - st[:, 7])
+        assert torch.equal(st[:, 8] != 0, st[:, 2] > 0) and int((st[:, 8] >> 40).max()) <= interval_s
+        return int((st[:, 5] > 0).sum())
     return None
 
 
@@ -67,7 +80,13 @@ def main():
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--start", default="2019-09-05 00:00:00")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--modules", type=int, default=1, help="PV modules per chain (the inverter scaled alike)")
+    ap.add_argument("--capacity-wh", type=float, default=5000.0)
+    ap.add_argument("--charge-w", type=float, default=2500.0)
+    ap.add_argument("--discharge-w", type=float, default=2500.0)
     a = ap.parse_args()
+    if a.kind == "storage":
+        a.precision = "fp64"   # (the kind's engines)
     import torch
     from tmhpvsim_amd import _lib
     from tmhpvsim_amd.engine import BatchedSim
@@ -75,21 +94,38 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("table_cost.py needs a GPU")
     out_of = {None: _lib.OUT_STATS, "intervals": _lib.OUT_INTERVALS, "registers": _lib.OUT_REGISTERS,
-              "demand": _lib.OUT_DEMAND}
+              "demand": _lib.OUT_DEMAND, "storage": _lib.OUT_STORAGE}
+    parts = (("map", _lib.K_STORAGE_MAP), ("scan", _lib.K_STORAGE_SCAN), ("replay", _lib.K_STORAGE_REPLAY))
+    part_ms = {name: [] for name, _ in parts}
+    mp = ModelParams()
+    if a.modules != 1:   # k modules on a k-fold inverter
+        import dataclasses
+        mod, inv = dict(mp.module), dict(mp.inverter)
+        mod["Impo"] *= a.modules
+        for key in ("Paco", "Pdco", "Pso", "Pnt"):
+            inv[key] *= a.modules
+        inv["C0"] /= a.modules
+        mp = dataclasses.replace(mp, module=mod, inverter=inv)
+    battery = dict(capacity_wh=a.capacity_wh, charge_w=a.charge_w, discharge_w=a.discharge_w, soc0_wh=a.capacity_wh / 2)
     runs = RUNS[a.kind]
     labels = [label for label, _ in runs]
 
     def one(table):
-        sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=ModelParams(), precision=a.precision,
+        sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=mp, precision=a.precision,
                          device="cuda:0", horizon=a.steps)
         sim.enable_stats()
-        raw = getattr(sim, "enable_" + table)(a.steps, a.interval) if table else None
+        raw = getattr(sim, "enable_" + table)(a.steps, a.interval, **(battery if table == "storage" else {})) if table else None
         _lib.check(sim.L.tmh_profile_enable(sim._eng, 1))
         sim.run(a.steps, trace=(), window=a.steps)
         torch.cuda.synchronize()
         ms, launches = _lib.profile_read(sim._eng, _lib.K_EXPAND)
         want = out_of[table] | (_lib.OUT_FP64 if a.precision == "fp64" else 0)
         assert launches == 1 and sim.L.tmh_engine_last_expand(sim._eng) == want, (launches, want)
+        if table == "storage":   # its three launches, once each, inside the span read above
+            for name, kk in parts:
+                pms, pn = _lib.profile_read(sim._eng, kk)
+                assert pn == 1
+                part_ms[name].append(pms)
         if raw is not None:
             assert int(raw[:, 2].sum()) == int(sim.hist.sum()) > 0
         return ms, sim.hist.clone(), sim.chain_acc.clone(), raw
@@ -97,6 +133,8 @@ def main():
     tables = {table: one(table)[3] for _, table in runs}   # warm-up: code objects, allocator
     export_cells = check_tables(a.kind, tables, a.interval)
     del tables
+    for v in part_ms.values():
+        v.clear()   # (the warm-up round's)
     t = {label: [] for label in labels}
     ref = None
     for _ in range(a.rounds):
@@ -121,6 +159,12 @@ def main():
                       f"ratio_{a.kind}_{below}": med[a.kind] / med[below],
                       f"ratio_{below}_stats": med[below] / med["stats_only"]},
                    ns_per_chain_second=ns)
+    if a.kind == "storage":
+        pmed = {name: statistics.median(v) for name, v in part_ms.items()}
+        res.update(modules=a.modules, battery=battery, **{f"storage_{k}_ms": v for k, v in part_ms.items()},
+                   **{f"storage_{k}_median_ms": v for k, v in pmed.items()},
+                   scan_share=pmed["scan"] / med["storage"], ratio_replay_registers=pmed["replay"] / med["registers"],
+                   ratio_map_registers=pmed["map"] / med["registers"], scan_over_replay=pmed["scan"] / pmed["replay"])
     res["build_stamp"] = _lib.loaded_stamp()
     line = json.dumps(res)
     print(line)

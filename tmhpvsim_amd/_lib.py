@@ -77,6 +77,13 @@ class Intervals(C.Structure):
 Registers = Demand = Intervals   # typedefs of tmh_intervals in the header
 
 
+class Storage(C.Structure):
+    """tmh_storage: the battery-storage table (tmh_intervals with 9 columns), the per-chain state of charge, the
+    window's work buffer and the battery's integers (tmh_set_storage)."""
+    _fields_ = [("table", Intervals), ("soc", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t),
+                ("capacity", C.c_int64), ("p_charge", C.c_int64), ("p_discharge", C.c_int64)]
+
+
 EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_bytes", "tmh_state_offsets", "tmh_plan_bytes",
            "tmh_scratch_bytes", "tmh_engine_scratch_bytes", "tmh_workspace_bytes", "tmh_engine_create", "tmh_engine_destroy", "tmh_engine_path",
            "tmh_init", "tmh_run", "tmh_plan", "tmh_step", "tmh_probe", "tmh_profile_enable", "tmh_profile_read",
@@ -85,8 +92,9 @@ EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_by
            "tmh_set_walk_chains_per_row", "tmh_set_walk_lanes", "tmh_set_chain_ids", "tmh_live_chains", "tmh_state_move",
            "tmh_stream_create_cus", "tmh_stream_destroy", "tmh_set_walk_order", "tmh_engine_last_expand",
            "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals",
-           "tmh_set_registers", "tmh_set_demand"]
+           "tmh_set_registers", "tmh_set_demand", "tmh_set_storage", "tmh_storage_work_bytes"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
+K_STORAGE_MAP, K_STORAGE_SCAN, K_STORAGE_REPLAY = 4, 5, 6   # battery storage's three launches (inside K_EXPAND)
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
 EXPAND_KERNEL, EXPAND_COMMIT, EXPAND_MINUTES, EXPAND_NO_MINUTES = 1, 2, 4, 8
 OUT_ANY, OUT_TRACE3, OUT_STATS, OUT_SITES, OUT_FP64 = 0, 1, 2, 16, 32   # tmh_engine_last_expand
@@ -94,6 +102,7 @@ OUT_SERIES = 3
 OUT_INTERVALS = 4
 OUT_REGISTERS = 5
 OUT_DEMAND = 6
+OUT_STORAGE = 7
 
 _lib = None
 
@@ -191,6 +200,10 @@ def load():
     L.tmh_set_registers.restype = C.c_int
     L.tmh_set_demand.argtypes = [p, C.POINTER(Demand)]
     L.tmh_set_demand.restype = C.c_int
+    L.tmh_set_storage.argtypes = [p, C.POINTER(Storage)]
+    L.tmh_set_storage.restype = C.c_int
+    L.tmh_storage_work_bytes.argtypes = [u32, u32]
+    L.tmh_storage_work_bytes.restype = sz
     L.tmh_series_frac_bits.restype = C.c_int
     L.tmh_series_max_w.restype = C.c_double
     L.tmh_test_guard_records.argtypes = [p, p, u32, u32]

@@ -17,6 +17,9 @@ tmhpvsim/metersim.py:79-95).
                                               [--precision fp32|fp64] [--start T --seconds S --seed K]
     python -m tmhpvsim_amd.cli demand FILE --batch N --no-realtime --interval S [--all-chains NPZ]
                                            [--precision fp32|fp64] [--start T --seconds S --seed K]
+    python -m tmhpvsim_amd.cli storage FILE --batch N --no-realtime --interval S --capacity-wh X --charge-w P
+                                            --discharge-w P [--soc0-wh X] [--all-chains NPZ]
+                                            [--start T --seconds S --seed K]
 
 Without --batch the commands are the reference's AMQP pipelines (a fanout
 exchange carrying one JSON float per second, pvsim.py:43-84, metersim.py:13-62):
@@ -52,6 +55,13 @@ plus each interval's peak import and peak feed-in and when each happened) and wr
 t_peak_export_s` -- the highest power drawn from the grid and fed in (W) and the earliest
 second of the interval at which each occurred; --all-chains writes every chain's raw table
 and its arrays to an .npz.
+`storage` runs N chains with a battery behind each meter (tmhpvsim_amd.storage: capacity
+--capacity-wh, power limits --charge-w and --discharge-w, every battery starting at --soc0-wh;
+greedy self-consumption, lossless; an fp64 engine run) and writes chain 0's intervals: header
+`time,import_wh,export_wh,pv_wh,meter_wh,charge_wh,discharge_wh,soc_wh,n_ok` -- the energy
+drawn from the grid and fed in with the battery, produced, consumed, put into and taken out of
+the battery (Wh), the state of charge at the interval's end and the ok seconds; --all-chains
+writes every chain's raw table and its arrays to an .npz.
 There is no CPU fallback: the batch mode fails if the engine cannot run.
 """
 from __future__ import annotations
@@ -102,9 +112,9 @@ def _fleet_run(n, start, seconds, seed, precision, bin_s):
     return {k: v[0] for k, v in out.items()}
 
 
-def _table_run(kind, n, start, seconds, seed, precision, interval_s):
-    """An engine run with the interval table `kind` ("intervals", "registers" or "demand") only:
-    the raw table and its watt / watt-hour arrays."""
+def _table_run(kind, n, start, seconds, seed, precision, interval_s, **enable_kw):
+    """An engine run with the interval table `kind` ("intervals", "registers", "demand" or "storage")
+    only: the raw table and its watt / watt-hour arrays.  enable_kw: the kind's own arguments."""
     from .engine import BatchedSim
     from .params import ModelParams
     import torch
@@ -113,7 +123,7 @@ def _table_run(kind, n, start, seconds, seed, precision, interval_s):
     params = ModelParams(seed=int(seed))
     sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
                      horizon=int(seconds))
-    raw = getattr(sim, "enable_" + kind)(int(seconds), int(interval_s))
+    raw = getattr(sim, "enable_" + kind)(int(seconds), int(interval_s), **enable_kw)
     sim.run(int(seconds), trace=())
     out = getattr(sim, kind)()
     bad = int((sim.status() != 0).sum())
@@ -233,12 +243,15 @@ TABLE_CSV = {
     "registers": REGISTERS_CSV,
     "demand": REGISTERS_CSV + (("peak_import_w", "peak_import"), ("t_peak_import_s", "t_peak_import"),
                                ("peak_export_w", "peak_export"), ("t_peak_export_s", "t_peak_export")),
+    "storage": (("import_wh", "energy_wh_import"), ("export_wh", "energy_wh_export"), ("pv_wh", "energy_wh_pv"),
+                ("meter_wh", "energy_wh_meter"), ("charge_wh", "energy_wh_charge"), ("discharge_wh", "energy_wh_discharge"),
+                ("soc_wh", "soc_wh"), ("n_ok", "n_ok")),
 }
 
 
-def _table_command(kind, file, batch, start, seconds, seed, precision, interval_s, all_chains):
-    """The `intervals`, `registers` and `demand` commands: chain 0's rows to FILE, every chain to the .npz."""
-    raw, out = _table_run(kind, batch, start, seconds, seed, precision, interval_s)
+def _table_command(kind, file, batch, start, seconds, seed, precision, interval_s, all_chains, **enable_kw):
+    """The `intervals`, `registers`, `demand` and `storage` commands: chain 0's rows to FILE, every chain to the .npz."""
+    raw, out = _table_run(kind, batch, start, seconds, seed, precision, interval_s, **enable_kw)
     t0 = dt.datetime.fromisoformat(str(start))
     rows = raw.shape[0]
     with open(file, mode="w", newline="") as fh:
@@ -292,6 +305,25 @@ def demand(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, s
     logging.basicConfig(level=logging.WARN - 10 * verbose)
     _need_batch(realtime, batch, "demand")
     _table_command("demand", file, batch, start, seconds, seed, precision, interval_s, all_chains)
+
+
+@main.command()
+@click.argument("file")
+@common
+@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
+@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
+              help="seconds per metering interval (a last partial interval is kept)")
+@click.option("--capacity-wh", type=float, required=True, help="battery capacity (Wh)")
+@click.option("--charge-w", type=float, required=True, help="charge power limit (W)")
+@click.option("--discharge-w", type=float, required=True, help="discharge power limit (W)")
+@click.option("--soc0-wh", type=float, default=0.0, help="every battery's state of charge at the start (Wh)")
+def storage(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
+            charge_w, discharge_w, soc0_wh):
+    """Battery storage of chain 0 over --batch chains to FILE (CSV; storage-only fp64 engine run)."""
+    logging.basicConfig(level=logging.WARN - 10 * verbose)
+    _need_batch(realtime, batch, "storage")
+    _table_command("storage", file, batch, start, seconds, seed, "fp64", interval_s, all_chains, capacity_wh=capacity_wh,
+                   charge_w=charge_w, discharge_w=discharge_w, soc0_wh=soc0_wh)
 
 
 if __name__ == "__main__":

@@ -48,7 +48,7 @@
 using namespace tmh;
 static_assert(OUT_ANY == TMH_OUT_ANY && OUT_TRACE3 == TMH_OUT_TRACE3 && OUT_STATS == TMH_OUT_STATS &&
                   OUT_SERIES == TMH_OUT_SERIES && OUT_INTERVALS == TMH_OUT_INTERVALS &&
-                  OUT_REGISTERS == TMH_OUT_REGISTERS && OUT_DEMAND == TMH_OUT_DEMAND,
+                  OUT_REGISTERS == TMH_OUT_REGISTERS && OUT_DEMAND == TMH_OUT_DEMAND && OUT_STORAGE == TMH_OUT_STORAGE,
               "expansion variants: tmh_model.h and include/tmhpvsim.h agree");
 
 namespace {
@@ -2120,16 +2120,26 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                             uint32_t (*cov_lds)[WGT], R (*min_lds)[WGT], uint4* held_lds,
                                             const PV64* pv_lds, const double* pv_lds_tab,
                                             const float4* nd_lds, const SeriesView& se, SeriesLds* ser_lds,
-                                            const IntervalsView& ivv)
+                                            const IntervalsView& ivv, const StorageView& sto)
 {
     constexpr bool SER = out_base(OUT) == OUT_SERIES;
+    // Battery storage (fp64 only), two passes over the same per-second body:
+    // MAP: no output but d = q(pv) - q(meter) -- the lane composes its ok seconds' clamped additions
+    // into one SocMap and stores it in the work buffer; no pieces, no atomics, no statistics.
+    // REP: the replay -- the intervals' pieces and flush with IVC = 9 columns; the lane's state of charge
+    // starts from what storage_scan_kernel left in the block's first work slot and is carried through
+    // the seconds.
+    constexpr bool STO = out_base(OUT) == OUT_STORAGE;
+    constexpr bool MAP = STO && (OUT & OUT_MAP) != 0;
+    constexpr bool REP = STO && !MAP;
+    static_assert(!STO || sizeof(R) == 8, "battery storage: fp64 engines only (no guard-band seconds)");
     // REG: the import / export registers -- the intervals' pieces, accumulators and flush, with
     // one more accumulator and IVC = 6 columns per cell instead of 4
     // DEM: the demand registers -- the registers' six columns and two more per cell, the
     // peak import and the peak export as packed keys (demand_key), combined by maximum
     constexpr bool DEM = out_base(OUT) == OUT_DEMAND;
     constexpr bool REG = out_base(OUT) == OUT_REGISTERS || DEM;
-    constexpr bool IVL = out_base(OUT) == OUT_INTERVALS || REG;
+    constexpr bool IVL = out_base(OUT) == OUT_INTERVALS || REG || REP;
     constexpr int IVC = interval_cols(OUT);
     const uint32_t c = cblk * blockDim.x + threadIdx.x;
     const bool live = c < n;
@@ -2308,6 +2318,18 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     long long iv_pv = 0, iv_m = 0, iv_ex = 0;
     int dm_im = 0, dm_ex = 0;
     uint32_t dm_imj = 0, dm_exj = 0;
+    // Battery storage.  MAP: the block's composed map.  REP: the lane's state of charge sx, its value at the
+    // piece's start sx0, and the piece's sums of export_b (iv_ex) and of the charge max(g, 0) (st_ch).  The
+    // other three columns need no accumulator: per second import_b - export_b = g - d and max(g, 0) -
+    // max(-g, 0) = g, so over the piece import_b = export_b + (sx - sx0) - (iv_pv - iv_m) and the
+    // discharge is st_ch - (sx - sx0), exact in integers.  A second that is not ok leaves sx as it is,
+    // so sx at the piece's end is the state after the piece's last ok second: the SoC key needs no tracking.
+    SocMap st_map = soc_identity();
+    long long sx = 0, sx0 = 0, st_ch = 0;
+    if constexpr (REP) {
+        if (live) sx = sto.work[(size_t)b * 3 * n + c];
+        sx0 = sx;
+    }
     uint32_t iv_k = 0, iv_next = j1;
     if constexpr (IVL) {
         iv_k = __builtin_amdgcn_readfirstlane((ivv.rel0 + j0) / ivv.interval_s);
@@ -2324,9 +2346,22 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 if (im) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)im);
                 if (iv_ex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)iv_ex);
             }
+            if constexpr (REP) {
+                const long long dx = sx - sx0, im = iv_ex + dx - (iv_pv - iv_m), dis = st_ch - dx;
+                if (im) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)im);
+                if (iv_ex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)iv_ex);
+                if (st_ch) atomicAdd(cell + 6 * ivv.ld, (unsigned long long)st_ch);
+                if (dis) atomicAdd(cell + 7 * ivv.ld, (unsigned long long)dis);
+            }
             const int32_t lo = (int32_t)(pa - j0), hi = min((int32_t)pb, fault_eff) - (int32_t)j0;
             if (hi > lo) {
                 atomicAdd(cell + 2 * ivv.ld, (unsigned long long)(hi - lo));
+                if constexpr (REP) {
+                    // the piece's last ok second, block-relative hi - 1; ob as for the demand keys
+                    const uint32_t ob = ivv.rel0 + j0 - iv_k * ivv.interval_s;
+                    __hip_atomic_fetch_max(cell + 8 * ivv.ld, soc_key(ob + (uint32_t)(hi - 1), sx), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                }
                 if constexpr (DEM) {
                     // offset of the block's first second in interval iv_k (mod 2^32: the piece's
                     // seconds lie in the interval, so ob + jb is their offset)
@@ -2349,6 +2384,11 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         iv_pv = 0;
         iv_m = 0;
         if constexpr (REG) iv_ex = 0;
+        if constexpr (REP) {
+            iv_ex = 0;
+            st_ch = 0;
+            sx0 = sx;
+        }
         if constexpr (DEM) {
             dm_im = 0;
             dm_ex = 0;
@@ -2378,7 +2418,30 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             if (__builtin_constant_p(pv) && pv == R(0)) series_add<false>(ser_lds, jb, 0, qm, nok, ncov);
             else series_add<true>(ser_lds, jb, okl ? series_q<R>(pv) : 0, qm, nok, ncov);
         }
-        if constexpr (IVL) {
+        if constexpr (STO) {
+            // the battery's second: d = q(pv) - q(meter) (a night second's literal pv = 0: -q(meter)), the
+            // ask a = clamp(d, -Pd, Pc), and the clamped addition x -> clamp(x + a, 0, C); a second that is
+            // not ok is the identity (lanes past the last chain are never stored or flushed)
+            const int qm = series_q<R>(meter);
+            int qp = 0;
+            if (!(__builtin_constant_p(pv) && pv == R(0))) qp = series_q<R>(pv);
+            const int d = qp - qm;
+            const long long a = (long long)soc_ask(d, sto.p_charge, sto.p_discharge);
+            if constexpr (MAP) {
+                const SocMap f = soc_compose(st_map, SocMap{a, 0, sto.cap});
+                st_map.a = ok ? f.a : st_map.a;
+                st_map.lo = ok ? f.lo : st_map.lo;
+                st_map.hi = ok ? f.hi : st_map.hi;
+            } else {
+                const long long xn = soc_clamp(sx + a, 0, sto.cap);
+                const int g = ok ? (int)(xn - sx) : 0;
+                sx = ok ? xn : sx;
+                iv_m += (long long)(ok ? qm : 0);
+                if (!(__builtin_constant_p(pv) && pv == R(0))) iv_pv += (long long)(ok ? qp : 0);
+                iv_ex += (long long)(ok ? max(d - g, 0) : 0);
+                st_ch += (long long)max(g, 0);
+            }
+        } else if constexpr (IVL) {
             // the lane's own sums of the piece; a second that is not ok adds 0, a night second's
             // literal pv = 0 nothing (lanes past the last chain are never flushed)
             if constexpr (!REG) {
@@ -2418,6 +2481,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             row_store(rs_pv, voff, so, pv);
             row_store(rs_m, voff, so, meter);
             row_store(rs_r, voff, so, res);
+        } else if constexpr (MAP) {   // the map pass: no trace, no statistics (the replay pass has them)
         } else if (live) {
             emit<R, OUT, exp_hist_pack<R, OUT, SITES>()>(tr, sv, lds_hist, (uint64_t)j * tr.ld + c, cov, csi, pv, meter,
                                                          res, acc, ok, held);
@@ -2622,6 +2686,15 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                               cov_lds[3][threadIdx.x])};
         }
     }
+    if constexpr (MAP) {   // the block's map, lane-consecutive ([block][3][n]); the launch carries no statistics
+        if (live) {
+            long long* w = sto.work + (size_t)b * 3 * n + c;
+            w[0] = st_map.a;
+            w[n] = st_map.lo;
+            w[2 * (size_t)n] = st_map.hi;
+        }
+        return;
+    }
     if (live && sv.acc) {   // the block's sums into the chain's fixed-point window totals (order-free)
         unsigned long long* fx = reinterpret_cast<unsigned long long*>(sg.acc_fx);
         atomicAdd(fx + c, (unsigned long long)llrint(acc.pv * sg.fx_scale));
@@ -2643,7 +2716,8 @@ template <int OUT>
 using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView,
                                    std::conditional_t<out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS ||
                                                           out_base(OUT) == OUT_DEMAND,
-                                                      IntervalsView, TraceView>>;
+                                                      IntervalsView,
+                                                      std::conditional_t<out_base(OUT) == OUT_STORAGE, StorageView, TraceView>>>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
                                                      uint32_t n, int64_t W0, uint32_t nsteps, int64_t utc0,
@@ -2660,10 +2734,14 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     TraceView tr{};
     SeriesView se{};
     IntervalsView ivv{};
+    StorageView sto{};
     if constexpr (out_base(OUT) == OUT_SERIES) se = ov;
     else if constexpr (out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS || out_base(OUT) == OUT_DEMAND)
         ivv = ov;
-    else tr = ov;
+    else if constexpr (out_base(OUT) == OUT_STORAGE) {   // battery storage: its table through the intervals' view
+        sto = ov;
+        ivv = ov.iv;
+    } else tr = ov;
     SeriesLds* const ser_lds = series_lds<out_base(OUT) == OUT_SERIES>();
     if constexpr (out_base(OUT) == OUT_SERIES) {
         for (uint32_t i = threadIdx.x; i < BLOCK_STEPS; i += blockDim.x) {
@@ -2687,7 +2765,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     auto tile = [&](uint32_t b, uint32_t cblk, auto night) __attribute__((always_inline)) {
         expand_tile<R, OUT, SITES, WGT, decltype(night)::value>(
             b, cblk, kp, dp, st, chain0, n, W0, nsteps, utc0, tab64, tab32, sun, events, n_events, desc, sg, tr, sv,
-            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv);
+            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv, sto);
     };
     // the workgroup's LDS histogram into the device histogram
     auto hist_flush = [&]() __attribute__((always_inline)) {
@@ -2778,6 +2856,43 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
         tile(bs, cs, std::false_type{});
     }
     hist_flush();
+}
+
+// Battery storage, between the map pass and the replay pass: one lane per chain walks the window's
+// blocks in order from the chain's state of charge, puts each block's starting state in place of the
+// map's first slot and applies the map; the state after the last block goes back to soc.  No lane
+// waits for another: the only dependent chain is the lane's own add and two clamps per block.  The
+// loads are lane-consecutive and do not depend on the state, so SCAN_G blocks' maps are loaded ahead
+// of the chain that consumes them.  (soc: per chain index, ids[slot] in a compacted window.)
+constexpr uint32_t SCAN_G = 8;
+__global__ __launch_bounds__(256) void storage_scan_kernel(long long* __restrict__ work, long long* __restrict__ soc,
+                                                           const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    const uint32_t i = gid(ids, c);
+    long long x = soc[i];
+    long long* w = work + c;
+    const size_t bs = (size_t)3 * n;   // a block's three rows
+    uint32_t b = 0;
+    for (; b + SCAN_G <= nblk; b += SCAN_G) {
+        SocMap f[SCAN_G];
+#pragma unroll
+        for (uint32_t k = 0; k < SCAN_G; ++k) f[k] = SocMap{w[k * bs], w[k * bs + n], w[k * bs + 2 * (size_t)n]};
+#pragma unroll
+        for (uint32_t k = 0; k < SCAN_G; ++k) {
+            w[k * bs] = x;
+            x = soc_apply(f[k], x);
+        }
+        w += SCAN_G * bs;
+    }
+    for (; b < nblk; ++b) {
+        const SocMap f{w[0], w[n], w[2 * (size_t)n]};
+        w[0] = x;
+        x = soc_apply(f, x);
+        w += bs;
+    }
+    soc[i] = x;
 }
 
 // ------------------------------------------------------------ compaction
@@ -3292,7 +3407,7 @@ void with_real(bool f64, F&& f)
 // one kind per engine at a step.  A kind is its column count, the expansion's and the fixup's
 // output, and the words the refusals name it by; a new kind is a row here, its columns in
 // expand_tile and the fixup, and its exported setter.
-enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_KINDS };
+enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_KINDS };
 struct TableKindInfo {
     int cols, out;
     const char* what;   // in the setter's and the checks' messages
@@ -3302,10 +3417,14 @@ constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
     {4, OUT_INTERVALS, "intervals", "interval metering"},
     {TMH_REGISTERS_COLS, OUT_REGISTERS, "registers", "the import / export registers"},
     {TMH_DEMAND_COLS, OUT_DEMAND, "demand registers", "the demand registers"},
+    // battery storage (tmh_storage: the descriptor's other fields sit beside the slot, tmh_engine::storage);
+    // fp64 engines only, three launches (phase_expand), no fixup
+    {TMH_STORAGE_COLS, OUT_STORAGE, "storage tables", "battery storage"},
 };
 static_assert(interval_cols(OUT_INTERVALS) == TABLE_KINDS[TBL_INTERVALS].cols &&
                   interval_cols(OUT_REGISTERS) == TABLE_KINDS[TBL_REGISTERS].cols &&
-                  interval_cols(OUT_DEMAND) == TABLE_KINDS[TBL_DEMAND].cols,
+                  interval_cols(OUT_DEMAND) == TABLE_KINDS[TBL_DEMAND].cols &&
+                  interval_cols(OUT_STORAGE) == TABLE_KINDS[TBL_STORAGE].cols,
               "the kernels' cells");
 
 }  // namespace
@@ -3329,6 +3448,7 @@ struct tmh_engine {
         bool set = false;   // tmh_set_intervals / _registers / _demand: every expansion adds its window to `t`
         tmh_intervals t{};
     } tables[TBL_KINDS];
+    tmh_storage storage{};   // tmh_set_storage: the battery, soc and the work buffer beside tables[TBL_STORAGE]
     // the first set kind (TBL_KINDS: none); a step is refused unless it is the only one (check_interval_tables)
     int table_kind() const
     {
@@ -3796,6 +3916,43 @@ int tmh_set_intervals(struct tmh_engine* eng, const tmh_intervals* iv) { return 
 int tmh_set_registers(struct tmh_engine* eng, const tmh_registers* rg) { return set_interval_table(eng, TBL_REGISTERS, rg); }
 int tmh_set_demand(struct tmh_engine* eng, const tmh_demand* dm) { return set_interval_table(eng, TBL_DEMAND, dm); }
 
+size_t tmh_storage_work_bytes(uint32_t n_chains, uint32_t n_steps)
+{
+    return (size_t)nblk_of(n_steps) * 3 * n_chains * sizeof(long long);
+}
+// battery storage: the table through the kinds' one setter, the battery's own fields checked here
+int tmh_set_storage(struct tmh_engine* eng, const tmh_storage* st)
+{
+    if (!st) {
+        if (int rc = set_interval_table(eng, TBL_STORAGE, nullptr)) return rc;
+        eng->storage = tmh_storage{};
+        return TMH_OK;
+    }
+    const char* what = TABLE_KINDS[TBL_STORAGE].what;
+    if (!st->table.sum || st->table.n_steps == 0 || st->table.ld == 0 || ((uintptr_t)st->table.sum & 7) ||
+        st->table.interval_s == 0)   // (the struct's cases, in the setter's words)
+        return set_interval_table(nullptr, TBL_STORAGE, &st->table);
+    if (st->table.interval_s > (1u << 23) - 1)
+        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
+                    st->table.interval_s);
+    if (!st->soc || ((uintptr_t)st->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer", what);
+    if (!st->work || ((uintptr_t)st->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
+    if (st->capacity < 0 || st->capacity >= (1ll << 40))
+        return fail(TMH_E_INVAL, "%s: capacity %lld outside [0, 2^40)", what, (long long)st->capacity);
+    if (st->p_charge < 0 || st->p_charge > (1ll << 27) || st->p_discharge < 0 || st->p_discharge > (1ll << 27))
+        return fail(TMH_E_INVAL, "%s: p_charge %lld, p_discharge %lld outside [0, 2^27]", what, (long long)st->p_charge,
+                    (long long)st->p_discharge);
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    // an fp32 engine replaces its guard-band seconds after the expansion (fixup_kernel): a correction that
+    // is additive for a sum, but a changed second changes the state of charge of every later one
+    if (eng->kp.precision != TMH_FP64)
+        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
+                                 "expansion, and the state of charge depends on every earlier second)", what);
+    if (int rc = set_interval_table(eng, TBL_STORAGE, &st->table)) return rc;
+    eng->storage = *st;
+    return TMH_OK;
+}
+
 // A step / expansion with an interval table set (nothing to check without one): everything the
 // kernels assume, checked on the host before any launch (tmhpvsim.h, tmh_set_intervals,
 // tmh_set_registers, tmh_set_demand).  The messages name the first set kind; with two kinds set
@@ -3812,6 +3969,11 @@ static int check_interval_tables(const tmh_engine* eng, uint32_t n_chains, int64
     if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
         return fail(TMH_E_INVAL, "%s are set: no traces in the same call (a caller with traces can sum them)", what);
     if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
+    if (eng->tables[TBL_STORAGE].set && kind != TBL_STORAGE)   // (kind: the first set one, so another table)
+        return fail(TMH_E_INVAL, "battery storage and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
+    if (kind == TBL_STORAGE && eng->storage.work_bytes < tmh_storage_work_bytes(n_chains, n_steps))
+        return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->storage.work_bytes,
+                    tmh_storage_work_bytes(n_chains, n_steps));
     if (has_intervals && has_registers)
         return fail(TMH_E_INVAL, "registers and intervals are both set: one of the two per engine (the registers table holds "
                                  "the intervals' columns)");
@@ -4142,7 +4304,7 @@ static int phase_expand(const StepCtx& c)
                     (unsigned long long)tv.ld);
     if (sites && out == OUT_TRACE3) out = OUT_ANY;   // per-chain sites: statistics only (C5), or any output
     // x = time blocks, y = chain blocks; LDS: the histogram (16-bit bin pairs or bins)
-    auto launch = [&](auto r, auto okind, auto st, const auto& view) {
+    auto launch = [&](auto r, auto okind, auto st, const auto& view, const StatsView& sv) {   // (sv: this launch's statistics)
         using R = decltype(r);
         constexpr int O = decltype(okind)::value;
         constexpr bool S = decltype(st)::value;
@@ -4160,9 +4322,29 @@ static int phase_expand(const StepCtx& c)
     with_real(f64, [&](auto r) {
         with_value<0, 1>(sites, [&](auto st) {
             constexpr bool F32 = sizeof(r) == 4, S = decltype(st)::value;
-            auto traces = [&](auto okind) { launch(r, okind, st, tv); };
-            auto ivl = [&](auto okind) { launch(r, okind, st, c.ivv); };
-            if (table != TBL_KINDS) {
+            auto traces = [&](auto okind) { launch(r, okind, st, tv, sv); };
+            auto ivl = [&](auto okind) { launch(r, okind, st, c.ivv, sv); };
+            if (table == TBL_STORAGE) {
+                // battery storage (fp64: tmh_set_storage), three launches in stream order, none waiting on
+                // another workgroup: the map pass (each (chain, block)'s composed SoC map, no statistics), the
+                // scan (each block's starting SoC, the window's end into soc), the replay pass (the table, with
+                // the statistics when given).  Each timed on its own beside TMH_K_EXPAND.
+                if constexpr (!F32) {
+                    const tmh_storage& sb = eng->storage;
+                    const StorageView stv{c.ivv, reinterpret_cast<long long*>(sb.work), (long long)sb.capacity,
+                                          (int)sb.p_charge, (int)sb.p_discharge};
+                    hipEvent_t t = eng->mark(c.s);
+                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_MAP>{}, st, stv, StatsView{});
+                    eng->close(TMH_K_STORAGE_MAP, t, c.s);
+                    t = eng->mark(c.s);
+                    hipLaunchKernelGGL(storage_scan_kernel, dim3(c.cb()), dim3(256), 0, c.s, stv.work,
+                                       reinterpret_cast<long long*>(sb.soc), eng->kp.ids, c.n_chains, c.sg.nblk);
+                    eng->close(TMH_K_STORAGE_SCAN, t, c.s);
+                    t = eng->mark(c.s);
+                    launch(r, std::integral_constant<int, OUT_STORAGE>{}, st, stv, sv);
+                    eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
+                }
+            } else if (table != TBL_KINDS) {
                 // an interval table (+ statistics when given, binned as the statistics-only kernel of the
                 // same histogram spec bins them: no per-second run-time choice)
                 with_value<OUT_INTERVALS, OUT_REGISTERS, OUT_DEMAND>(out, [&](auto o) {
@@ -4172,7 +4354,7 @@ static int phase_expand(const StepCtx& c)
                 });
             } else if (c.series()) {
                 // the fleet series (+ statistics when given; the histogram bins as hist_bin_rt decides)
-                launch(r, std::integral_constant<int, OUT_SERIES | OUT_BRT>{}, st, c.sev);
+                launch(r, std::integral_constant<int, OUT_SERIES | OUT_BRT>{}, st, c.sev, sv);
             } else if (b64) {
                 if constexpr (F32) with_value<OUT_STATS | OUT_B64, OUT_ANY | OUT_B64>(out | OUT_B64, traces);
             } else if constexpr (S) with_value<OUT_STATS, OUT_ANY>(out, traces);

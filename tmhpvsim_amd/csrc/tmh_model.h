@@ -1532,16 +1532,19 @@ enum OutKind : int {
     OUT_INTERVALS = 4,   // interval metering (per-chain integer sums per metering interval), statistics if given, no trace
     OUT_REGISTERS = 5,   // import / export registers (the intervals' columns + import and export per interval), likewise
     OUT_DEMAND = 6,      // demand registers (the registers' columns + the peak import and peak export keys), likewise
+    OUT_STORAGE = 7,     // battery storage (fp64): the replay pass -- the intervals' columns + the battery's five, likewise
     // flags on OUT_ANY / OUT_STATS (fp32 kernels): OUT_B64 bins in fp64 (a histogram spec whose
     // fp32 bin position is not accurate enough, StatsView::bin64); OUT_BRT decides at run time
-    OUT_B64 = 8, OUT_BRT = 16
+    OUT_B64 = 8, OUT_BRT = 16,
+    // flag on OUT_STORAGE: the map pass -- no output but each (chain, block)'s composed state-of-charge map
+    OUT_MAP = 32
 };
 constexpr int out_base(int out) { return out & 7; }
 // no trace: the statistics-only expansion's workgroup shape
 constexpr bool out_no_trace(int out)
 {
     return out_base(out) == OUT_STATS || out_base(out) == OUT_SERIES || out_base(out) == OUT_INTERVALS ||
-           out_base(out) == OUT_REGISTERS || out_base(out) == OUT_DEMAND;
+           out_base(out) == OUT_REGISTERS || out_base(out) == OUT_DEMAND || out_base(out) == OUT_STORAGE;
 }
 
 // The fleet series of a window (tmh_series): rows of 4 int64 per step, `sum` at the
@@ -1564,8 +1567,55 @@ struct IntervalsView {
 };
 constexpr int interval_cols(int out)
 {
-    return out_base(out) == OUT_DEMAND ? TMH_DEMAND_COLS : out_base(out) == OUT_REGISTERS ? TMH_REGISTERS_COLS : 4;
+    return out_base(out) == OUT_STORAGE  ? TMH_STORAGE_COLS
+           : out_base(out) == OUT_DEMAND ? TMH_DEMAND_COLS
+           : out_base(out) == OUT_REGISTERS ? TMH_REGISTERS_COLS
+                                            : 4;
 }
+// Battery storage (tmh_storage).  One ok second asks the battery for a = clamp(d, -Pd, Pc) with d = q(pv) -
+// q(meter) and moves the state of charge x to clamp(x + a, 0, C): a clamped addition.  Clamped additions
+// x -> min(max(x + a, lo), hi) (lo <= hi) are closed under composition, exactly on integers, and the
+// composition is associative: a block's seconds collapse into one SocMap whatever the state they start
+// from.  Plain C++ (constexpr: host and device alike).
+struct SocMap {
+    long long a, lo, hi;
+};
+// the identity's bounds: +-2^62, so adding any block's |a| <= 128 * 2^27 (or a window's) cannot overflow
+constexpr long long SOC_LO = LLONG_MIN / 2, SOC_HI = LLONG_MAX / 2;
+constexpr SocMap soc_identity() { return SocMap{0, SOC_LO, SOC_HI}; }
+constexpr long long soc_clamp(long long v, long long lo, long long hi)
+{
+    const long long m = v > lo ? v : lo;
+    return m < hi ? m : hi;
+}
+constexpr long long soc_apply(const SocMap& f, long long x) { return soc_clamp(x + f.a, f.lo, f.hi); }
+// f first, then g
+constexpr SocMap soc_compose(const SocMap& f, const SocMap& g)
+{
+    return SocMap{f.a + g.a, soc_clamp(f.lo + g.a, g.lo, g.hi), soc_clamp(f.hi + g.a, g.lo, g.hi)};
+}
+// what the battery is asked to take (+) or give (-) in a second with d = q(pv) - q(meter)
+constexpr int soc_ask(int d, int p_charge, int p_discharge)
+{
+    const int m = d > -p_discharge ? d : -p_discharge;
+    return m < p_charge ? m : p_charge;
+}
+// The SoC key of table column 8: the second's offset o in its interval (+ 1, so every key is positive)
+// above the state of charge after it (0 <= x < 2^40); the maximum key is the interval's last ok second's.
+constexpr int SOC_KEY_SHIFT = 40;
+constexpr unsigned long long soc_key(uint32_t o, long long x)
+{
+    return ((unsigned long long)(o + 1u) << SOC_KEY_SHIFT) | (unsigned long long)x;
+}
+// The storage kind's view: the table, the battery and the window's work buffer [block][3][n] (n: the
+// call's chains, lane-consecutive) -- the map pass writes each block's SocMap, storage_scan_kernel puts the
+// block's starting state of charge in the first slot, the replay pass reads it.
+struct StorageView {
+    IntervalsView iv;
+    long long* work;
+    long long cap;
+    int p_charge, p_discharge;
+};
 // The demand registers' packed key of a second (tmh_demand): the quantised power v (0 <= v < 2^27)
 // above the complement of the second's offset o in its interval, so the maximum key is the
 // largest power at its earliest second; > 0 for every second.

@@ -63,7 +63,21 @@ _TABLES = {
         run_excludes=(("_intervals", "_registers"), "the demand registers and interval metering or the import / export "
                                                     "registers are both enabled: one of them per sim"),
         no_trace="a demand run takes no traces (trace=()): take the peaks of the traces instead (demand.from_traces)"),
+    # battery storage (enable_storage: the battery's arguments beside the table's; fp64 sims only)
+    "storage": dict(
+        noun="storage tables", name="battery storage",
+        enable_excludes=tuple(
+            (attr, f"{what} is enabled: one table output per sim (battery storage runs alone)")
+            for attr, what in (("_series", "a fleet series"), ("_intervals", "interval metering"),
+                               ("_registers", "the import / export registers"), ("_demand", "the demand registers"))),
+        run_excludes=(("_intervals", "_registers", "_demand"), "battery storage and another interval table are both "
+                                                               "enabled: one of them per sim"),
+        no_trace="a storage run takes no traces (trace=()): run the battery over the traces instead (storage.from_traces)"),
 }
+for _kind, _t in _TABLES.items():   # no table beside battery storage, whichever was enabled first
+    if _kind != "storage":
+        _t["enable_excludes"] += (("_storage", "battery storage is enabled: one table output per sim "
+                                               "(battery storage runs alone)"),)
 
 
 class BatchedSim:
@@ -163,6 +177,8 @@ class BatchedSim:
         for kind in _TABLES:   # intervals_raw, registers_raw, demand_raw: int64 [n_intervals, 4 / 6 / 8, n] (enable_<kind>)
             setattr(self, kind + "_raw", None)
             setattr(self, "_" + kind, None)
+        self.soc = None           # int64 [n]: the batteries' state of charge (enable_storage)
+        self._storage_args = self._storage_work = self._storage_desc = None
         self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
@@ -253,7 +269,10 @@ class BatchedSim:
     def _enable_table(self, kind, n_steps, interval_s, step0, buffer):
         """enable_intervals, enable_registers and enable_demand (_TABLES[kind])."""
         torch = _torch()
-        setter = getattr(self.L, "tmh_set_" + kind)
+        if kind == "storage":   # (its descriptor holds the table's: _set_storage)
+            setter = lambda eng, st: self._set_storage(st._obj if st is not None else None)
+        else:
+            setter = getattr(self.L, "tmh_set_" + kind)
         if n_steps is None:
             _lib.check(setter(self._eng, None))
             setattr(self, kind + "_raw", None)
@@ -349,6 +368,80 @@ class BatchedSim:
         load_factor, [n_intervals, n] each."""
         return self._table_watts("demand")
 
+    # ------------------------------------------------------------------ battery storage
+    def enable_storage(self, n_steps, interval_s=900, *, capacity_wh=None, charge_w=None, discharge_w=None, soc0_wh=0.0,
+                       step0=None, buffer=None, soc=None):
+        """Put a battery behind every chain's meter (tmhpvsim_amd.storage: greedy self-consumption,
+        lossless, integers in the series' units) and keep, per metering interval of interval_s seconds
+        over steps [step0, step0 + n_steps), the interval table's four columns, the import and export
+        with the battery, what the battery took and gave, and the state of charge at the interval's end.
+        capacity_wh, charge_w and discharge_w are the battery's capacity and power limits (uniform over
+        the batch, quantised by storage.quantize_params); every chain starts at soc0_wh.  Returns the raw
+        int64 tensor [n_intervals, 9, n]; `sim.soc` is the int64 state of charge [n], advanced by every
+        window.  buffer: as enable_registers (strides (9 ld, ld, 1)); soc: an int64 device tensor [n] to
+        carry instead of a new one (a slice of a larger one: several batches beside each other).  fp64
+        sims only: an fp32 engine replaces guard-band seconds after the expansion, and the state of
+        charge depends on every earlier second.  Runs with storage take no traces, no fleet series and no
+        other table; compaction is allowed.  n_steps=None switches the output off."""
+        torch = _torch()
+        if n_steps is None:
+            self.soc = self._storage_work = self._storage_desc = None
+            return self._enable_table("storage", None, interval_s, step0, buffer)
+        if self.precision != _lib.TMH_FP64:
+            raise ValueError("battery storage needs precision='fp64': an fp32 engine replaces its guard-band seconds "
+                             "after the expansion, and the state of charge depends on every earlier second")
+        if capacity_wh is None or charge_w is None or discharge_w is None:
+            raise ValueError("enable_storage: capacity_wh, charge_w and discharge_w are required")
+        from . import storage
+        cap, pc, pd, x0 = storage.quantize_params(capacity_wh, charge_w, discharge_w, soc0_wh)
+        if int(interval_s) > storage.MAX_INTERVAL_S:
+            raise ValueError(f"enable_storage: interval_s <= {storage.MAX_INTERVAL_S}")
+        if soc is None:
+            soc = torch.full((self.n,), x0, dtype=torch.int64, device=self.device)
+        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (self.n,)
+              or (self.n > 1 and soc.stride(0) != 1)):
+            raise ValueError(f"storage soc must be a contiguous int64 [{self.n}] tensor on {self.device}")
+        kept = self._storage_args
+        self._storage_args = (soc, cap, pc, pd)
+        try:
+            raw = self._enable_table("storage", n_steps, interval_s, step0, buffer)
+        except Exception:   # (refused: what was enabled before stays as it was)
+            self._storage_args = kept
+            raise
+        self.soc = soc
+        return raw
+
+    def _set_storage(self, table):
+        """tmh_set_storage with the table descriptor `table` (or None) and the battery's fields; the work
+        buffer is sized for the default window of a run and grown by run() when a window needs more."""
+        if table is None:
+            return self.L.tmh_set_storage(self._eng, None)
+        torch = _torch()
+        soc, cap, pc, pd = self._storage_args
+        if self._storage_work is None:
+            nb = self.L.tmh_storage_work_bytes(self.n, min(int(table.n_steps), 86400))
+            self._storage_work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
+        work = self._storage_work
+        st = _lib.Storage(table, soc.data_ptr(), work.data_ptr(), work.numel(), cap, pc, pd)
+        rc = self.L.tmh_set_storage(self._eng, C.byref(st))
+        if rc == 0:
+            self._storage_desc = st
+        return rc
+
+    def _storage_window(self, win):
+        """run(): the work buffer holds a window of `win` steps (a larger one replaces it)."""
+        need = self.L.tmh_storage_work_bytes(self.n, int(win))
+        if self._storage_work.numel() < need:
+            _torch().cuda.synchronize(self.device)   # (launches of earlier runs may still read the old one)
+            self._storage_work = _torch().empty(need, dtype=torch_uint8(), device=self.device)
+            _lib.check(self._set_storage(self._storage))
+
+    def storage(self):
+        """The storage table in watts and watt-hours (storage.to_watts of storage_raw): the intervals'
+        keys plus energy_wh_import, energy_wh_export, energy_wh_charge, energy_wh_discharge, soc_wh and
+        the self_consumption and self_sufficiency ratios, [n_intervals, n] each."""
+        return self._table_watts("storage")
+
     def guard_records(self):
         """Tests: the fp32 guard-band records (chain, 128-s block) of the last window that run()
         issued as a single tmh_run (tmh_test_guard_records; synchronises the device)."""
@@ -421,6 +514,8 @@ class BatchedSim:
         res = out if out is not None else self._alloc(n_steps, trace)
         st = self._stats_struct()
         win = max(1, min(int(window), n_steps))
+        if self._storage is not None:
+            self._storage_window(win)
         if compact and n_steps > win:
             with torch.cuda.device(self.device):
                 self._run_compacted(n_steps, win, st)
