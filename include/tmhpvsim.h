@@ -32,7 +32,9 @@
  *    registers (tmh_demand: the registers' columns plus the peak import and the peak
  *    feed-in of each interval and the second of each) or battery storage (tmh_storage,
  *    fp64 engines: the intervals' columns plus what the meter reads with a battery behind
- *    it, what the battery took and gave and its state of charge at each interval's end).
+ *    it, what the battery took and gave and its state of charge at each interval's end) or
+ *    the battery kind (tmh_battery: the same with charge and discharge efficiency, a standby
+ *    drain, a loss column and per-chain battery parameters).
  *  - `stream` is a hipStream_t (NULL = default stream); all work is enqueued
  *    asynchronously on it.  One engine per device; not re-entrant per engine.
  */
@@ -269,6 +271,58 @@ typedef struct tmh_storage {
     int64_t capacity, p_charge, p_discharge;
 } tmh_storage;
 
+/* The battery kind: tmh_storage's battery with charge and discharge efficiency, a standby
+ * drain and per-chain parameters.  tmh_storage stays as it is (lossless, uniform); this kind
+ * reproduces it bit for bit in columns 0-8 and soc when every chain has ec = ed = 2^16 and
+ * sigma = 0, and its column 9 is then 0.  Integers in the series' units as above.
+ * params: device int64 [6][ld] of the caller (ld: table.ld), row r of chain i at
+ * params[r*ld + i], i as soc's (ids[slot] under tmh_set_chain_ids); a column slice of a
+ * larger [6][N] tensor is a valid argument.  Read by every window, never written:
+ *   row 0  capacity C                                0 <= C < 2^40
+ *   row 1  charge limit Pc at the meter side         0 .. 2^27
+ *   row 2  discharge limit Pd at the meter side      0 .. 2^27
+ *   row 3  charge efficiency ec in 2^-16             2^15 .. 2^16
+ *   row 4  discharge efficiency ed in 2^-16          2^15 .. 2^16
+ *   row 5  standby drain sigma per ok second         0 .. 2^27
+ * No address depends on a parameter; a value outside its range is clamped into it when a lane
+ * loads it, so the result is defined without the host reading the tensor.  Two multipliers are
+ * derived: kc = ceil(2^32 / ec), kd = ceil(2^32 / ed) (= floor((2^32 - 1) / e) + 1; in
+ * [2^16, 2^17]).  The SoC x is clamped into [0, C] when a window reads it; at a window's end
+ * it lies there, so splitting into windows changes nothing.  For an ok second with
+ * d = q(pv) - q(meter) and the SoC x before it:
+ *   a  = clamp(d, -Pd, Pc)                                   asked at the meter side
+ *   s  = a >= 0 ?  (a*ec) >> 16  :  -((-a*kd + 65535) >> 16) stored (floor) / drained (ceil)
+ *   x1 = clamp(x + s, 0, C)          g = x1 - x
+ *   b  = a                                    if g == s      (not clipped)
+ *      =  min( a, (g*kc + 65535) >> 16)       if g > 0       (fills during this second)
+ *      = -min(-a, (-g*ed) >> 16)              if g < 0       (runs empty during this second)
+ *      = 0                                    if g == 0
+ *   x' = max(x1 - sigma, 0)
+ *   import_b = max(b - d, 0)   export_b = max(d - b, 0)   loss = b - (x' - x)
+ * A second that is not ok leaves x unchanged and adds nothing.  All products stay below 2^60;
+ * loss >= 0, |b| <= |a| and b has a's sign in every second.  The second's map of x is the
+ * clamped addition {s, 0, C} followed by {-sigma, 0, C}: tmh_storage's algebra and its three
+ * launches carry over.
+ * table.sum: device int64 [n_intervals][TMH_BATTERY_COLS][ld], zero-initialised by the caller.
+ * Over the ok seconds of interval k:
+ *   [0..3] tmh_intervals' columns exactly            (added)
+ *   [4] sum of import_b    [5] sum of export_b       (added)
+ *   [6] sum of max(b, 0)   [7] sum of max(-b, 0)     (added: charged, discharged, meter side)
+ *   [8] the maximum of ((o + 1) << 40) | x'          (tmh_storage's key)
+ *   [9] sum of loss                                  (added)
+ * For every cell [4] - [5] == [1] - [0] + [6] - [7], columns 4-7 and 9 are >= 0, and
+ * [6] - [7] - [9] is the interval's SoC change.  The bits do not depend on windows, batches,
+ * shards or compaction and equal a sequential loop over the traces.  fp64 engines only, as
+ * tmh_storage.  soc, work and work_bytes: tmh_storage's (tmh_storage_work_bytes). */
+#define TMH_BATTERY_COLS 10
+typedef struct tmh_battery {
+    tmh_intervals table;      /* sum is [n_intervals][10][ld] */
+    int64_t* soc;             /* device [ld]: per chain index, read (clamped into [0, C]) at a window's start, written at its end */
+    void* work;               /* device scratch */
+    size_t work_bytes;        /* >= tmh_storage_work_bytes(n_chains, n_steps) of the largest window */
+    const int64_t* params;    /* device [6][ld], ld = table.ld */
+} tmh_battery;
+
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
 /* TMH_SERIES_FRAC_BITS and TMH_SERIES_MAX_W as the library was built with them */
@@ -453,6 +507,16 @@ int tmh_set_demand(struct tmh_engine* eng, const tmh_demand* dm);
  * and tmh_engine_scratch_bytes do not change: the caller owns every buffer. */
 size_t tmh_storage_work_bytes(uint32_t n_chains, uint32_t n_steps);
 int tmh_set_storage(struct tmh_engine* eng, const tmh_storage* st);
+/* The battery kind (tmh_battery above): as tmh_set_storage, with the parameters in memory.
+ * Every later expansion clamps bt->soc into [0, C], advances it over its window and adds
+ * the window to bt->table.sum, in tmh_set_storage's three launches (timed by the same
+ * TMH_K_STORAGE_* slots); NULL switches it off.  Refused here (TMH_E_INVAL, the messages name
+ * "battery"): everything tmh_set_storage refuses of the table, soc, work and the engine; a
+ * NULL or misaligned (8 bytes) params.  Refused at a step / expansion call or a walk of that
+ * window, before any launch: everything tmh_set_storage's step refuses; battery storage
+ * (tmh_set_storage) set too, in either order.  The parameters' values are not read on the
+ * host: the kernels clamp them. */
+int tmh_set_battery(struct tmh_engine* eng, const tmh_battery* bt);
 /* Tests only: the fp32 guard-band records (chain, block) the last expansion on
  * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
  * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
@@ -547,7 +611,7 @@ int tmh_expand_part(struct tmh_engine* eng, void* state, uint64_t chain0, uint32
  * milliseconds and launch count of one kernel since the last read, then resets
  * it.  kernel: TMH_K_EXPAND (P2 trace/stats expansion), TMH_K_SEGMENTS (P1
  * segment walk), TMH_K_CANDIDATES (P1's candidate table), TMH_K_STEP (the
- * whole tmh_step); with battery storage set, TMH_K_EXPAND spans the kind's three launches
+ * whole tmh_step); with battery storage or the battery kind set, TMH_K_EXPAND spans the kind's three launches
  * and TMH_K_STORAGE_MAP, TMH_K_STORAGE_SCAN and TMH_K_STORAGE_REPLAY time each of them. */
 enum { TMH_K_EXPAND = 0, TMH_K_SEGMENTS = 1, TMH_K_CANDIDATES = 2, TMH_K_STEP = 3, TMH_K_STORAGE_MAP = 4,
        TMH_K_STORAGE_SCAN = 5, TMH_K_STORAGE_REPLAY = 6, TMH_K_COUNT = 7 };
@@ -562,7 +626,8 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * TMH_OUT_INTERVALS (interval metering, with or without statistics),
  * TMH_OUT_REGISTERS (import / export registers, with or without statistics),
  * TMH_OUT_DEMAND (demand registers, with or without statistics), TMH_OUT_STORAGE (battery
- * storage: the replay pass, the last of the kind's three launches, with or without statistics), plus
+ * storage: the replay pass, the last of the kind's three launches, with or without statistics),
+ * TMH_OUT_BATTERY (the battery kind, likewise), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
@@ -573,6 +638,7 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
 #define TMH_OUT_REGISTERS 5
 #define TMH_OUT_DEMAND 6
 #define TMH_OUT_STORAGE 7
+#define TMH_OUT_BATTERY 8
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

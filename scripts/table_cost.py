@@ -3,10 +3,11 @@
 kernel) of the statistics-only expansion and of the expansions with a table, same chains,
 same window, same process, the runs alternating.
 
-    python scripts/table_cost.py --kind intervals|registers|demand|storage [--chains 65536] [--steps 86400]
+    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery [--chains 65536] [--steps 86400]
                                  [--interval 900] [--rounds 5] [--precision fp32]
                                  [--start "2019-09-05 00:00:00"] [--out FILE.json]
                                  [--modules 1 --capacity-wh 5000 --charge-w 2500 --discharge-w 2500]
+                                 [--charge-eff 0.95 --discharge-eff 0.95 --standby-w 2]
 
 The runs of a kind, each with the same statistics beside its table:
   intervals: OUT_STATS and OUT_INTERVALS;
@@ -20,6 +21,9 @@ The runs of a kind, each with the same statistics beside its table:
              in every cell; its three launches (map pass, scan, replay) are timed separately as well
              (TMH_K_STORAGE_*), inside the TMH_K_EXPAND span.  --modules k scales the PV system (k modules) so
              that the battery of --capacity-wh / --charge-w / --discharge-w charges and discharges.
+  battery:   OUT_STATS, OUT_STORAGE and OUT_BATTERY on an fp64 engine -- storage's setting with --charge-eff,
+             --discharge-eff and --standby-w; the battery table's identities, a loss, and battery / storage for
+             the whole expansion and for each of the three launches (the same TMH_K_STORAGE_* slots time both).
 The script checks each run's variant, these identities (on the warm-up round's tables), that
 the statistics of all runs agree bit for bit and that every table's ok seconds equal the
 histogram's count.  One warm-up round, then --rounds timed ones.  Prints one JSON line: the
@@ -42,6 +46,7 @@ RUNS = {
     "registers": (("stats_only", None), ("intervals", "intervals"), ("registers", "registers")),
     "demand": (("stats_only", None), ("registers", "registers"), ("demand", "demand")),
     "storage": (("stats_only", None), ("registers", "registers"), ("storage", "storage")),
+    "battery": (("stats_only", None), ("storage", "storage"), ("battery", "battery")),
 }
 
 
@@ -67,6 +72,13 @@ def check_tables(kind, tables, interval_s):
         assert torch.equal(st[:, 4] - st[:, 5], st[:, 1] - st[:, 0] + st[:, 6] - st[:, 7])
         assert torch.equal(st[:, 8] != 0, st[:, 2] > 0) and int((st[:, 8] >> 40).max()) <= interval_s
         return int((st[:, 5] > 0).sum())
+    if kind == "battery":
+        bt, st = tables["battery"], tables["storage"]
+        assert torch.equal(bt[:, :4], st[:, :4]) and bool((bt[:, 4:8] >= 0).all()) and bool((bt[:, 9] >= 0).all())
+        assert torch.equal(bt[:, 4] - bt[:, 5], bt[:, 1] - bt[:, 0] + bt[:, 6] - bt[:, 7])
+        assert torch.equal(bt[:, 8] != 0, bt[:, 2] > 0) and int((bt[:, 8] >> 40).max()) <= interval_s
+        assert int(bt[:, 9].sum()) > 0 and int(bt[:, 6].sum()) > 0 and int(bt[:, 7].sum()) > 0
+        return int((bt[:, 5] > 0).sum())
     return None
 
 
@@ -84,8 +96,11 @@ def main():
     ap.add_argument("--capacity-wh", type=float, default=5000.0)
     ap.add_argument("--charge-w", type=float, default=2500.0)
     ap.add_argument("--discharge-w", type=float, default=2500.0)
+    ap.add_argument("--charge-eff", type=float, default=0.95)
+    ap.add_argument("--discharge-eff", type=float, default=0.95)
+    ap.add_argument("--standby-w", type=float, default=2.0)
     a = ap.parse_args()
-    if a.kind == "storage":
+    if a.kind in ("storage", "battery"):
         a.precision = "fp64"   # (the kind's engines)
     import torch
     from tmhpvsim_amd import _lib
@@ -94,9 +109,10 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("table_cost.py needs a GPU")
     out_of = {None: _lib.OUT_STATS, "intervals": _lib.OUT_INTERVALS, "registers": _lib.OUT_REGISTERS,
-              "demand": _lib.OUT_DEMAND, "storage": _lib.OUT_STORAGE}
+              "demand": _lib.OUT_DEMAND, "storage": _lib.OUT_STORAGE, "battery": _lib.OUT_BATTERY}
     parts = (("map", _lib.K_STORAGE_MAP), ("scan", _lib.K_STORAGE_SCAN), ("replay", _lib.K_STORAGE_REPLAY))
-    part_ms = {name: [] for name, _ in parts}
+    part_ms = {name: [] for name, _ in parts}           # the kind's own launches
+    below_ms = {name: [] for name, _ in parts}          # --kind battery: storage's, the run below it
     mp = ModelParams()
     if a.modules != 1:   # k modules on a k-fold inverter
         import dataclasses
@@ -107,6 +123,8 @@ def main():
         inv["C0"] /= a.modules
         mp = dataclasses.replace(mp, module=mod, inverter=inv)
     battery = dict(capacity_wh=a.capacity_wh, charge_w=a.charge_w, discharge_w=a.discharge_w, soc0_wh=a.capacity_wh / 2)
+    lossy = dict(battery, charge_eff=a.charge_eff, discharge_eff=a.discharge_eff, standby_w=a.standby_w)
+    enable_kw = {"storage": battery, "battery": lossy}
     runs = RUNS[a.kind]
     labels = [label for label, _ in runs]
 
@@ -114,18 +132,18 @@ def main():
         sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=mp, precision=a.precision,
                          device="cuda:0", horizon=a.steps)
         sim.enable_stats()
-        raw = getattr(sim, "enable_" + table)(a.steps, a.interval, **(battery if table == "storage" else {})) if table else None
+        raw = getattr(sim, "enable_" + table)(a.steps, a.interval, **enable_kw.get(table, {})) if table else None
         _lib.check(sim.L.tmh_profile_enable(sim._eng, 1))
         sim.run(a.steps, trace=(), window=a.steps)
         torch.cuda.synchronize()
         ms, launches = _lib.profile_read(sim._eng, _lib.K_EXPAND)
         want = out_of[table] | (_lib.OUT_FP64 if a.precision == "fp64" else 0)
         assert launches == 1 and sim.L.tmh_engine_last_expand(sim._eng) == want, (launches, want)
-        if table == "storage":   # its three launches, once each, inside the span read above
+        if table in ("storage", "battery"):   # its three launches, once each, inside the span read above
             for name, kk in parts:
                 pms, pn = _lib.profile_read(sim._eng, kk)
                 assert pn == 1
-                part_ms[name].append(pms)
+                (part_ms if table == a.kind else below_ms)[name].append(pms)
         if raw is not None:
             assert int(raw[:, 2].sum()) == int(sim.hist.sum()) > 0
         return ms, sim.hist.clone(), sim.chain_acc.clone(), raw
@@ -133,7 +151,7 @@ def main():
     tables = {table: one(table)[3] for _, table in runs}   # warm-up: code objects, allocator
     export_cells = check_tables(a.kind, tables, a.interval)
     del tables
-    for v in part_ms.values():
+    for v in list(part_ms.values()) + list(below_ms.values()):
         v.clear()   # (the warm-up round's)
     t = {label: [] for label in labels}
     ref = None
@@ -165,6 +183,15 @@ def main():
                    **{f"storage_{k}_median_ms": v for k, v in pmed.items()},
                    scan_share=pmed["scan"] / med["storage"], ratio_replay_registers=pmed["replay"] / med["registers"],
                    ratio_map_registers=pmed["map"] / med["registers"], scan_over_replay=pmed["scan"] / pmed["replay"])
+    if a.kind == "battery":   # battery / storage: the whole expansion and each launch, beside the spread of storage's own rounds
+        pmed = {name: statistics.median(v) for name, v in part_ms.items()}
+        smed = {name: statistics.median(v) for name, v in below_ms.items()}
+        res.update(modules=a.modules, battery=lossy,
+                   **{f"battery_{k}_ms": v for k, v in part_ms.items()}, **{f"storage_{k}_ms": v for k, v in below_ms.items()},
+                   **{f"battery_{k}_median_ms": v for k, v in pmed.items()},
+                   **{f"storage_{k}_median_ms": v for k, v in smed.items()},
+                   **{f"ratio_{k}_battery_storage": pmed[k] / smed[k] for k in pmed},
+                   storage_spread=max(t["storage"]) / min(t["storage"]))
     res["build_stamp"] = _lib.loaded_stamp()
     line = json.dumps(res)
     print(line)

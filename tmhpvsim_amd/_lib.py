@@ -84,6 +84,13 @@ class Storage(C.Structure):
                 ("capacity", C.c_int64), ("p_charge", C.c_int64), ("p_discharge", C.c_int64)]
 
 
+class Battery(C.Structure):
+    """tmh_battery: the battery kind's table (tmh_intervals with 10 columns), the per-chain state of charge, the
+    window's work buffer and the per-chain parameters int64 [6][ld] (tmh_set_battery)."""
+    _fields_ = [("table", Intervals), ("soc", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t),
+                ("params", C.c_void_p)]
+
+
 EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_bytes", "tmh_state_offsets", "tmh_plan_bytes",
            "tmh_scratch_bytes", "tmh_engine_scratch_bytes", "tmh_workspace_bytes", "tmh_engine_create", "tmh_engine_destroy", "tmh_engine_path",
            "tmh_init", "tmh_run", "tmh_plan", "tmh_step", "tmh_probe", "tmh_profile_enable", "tmh_profile_read",
@@ -92,7 +99,7 @@ EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_by
            "tmh_set_walk_chains_per_row", "tmh_set_walk_lanes", "tmh_set_chain_ids", "tmh_live_chains", "tmh_state_move",
            "tmh_stream_create_cus", "tmh_stream_destroy", "tmh_set_walk_order", "tmh_engine_last_expand",
            "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals",
-           "tmh_set_registers", "tmh_set_demand", "tmh_set_storage", "tmh_storage_work_bytes"]
+           "tmh_set_registers", "tmh_set_demand", "tmh_set_storage", "tmh_storage_work_bytes", "tmh_set_battery"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
 K_STORAGE_MAP, K_STORAGE_SCAN, K_STORAGE_REPLAY = 4, 5, 6   # battery storage's three launches (inside K_EXPAND)
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
@@ -103,6 +110,7 @@ OUT_INTERVALS = 4
 OUT_REGISTERS = 5
 OUT_DEMAND = 6
 OUT_STORAGE = 7
+OUT_BATTERY = 8
 
 _lib = None
 
@@ -202,6 +210,8 @@ def load():
     L.tmh_set_demand.restype = C.c_int
     L.tmh_set_storage.argtypes = [p, C.POINTER(Storage)]
     L.tmh_set_storage.restype = C.c_int
+    L.tmh_set_battery.argtypes = [p, C.POINTER(Battery)]
+    L.tmh_set_battery.restype = C.c_int
     L.tmh_storage_work_bytes.argtypes = [u32, u32]
     L.tmh_storage_work_bytes.restype = sz
     L.tmh_series_frac_bits.restype = C.c_int

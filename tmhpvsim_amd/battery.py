@@ -1,0 +1,186 @@
+"""The battery kind: battery storage with losses and per-chain batteries (tmh_battery).
+
+`storage` puts a lossless battery of one size behind every meter.  Here each chain has its
+own battery -- capacity C, charge and discharge limits Pc and Pd at the meter side, charge
+and discharge efficiency ec and ed in units of 2^-16, and a standby drain sigma per ok
+second -- as the six rows of an int64 array params [6, n] (`quantize_params`).  Everything
+is an integer in the fleet series' units: powers in 2^-FRAC_BITS W, energies and the state
+of charge (SoC) in 2^-FRAC_BITS W s.  With kc = ceil(2^32 / ec), kd = ceil(2^32 / ed), an ok
+second with d = q(pv) - q(meter) and the SoC x before it (clamped into [0, C] when a window
+reads it):
+
+    a  = clamp(d, -Pd, Pc)                                   asked at the meter side
+    s  = a >= 0 ?  (a ec) >> 16  :  -((-a kd + 65535) >> 16) stored (floor) / drained (ceil)
+    x1 = clamp(x + s, 0, C)          g = x1 - x
+    b  = a                                   if g == s       (not clipped)
+       =  min( a, (g kc + 65535) >> 16)      if g > 0        (fills during this second)
+       = -min(-a, (-g ed) >> 16)             if g < 0        (runs empty during this second)
+       = 0                                   if g == 0
+    x' = max(x1 - sigma, 0)
+    import_b = max(b - d, 0)    export_b = max(d - b, 0)    loss = b - (x' - x)
+
+A second that is not ok leaves x unchanged and adds nothing.  The engine fills an int64 tensor
+[n_intervals, 10, n] (BatchedSim.enable_battery, tmh_set_battery; fp64 engines only):
+
+    [k, 0:4, i] the interval table's columns (pv, meter, n_ok, covered), added
+    [k, 4, i]   sum of import_b          [k, 5, i] sum of export_b
+    [k, 6, i]   sum of max(b, 0)         [k, 7, i] sum of max(-b, 0)   (charged, discharged: meter side)
+    [k, 8, i]   storage's SoC key: the maximum of ((o + 1) << 40) | x'
+    [k, 9, i]   sum of loss
+
+In every cell [4] - [5] == [1] - [0] + [6] - [7], columns 4-7 and 9 are >= 0 and [6] - [7] - [9]
+is the interval's SoC change.  With ec = ed = 2^16 and sigma = 0 columns 0-8 and the SoC are
+`storage`'s bit for bit and column 9 is 0.  s does not depend on x, so the second is still a
+clamped addition (followed by the drain's): `second_maps` gives the per-second triples that
+storage.compose / storage.apply fold, as the engine's map pass and scan do.  `from_traces` is the
+contract as a plain loop over the seconds.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import intervals, storage
+from .intervals import FRAC_BITS, MAX_W, n_intervals, quantize   # the series' units, as the loaded library has them
+from .storage import (HI, KEY_SHIFT, LO, MAX_CAPACITY, MAX_INTERVAL_S, MAX_POWER, apply, compose,   # noqa: F401
+                      unpack_soc)
+
+COLUMNS = storage.COLUMNS + ("loss",)
+PARAMS = ("capacity", "p_charge", "p_discharge", "eff_charge", "eff_discharge", "standby")   # the rows of params
+EFF_ONE, EFF_MIN = 1 << 16, 1 << 15
+# each row's inclusive range (tmh_battery)
+RANGES = ((0, MAX_CAPACITY - 1), (0, MAX_POWER), (0, MAX_POWER), (EFF_MIN, EFF_ONE), (EFF_MIN, EFF_ONE), (0, MAX_POWER))
+
+
+def check_params(params):
+    """params as an int64 [6, n] array, every row inside its range (ValueError otherwise)."""
+    params = np.asarray(params.cpu() if hasattr(params, "cpu") else params)
+    if params.ndim != 2 or params.shape[0] != len(PARAMS) or params.dtype != np.int64:
+        raise ValueError("battery params must be an int64 [6, n] array")
+    for name, row, (lo, hi) in zip(PARAMS, params, RANGES):
+        if row.size and (int(row.min()) < lo or int(row.max()) > hi):
+            raise ValueError(f"battery {name} outside [{lo}, {hi}]: [{int(row.min())}, {int(row.max())}]")
+    return params
+
+
+def quantize_params(capacity_wh, charge_w, discharge_w, charge_eff=1.0, discharge_eff=1.0, standby_w=0.0, n=None):
+    """The int64 [6, n] parameters of batteries given in Wh, W and efficiencies as floats in [0.5, 1], each
+    a scalar or [n] (n: the longest argument's length when not given): watt-hours times 3600 * 2^FRAC_BITS,
+    watts times 2^FRAC_BITS, efficiencies times 2^16, each rounded half to even.  Raises ValueError on
+    anything outside tmh_battery's ranges (NaN included)."""
+    e, p = 3600.0 * (1 << FRAC_BITS), float(1 << FRAC_BITS)
+    args = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in
+            (capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w)]
+    if any(a.ndim != 1 for a in args):
+        raise ValueError("battery quantities are scalars or [n] arrays")
+    if n is None:
+        n = max(a.shape[0] for a in args)
+    out = np.empty((len(PARAMS), int(n)), dtype=np.int64)
+    for r, (name, a, scale, (lo, hi)) in enumerate(zip(PARAMS, args, (e, p, p, float(EFF_ONE), float(EFF_ONE), p), RANGES)):
+        if a.shape[0] not in (1, n):
+            raise ValueError(f"battery {name}: {a.shape[0]} values for {n} chains")
+        q = np.rint(a * scale)
+        if not bool(((q >= lo) & (q <= hi)).all()):   # (NaN fails both)
+            raise ValueError(f"battery {name} {a[~((q >= lo) & (q <= hi))][0]!r} outside [{lo / scale:.6g}, {hi / scale:.6g}]")
+        out[r] = q.astype(np.int64)
+    return out
+
+
+def quantize_soc(soc0_wh, params):
+    """The starting SoC [n] of batteries `params` from watt-hours (a scalar or [n]); ValueError outside [0, C]."""
+    n = params.shape[1]
+    x0 = np.rint(np.broadcast_to(np.asarray(soc0_wh, dtype=np.float64), (n,)) * (3600.0 * (1 << FRAC_BITS)))
+    if not bool(((x0 >= 0) & (x0 <= params[0])).all()):
+        raise ValueError("battery soc0 outside [0, capacity]")
+    return x0.astype(np.int64)
+
+
+def _recip(e):
+    return ((1 << 32) - 1) // e + 1   # ceil(2^32 / e)
+
+
+def _stored(a, ec, kd):
+    """s of the ask a: what it stores (floor) or drains (ceil)."""
+    return np.where(a >= 0, (a * ec) >> 16, -((-a * kd + 65535) >> 16))
+
+
+def _ok_d(pv, meter, covered):
+    ok = ~(np.isnan(pv) | np.isnan(meter) | (covered == 255))
+    return ok, np.where(ok, quantize(pv) - quantize(meter), 0).astype(np.int64)
+
+
+def second_maps(pv, meter, covered, *, params):
+    """The per-second triples of traces [n_steps, n] with the batteries params [6, n]: the clamped
+    addition (s, 0, C) composed with the standby drain's (-sigma, 0, C) for an ok second, the identity
+    otherwise; int64 arrays [n_steps, n] each (storage.compose, storage.apply)."""
+    pv, meter, covered = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (pv, meter, covered))
+    cap, pc, pd, ec, ed, sb = check_params(params)
+    ok, d = _ok_d(pv, meter, covered)
+    s = _stored(np.clip(d, -pd, pc), ec, _recip(ed))
+    a, lo, hi = compose((s, 0, np.broadcast_to(cap, s.shape)), (-sb, 0, cap))
+    return np.where(ok, a, 0), np.where(ok, lo, LO).astype(np.int64), np.where(ok, hi, HI).astype(np.int64)
+
+
+def from_traces(pv, meter, covered, interval_s, *, params, soc0, origin=0):
+    """The battery table of time-major traces [n_steps, n_chains] and the SoC after them: (int64
+    [n_intervals, 10, n_chains], int64 [n_chains]).  A plain loop over the seconds, vectorised over the
+    chains.  params: int64 [6, n_chains] inside their ranges; soc0: the SoC before the first second, a
+    scalar or [n_chains], clamped into [0, C]; ok seconds, interval_s and origin as intervals.from_traces."""
+    pv, meter, covered = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (pv, meter, covered))
+    base = intervals.from_traces(pv, meter, covered, interval_s, origin=origin)      # (checks the arguments)
+    interval_s, origin = int(interval_s), int(origin)
+    if interval_s > MAX_INTERVAL_S:
+        raise ValueError("interval_s <= 2^23 - 1")
+    n_steps, n = pv.shape
+    params = check_params(params)
+    if params.shape[1] != n:
+        raise ValueError(f"battery params for {params.shape[1]} chains, traces of {n}")
+    cap, pc, pd, ec, ed, sb = params
+    kc, kd = _recip(ec), _recip(ed)
+    out = np.zeros((base.shape[0], len(COLUMNS), n), dtype=np.int64)
+    out[:, :4] = base
+    x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (n,)), 0, cap)
+    ok, d_all = _ok_d(pv, meter, covered)
+    for t in range(n_steps):
+        k, o = divmod(origin + t, interval_s)
+        oks, d = ok[t], d_all[t]
+        a = np.clip(d, -pd, pc)
+        s = _stored(a, ec, kd)
+        x1 = np.clip(x + s, 0, cap)
+        g = x1 - x
+        fill = np.minimum(a, (g * kc + 65535) >> 16)
+        drain = -np.minimum(-a, (-g * ed) >> 16)
+        b = np.where(g == s, a, np.where(g > 0, fill, np.where(g < 0, drain, 0)))
+        xn = np.maximum(x1 - sb, 0)
+        row = out[k]
+        row[4] += np.where(oks, np.maximum(b - d, 0), 0)
+        row[5] += np.where(oks, np.maximum(d - b, 0), 0)
+        row[6] += np.where(oks, np.maximum(b, 0), 0)
+        row[7] += np.where(oks, np.maximum(-b, 0), 0)
+        row[8] = np.where(oks, ((o + 1) << KEY_SHIFT) | xn, row[8])                 # later seconds have larger keys
+        row[9] += np.where(oks, b - (xn - x), 0)
+        x = np.where(oks, xn, x)
+    return out, x
+
+
+def to_registers(raw):
+    """The registers table [n_intervals, 6, n] of the meter behind the battery (the first six columns; a view)."""
+    if raw.ndim != 3 or raw.shape[1] != len(COLUMNS):
+        raise ValueError("raw battery table must be [n_intervals, 10, n]")
+    return raw[:, :6]
+
+
+def to_watts(raw, interval_s, n_steps=None):
+    """float64 views of a raw table [n_intervals, 10, n]: storage.to_watts' keys (charge and discharge at the
+    meter side) plus energy_wh_loss (Wh lost in conversion and standby) and round_trip = discharged /
+    (charged - the interval's SoC change), the share of what went in and is no longer stored that came out
+    again -- NaN where the denominator is 0.  n_steps, when given, is checked against the interval count."""
+    raw = np.asarray(raw.cpu() if hasattr(raw, "cpu") else raw).astype(np.int64, copy=False)
+    if raw.ndim != 3 or raw.shape[1] != len(COLUMNS):
+        raise ValueError("raw battery table must be [n_intervals, 10, n]")
+    out = storage.to_watts(raw[:, :9], interval_s, n_steps=n_steps)
+    e = float(1 << FRAC_BITS) * 3600.0
+    dsoc = raw[:, 6] - raw[:, 7] - raw[:, 9]
+    den = raw[:, 6] - dsoc
+    out.update({"energy_wh_loss": raw[:, 9] / e,
+                "round_trip": raw[:, 7] / np.where(den != 0, den, np.nan).astype(np.float64)})
+    return out

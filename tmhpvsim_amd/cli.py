@@ -20,6 +20,10 @@ tmhpvsim/metersim.py:79-95).
     python -m tmhpvsim_amd.cli storage FILE --batch N --no-realtime --interval S --capacity-wh X --charge-w P
                                             --discharge-w P [--soc0-wh X] [--all-chains NPZ]
                                             [--start T --seconds S --seed K]
+    python -m tmhpvsim_amd.cli battery FILE --batch N --no-realtime --interval S --capacity-wh X[,X..] --charge-w P[,P..]
+                                            --discharge-w P[,P..] [--charge-eff E[,E..]] [--discharge-eff E[,E..]]
+                                            [--standby-w P[,P..]] [--soc0-wh X[,X..]] [--all-chains NPZ]
+                                            [--start T --seconds S --seed K]
 
 Without --batch the commands are the reference's AMQP pipelines (a fanout
 exchange carrying one JSON float per second, pvsim.py:43-84, metersim.py:13-62):
@@ -61,6 +65,12 @@ greedy self-consumption, lossless; an fp64 engine run) and writes chain 0's inte
 `time,import_wh,export_wh,pv_wh,meter_wh,charge_wh,discharge_wh,soc_wh,n_ok` -- the energy
 drawn from the grid and fed in with the battery, produced, consumed, put into and taken out of
 the battery (Wh), the state of charge at the interval's end and the ok seconds; --all-chains
+writes every chain's raw table and its arrays to an .npz.
+`battery` is `storage` with losses and per-chain batteries (tmhpvsim_amd.battery: charge and
+discharge efficiency in [0.5, 1], a standby drain in W).  Each battery option takes one value or a
+comma-separated list dealt to the chains round-robin (chain i gets value i mod the list's length):
+a fleet of different batteries, or a sweep of sizes across otherwise equal scenarios in one run.
+The CSV is `storage`'s with `loss_wh` (conversion and standby losses) before `n_ok`; --all-chains
 writes every chain's raw table and its arrays to an .npz.
 There is no CPU fallback: the batch mode fails if the engine cannot run.
 """
@@ -113,7 +123,7 @@ def _fleet_run(n, start, seconds, seed, precision, bin_s):
 
 
 def _table_run(kind, n, start, seconds, seed, precision, interval_s, **enable_kw):
-    """An engine run with the interval table `kind` ("intervals", "registers", "demand" or "storage")
+    """An engine run with the interval table `kind` ("intervals", "registers", "demand", "storage" or "battery")
     only: the raw table and its watt / watt-hour arrays.  enable_kw: the kind's own arguments."""
     from .engine import BatchedSim
     from .params import ModelParams
@@ -246,11 +256,15 @@ TABLE_CSV = {
     "storage": (("import_wh", "energy_wh_import"), ("export_wh", "energy_wh_export"), ("pv_wh", "energy_wh_pv"),
                 ("meter_wh", "energy_wh_meter"), ("charge_wh", "energy_wh_charge"), ("discharge_wh", "energy_wh_discharge"),
                 ("soc_wh", "soc_wh"), ("n_ok", "n_ok")),
+    "battery": (("import_wh", "energy_wh_import"), ("export_wh", "energy_wh_export"), ("pv_wh", "energy_wh_pv"),
+                ("meter_wh", "energy_wh_meter"), ("charge_wh", "energy_wh_charge"), ("discharge_wh", "energy_wh_discharge"),
+                ("soc_wh", "soc_wh"), ("loss_wh", "energy_wh_loss"), ("n_ok", "n_ok")),
 }
 
 
 def _table_command(kind, file, batch, start, seconds, seed, precision, interval_s, all_chains, **enable_kw):
-    """The `intervals`, `registers`, `demand` and `storage` commands: chain 0's rows to FILE, every chain to the .npz."""
+    """The `intervals`, `registers`, `demand`, `storage` and `battery` commands: chain 0's rows to FILE, every chain
+    to the .npz."""
     raw, out = _table_run(kind, batch, start, seconds, seed, precision, interval_s, **enable_kw)
     t0 = dt.datetime.fromisoformat(str(start))
     rows = raw.shape[0]
@@ -324,6 +338,47 @@ def storage(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, 
     _need_batch(realtime, batch, "storage")
     _table_command("storage", file, batch, start, seconds, seed, "fp64", interval_s, all_chains, capacity_wh=capacity_wh,
                    charge_w=charge_w, discharge_w=discharge_w, soc0_wh=soc0_wh)
+
+
+def _dealt(ctx, param, value):
+    """A battery option: one float or a comma-separated list of them."""
+    try:
+        vals = [float(v) for v in str(value).split(",")]
+    except ValueError:
+        raise click.BadParameter("a number or a comma-separated list of numbers")
+    return vals
+
+
+def _deal(vals, n):
+    """vals dealt to n chains round-robin."""
+    return [vals[i % len(vals)] for i in range(int(n))]
+
+
+@main.command()
+@click.argument("file")
+@common
+@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
+@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
+              help="seconds per metering interval (a last partial interval is kept)")
+@click.option("--capacity-wh", callback=_dealt, required=True, help="battery capacity (Wh); a list is dealt to the chains")
+@click.option("--charge-w", callback=_dealt, required=True, help="charge power limit at the meter side (W)")
+@click.option("--discharge-w", callback=_dealt, required=True, help="discharge power limit at the meter side (W)")
+@click.option("--charge-eff", callback=_dealt, default="1.0", help="charge efficiency in [0.5, 1]")
+@click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]")
+@click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)")
+@click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)")
+def battery(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
+            charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh):
+    """Battery storage with losses of chain 0 over --batch chains to FILE (CSV; battery-only fp64 engine run)."""
+    logging.basicConfig(level=logging.WARN - 10 * verbose)
+    _need_batch(realtime, batch, "battery")
+    try:
+        _table_command("battery", file, batch, start, seconds, seed, "fp64", interval_s, all_chains,
+                       **{k: _deal(v, batch) for k, v in dict(
+                           capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
+                           discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh).items()})
+    except ValueError as e:   # (a quantity outside its range: battery.quantize_params)
+        raise click.ClickException(str(e))
 
 
 if __name__ == "__main__":

@@ -79,6 +79,13 @@ constexpr int EXP_WG_STATS = 512;
 //    kernel ran 2.4 x the registers kernel (Demand registers).  512-chain workgroups are
 //    two waves per SIMD each, so 5 waves (96 VGPRs) would hold no more workgroups than 4.
 constexpr int EXP_WAVES_TRACE = 7, EXP_WAVES_STATS = 6, EXP_WAVES_F64 = 4, EXP_WAVES_SITES = 3, EXP_WAVES_DEMAND = 4;
+//  the battery kind's replay pass (fp64 single-site): 3 = at most 168 VGPRs, in 256-chain workgroups (exp_wg) so
+//    that three of them are resident per CU.  Its per-lane parameters and one more 64-bit sum are eleven more
+//    registers live across the per-second loop than storage's replay holds; at 4 waves (128 VGPRs, 512-chain
+//    workgroups) it spilled 213 VGPRs against storage's 81 and ran 87.5 ms where storage's replay runs 51.2 ms;
+//    at 3 it spills 24 and runs 47.1 ms (Battery losses)
+constexpr int EXP_WAVES_LOSSY = 3;
+constexpr bool out_lossy_replay(int out) { return out_base(out) == OUT_STORAGE && (out & OUT_LOSSY) && !(out & OUT_MAP); }
 constexpr int FIX_WAVES_SITES = 1;   // min waves per SIMD of the per-site fixup (its fp64 redo recomputes the site's geometry)
 
 struct BlockDesc {                 // as of the step before the block start; -1 = none in the window
@@ -2022,7 +2029,7 @@ constexpr int exp_tile_order()
 template <typename R, int OUT, bool SITES>
 constexpr int exp_wg()
 {
-    return out_no_trace(OUT) && !SITES ? EXP_WG_STATS : 256;
+    return out_lossy_replay(OUT) ? 256 : out_no_trace(OUT) && !SITES ? EXP_WG_STATS : 256;
 }
 // the LDS histogram as 16-bit bin pairs when one tile (WG chains x 128 s) cannot fill a
 // 16-bit bin, else one 32-bit word per bin
@@ -2035,6 +2042,7 @@ template <typename R, int OUT, bool SITES>
 constexpr int exp_waves()
 {
     return SITES                             ? EXP_WAVES_SITES
+           : out_lossy_replay(OUT)            ? EXP_WAVES_LOSSY
            : sizeof(R) == 8                   ? EXP_WAVES_F64
            : out_base(OUT) == OUT_TRACE3      ? EXP_WAVES_TRACE
            : out_base(OUT) == OUT_DEMAND      ? EXP_WAVES_DEMAND
@@ -2120,7 +2128,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                             uint32_t (*cov_lds)[WGT], R (*min_lds)[WGT], uint4* held_lds,
                                             const PV64* pv_lds, const double* pv_lds_tab,
                                             const float4* nd_lds, const SeriesView& se, SeriesLds* ser_lds,
-                                            const IntervalsView& ivv, const StorageView& sto)
+                                            const IntervalsView& ivv, const StorageView& sto, const long long* batp)
 {
     constexpr bool SER = out_base(OUT) == OUT_SERIES;
     // Battery storage (fp64 only), two passes over the same per-second body:
@@ -2132,6 +2140,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     constexpr bool STO = out_base(OUT) == OUT_STORAGE;
     constexpr bool MAP = STO && (OUT & OUT_MAP) != 0;
     constexpr bool REP = STO && !MAP;
+    // BAT: the battery kind on the same two passes -- the lane's six parameters from batp (once per block,
+    // lane-consecutive rows), what the ask stores or drains in place of the ask, the standby drain after it,
+    // and in the replay one accumulator and one column more (IVC = 10)
+    constexpr bool BAT = STO && (OUT & OUT_LOSSY) != 0;
     static_assert(!STO || sizeof(R) == 8, "battery storage: fp64 engines only (no guard-band seconds)");
     // REG: the import / export registers -- the intervals' pieces, accumulators and flush, with
     // one more accumulator and IVC = 6 columns per cell instead of 4
@@ -2324,8 +2336,17 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // max(-g, 0) = g, so over the piece import_b = export_b + (sx - sx0) - (iv_pv - iv_m) and the
     // discharge is st_ch - (sx - sx0), exact in integers.  A second that is not ok leaves sx as it is,
     // so sx at the piece's end is the state after the piece's last ok second: the SoC key needs no tracking.
+    // The battery kind (BAT) accumulates what the meter side gave (st_ch: max(b, 0)) and took back (st_dis:
+    // max(-b, 0)) beside export_b: per second import_b - export_b = b - d and loss = b - (x' - x), so over the
+    // piece import_b = export_b + (st_ch - st_dis) - (iv_pv - iv_m) and the loss is st_ch - st_dis - (sx - sx0).
     SocMap st_map = soc_identity();
-    long long sx = 0, sx0 = 0, st_ch = 0;
+    long long sx = 0, sx0 = 0, st_ch = 0, st_dis = 0;
+    BatteryParams bp = battery_none();
+    long long bat_hi = 0;   // the second's map after the standby drain: {s - sigma, 0, max(C - sigma, 0)}
+    if constexpr (BAT) {
+        if (live) bp = battery_load(batp, ivv.ld, gid(kp.ids, c));
+        bat_hi = max(bp.cap - (long long)bp.sigma, 0ll);
+    }
     if constexpr (REP) {
         if (live) sx = sto.work[(size_t)b * 3 * n + c];
         sx0 = sx;
@@ -2346,7 +2367,14 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 if (im) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)im);
                 if (iv_ex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)iv_ex);
             }
-            if constexpr (REP) {
+            if constexpr (BAT && REP) {
+                const long long net = st_ch - st_dis, im = iv_ex + net - (iv_pv - iv_m), loss = net - (sx - sx0);
+                if (im) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)im);
+                if (iv_ex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)iv_ex);
+                if (st_ch) atomicAdd(cell + 6 * ivv.ld, (unsigned long long)st_ch);
+                if (st_dis) atomicAdd(cell + 7 * ivv.ld, (unsigned long long)st_dis);
+                if (loss) atomicAdd(cell + 9 * ivv.ld, (unsigned long long)loss);
+            } else if constexpr (REP) {
                 const long long dx = sx - sx0, im = iv_ex + dx - (iv_pv - iv_m), dis = st_ch - dx;
                 if (im) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)im);
                 if (iv_ex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)iv_ex);
@@ -2388,6 +2416,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             iv_ex = 0;
             st_ch = 0;
             sx0 = sx;
+            if constexpr (BAT) st_dis = 0;
         }
         if constexpr (DEM) {
             dm_im = 0;
@@ -2427,7 +2456,27 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             if (!(__builtin_constant_p(pv) && pv == R(0))) qp = series_q<R>(pv);
             const int d = qp - qm;
             const long long a = (long long)soc_ask(d, sto.p_charge, sto.p_discharge);
-            if constexpr (MAP) {
+            if constexpr (BAT) {
+                // the battery kind (tmh_battery): what the lane's own ask stores or drains, then the standby
+                // drain; the map pass composes the two clamped additions as one, the replay pass takes the
+                // meter side b from how far the state of charge really moved
+                const int ab = soc_ask(d, bp.pc, bp.pd), s = bat_stored(ab, bp);
+                if constexpr (MAP) {
+                    const SocMap f = soc_compose(st_map, SocMap{(long long)(s - bp.sigma), 0, bat_hi});
+                    st_map.a = ok ? f.a : st_map.a;
+                    st_map.lo = ok ? f.lo : st_map.lo;
+                    st_map.hi = ok ? f.hi : st_map.hi;
+                } else {
+                    const long long x1 = soc_clamp(sx + s, 0, bp.cap);
+                    const int bm = bat_meter_side(ab, s, (int)(x1 - sx), bp);
+                    sx = ok ? max(x1 - (long long)bp.sigma, 0ll) : sx;
+                    iv_m += (long long)(ok ? qm : 0);
+                    if (!(__builtin_constant_p(pv) && pv == R(0))) iv_pv += (long long)(ok ? qp : 0);
+                    iv_ex += (long long)(ok ? max(d - bm, 0) : 0);
+                    st_ch += (long long)(ok ? max(bm, 0) : 0);
+                    st_dis += (long long)(ok ? max(-bm, 0) : 0);
+                }
+            } else if constexpr (MAP) {
                 const SocMap f = soc_compose(st_map, SocMap{a, 0, sto.cap});
                 st_map.a = ok ? f.a : st_map.a;
                 st_map.lo = ok ? f.lo : st_map.lo;
@@ -2717,7 +2766,9 @@ using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView,
                                    std::conditional_t<out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS ||
                                                           out_base(OUT) == OUT_DEMAND,
                                                       IntervalsView,
-                                                      std::conditional_t<out_base(OUT) == OUT_STORAGE, StorageView, TraceView>>>;
+                                                      std::conditional_t<out_base(OUT) == OUT_STORAGE,
+                                                                         std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>,
+                                                                         TraceView>>>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
                                                      uint32_t n, int64_t W0, uint32_t nsteps, int64_t utc0,
@@ -2735,10 +2786,15 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     SeriesView se{};
     IntervalsView ivv{};
     StorageView sto{};
+    const long long* batp = nullptr;
     if constexpr (out_base(OUT) == OUT_SERIES) se = ov;
     else if constexpr (out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS || out_base(OUT) == OUT_DEMAND)
         ivv = ov;
-    else if constexpr (out_base(OUT) == OUT_STORAGE) {   // battery storage: its table through the intervals' view
+    else if constexpr (out_base(OUT) == OUT_STORAGE && (OUT & OUT_LOSSY) != 0) {   // the battery kind: storage's view + the parameters
+        sto = ov.st;
+        ivv = ov.st.iv;
+        batp = ov.params;
+    } else if constexpr (out_base(OUT) == OUT_STORAGE) {   // battery storage: its table through the intervals' view
         sto = ov;
         ivv = ov.iv;
     } else tr = ov;
@@ -2765,7 +2821,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     auto tile = [&](uint32_t b, uint32_t cblk, auto night) __attribute__((always_inline)) {
         expand_tile<R, OUT, SITES, WGT, decltype(night)::value>(
             b, cblk, kp, dp, st, chain0, n, W0, nsteps, utc0, tab64, tab32, sun, events, n_events, desc, sg, tr, sv,
-            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv, sto);
+            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv, sto, batp);
     };
     // the workgroup's LDS histogram into the device histogram
     auto hist_flush = [&]() __attribute__((always_inline)) {
@@ -2864,14 +2920,20 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
 // waits for another: the only dependent chain is the lane's own add and two clamps per block.  The
 // loads are lane-consecutive and do not depend on the state, so SCAN_G blocks' maps are loaded ahead
 // of the chain that consumes them.  (soc: per chain index, ids[slot] in a compacted window.)
+// BAT (battery_scan_kernel, the battery kind): the state of charge read from soc is clamped into the chain's
+// [0, C] first (params row 0, clamped as battery_load clamps it), so a caller's soc above C cannot leave a
+// block start outside the range the replay pass assumes.
 constexpr uint32_t SCAN_G = 8;
-__global__ __launch_bounds__(256) void storage_scan_kernel(long long* __restrict__ work, long long* __restrict__ soc,
-                                                           const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk)
+template <bool BAT>
+__device__ __forceinline__ void storage_scan(long long* __restrict__ work, long long* __restrict__ soc,
+                                             const long long* __restrict__ params, const uint32_t* __restrict__ ids,
+                                             uint32_t n, uint32_t nblk)
 {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n) return;
     const uint32_t i = gid(ids, c);
     long long x = soc[i];
+    if constexpr (BAT) x = soc_clamp(x, 0, soc_clamp(params[i], 0, BAT_CAP_MAX));
     long long* w = work + c;
     const size_t bs = (size_t)3 * n;   // a block's three rows
     uint32_t b = 0;
@@ -2893,6 +2955,17 @@ __global__ __launch_bounds__(256) void storage_scan_kernel(long long* __restrict
         w += bs;
     }
     soc[i] = x;
+}
+__global__ __launch_bounds__(256) void storage_scan_kernel(long long* __restrict__ work, long long* __restrict__ soc,
+                                                           const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk)
+{
+    storage_scan<false>(work, soc, nullptr, ids, n, nblk);
+}
+__global__ __launch_bounds__(256) void battery_scan_kernel(long long* __restrict__ work, long long* __restrict__ soc,
+                                                           const long long* __restrict__ params,
+                                                           const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk)
+{
+    storage_scan<true>(work, soc, params, ids, n, nblk);
 }
 
 // ------------------------------------------------------------ compaction
@@ -3407,9 +3480,9 @@ void with_real(bool f64, F&& f)
 // one kind per engine at a step.  A kind is its column count, the expansion's and the fixup's
 // output, and the words the refusals name it by; a new kind is a row here, its columns in
 // expand_tile and the fixup, and its exported setter.
-enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_KINDS };
+enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_KINDS };
 struct TableKindInfo {
-    int cols, out;
+    int cols, out;      // out: TMH_OUT_* as tmh_engine_last_expand reports it (the expansion's OutKind but for TBL_BATTERY)
     const char* what;   // in the setter's and the checks' messages
     const char* name;   // as the other table of a both-set refusal
 };
@@ -3420,11 +3493,16 @@ constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
     // battery storage (tmh_storage: the descriptor's other fields sit beside the slot, tmh_engine::storage);
     // fp64 engines only, three launches (phase_expand), no fixup
     {TMH_STORAGE_COLS, OUT_STORAGE, "storage tables", "battery storage"},
+    // the battery kind (tmh_battery: losses and per-chain parameters; tmh_engine::battery): storage's three
+    // launches on the OUT_STORAGE | OUT_LOSSY instantiations, reported as TMH_OUT_BATTERY
+    {TMH_BATTERY_COLS, TMH_OUT_BATTERY, "battery tables", "the battery kind"},
 };
+static_assert(TMH_OUT_BATTERY > out_base(~0) && TMH_OUT_BATTERY < TMH_OUT_SITES, "TMH_OUT_BATTERY: a code of its own below the flags");
 static_assert(interval_cols(OUT_INTERVALS) == TABLE_KINDS[TBL_INTERVALS].cols &&
                   interval_cols(OUT_REGISTERS) == TABLE_KINDS[TBL_REGISTERS].cols &&
                   interval_cols(OUT_DEMAND) == TABLE_KINDS[TBL_DEMAND].cols &&
-                  interval_cols(OUT_STORAGE) == TABLE_KINDS[TBL_STORAGE].cols,
+                  interval_cols(OUT_STORAGE) == TABLE_KINDS[TBL_STORAGE].cols &&
+                  interval_cols(OUT_STORAGE | OUT_LOSSY) == TABLE_KINDS[TBL_BATTERY].cols,
               "the kernels' cells");
 
 }  // namespace
@@ -3449,6 +3527,7 @@ struct tmh_engine {
         tmh_intervals t{};
     } tables[TBL_KINDS];
     tmh_storage storage{};   // tmh_set_storage: the battery, soc and the work buffer beside tables[TBL_STORAGE]
+    tmh_battery battery{};   // tmh_set_battery: soc, the work buffer and the parameters beside tables[TBL_BATTERY]
     // the first set kind (TBL_KINDS: none); a step is refused unless it is the only one (check_interval_tables)
     int table_kind() const
     {
@@ -3953,6 +4032,35 @@ int tmh_set_storage(struct tmh_engine* eng, const tmh_storage* st)
     return TMH_OK;
 }
 
+// the battery kind: tmh_set_storage's checks in its own words, the parameters in place of the three integers
+// (their values are the kernels' to clamp: the host never reads the tensor)
+int tmh_set_battery(struct tmh_engine* eng, const tmh_battery* bt)
+{
+    if (!bt) {
+        if (int rc = set_interval_table(eng, TBL_BATTERY, nullptr)) return rc;
+        eng->battery = tmh_battery{};
+        return TMH_OK;
+    }
+    const char* what = TABLE_KINDS[TBL_BATTERY].what;
+    if (!bt->table.sum || bt->table.n_steps == 0 || bt->table.ld == 0 || ((uintptr_t)bt->table.sum & 7) ||
+        bt->table.interval_s == 0)   // (the struct's cases, in the setter's words)
+        return set_interval_table(nullptr, TBL_BATTERY, &bt->table);
+    if (bt->table.interval_s > (1u << 23) - 1)
+        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
+                    bt->table.interval_s);
+    if (!bt->soc || ((uintptr_t)bt->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer", what);
+    if (!bt->work || ((uintptr_t)bt->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
+    if (!bt->params || ((uintptr_t)bt->params & 7))
+        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor [6][ld]", what);
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (eng->kp.precision != TMH_FP64)   // (as tmh_set_storage)
+        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
+                                 "expansion, and the state of charge depends on every earlier second)", what);
+    if (int rc = set_interval_table(eng, TBL_BATTERY, &bt->table)) return rc;
+    eng->battery = *bt;
+    return TMH_OK;
+}
+
 // A step / expansion with an interval table set (nothing to check without one): everything the
 // kernels assume, checked on the host before any launch (tmhpvsim.h, tmh_set_intervals,
 // tmh_set_registers, tmh_set_demand).  The messages name the first set kind; with two kinds set
@@ -3969,6 +4077,11 @@ static int check_interval_tables(const tmh_engine* eng, uint32_t n_chains, int64
     if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
         return fail(TMH_E_INVAL, "%s are set: no traces in the same call (a caller with traces can sum them)", what);
     if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
+    if (eng->tables[TBL_BATTERY].set && kind != TBL_BATTERY)   // (kind: the first set one, so another table, storage included)
+        return fail(TMH_E_INVAL, "the battery kind and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
+    if (kind == TBL_BATTERY && eng->battery.work_bytes < tmh_storage_work_bytes(n_chains, n_steps))
+        return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->battery.work_bytes,
+                    tmh_storage_work_bytes(n_chains, n_steps));
     if (eng->tables[TBL_STORAGE].set && kind != TBL_STORAGE)   // (kind: the first set one, so another table)
         return fail(TMH_E_INVAL, "battery storage and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
     if (kind == TBL_STORAGE && eng->storage.work_bytes < tmh_storage_work_bytes(n_chains, n_steps))
@@ -3994,7 +4107,7 @@ static int check_interval_tables(const tmh_engine* eng, uint32_t n_chains, int64
     const double paco = eng->kp.inverter[0], pnt = std::fabs(eng->kp.inverter[8]);
     if (eng->kp.with_pv && !(paco < TMH_SERIES_MAX_W && (double)(float)paco < TMH_SERIES_MAX_W &&
                              pnt < TMH_SERIES_MAX_W && (double)(float)pnt < TMH_SERIES_MAX_W))
-        return fail(TMH_E_INVAL, "inverter Paco %g W (|Pnt| %g W) not below TMH_SERIES_MAX_W %g W", paco, pnt,
+        return fail(TMH_E_INVAL, "%s: inverter Paco %g W (|Pnt| %g W) not below TMH_SERIES_MAX_W %g W", what, paco, pnt,
                     (double)TMH_SERIES_MAX_W);
     return TMH_OK;
 }
@@ -4342,6 +4455,24 @@ static int phase_expand(const StepCtx& c)
                     eng->close(TMH_K_STORAGE_SCAN, t, c.s);
                     t = eng->mark(c.s);
                     launch(r, std::integral_constant<int, OUT_STORAGE>{}, st, stv, sv);
+                    eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
+                }
+            } else if (table == TBL_BATTERY) {
+                // the battery kind (fp64: tmh_set_battery): storage's three launches and work buffer, the
+                // parameters from memory, the scan clamping the state of charge it reads; the same timers
+                if constexpr (!F32) {
+                    const tmh_battery& bb = eng->battery;
+                    const long long* params = reinterpret_cast<const long long*>(bb.params);
+                    const BatteryView btv{StorageView{c.ivv, reinterpret_cast<long long*>(bb.work), 0, 0, 0}, params};
+                    hipEvent_t t = eng->mark(c.s);
+                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_MAP>{}, st, btv, StatsView{});
+                    eng->close(TMH_K_STORAGE_MAP, t, c.s);
+                    t = eng->mark(c.s);
+                    hipLaunchKernelGGL(battery_scan_kernel, dim3(c.cb()), dim3(256), 0, c.s, btv.st.work,
+                                       reinterpret_cast<long long*>(bb.soc), params, eng->kp.ids, c.n_chains, c.sg.nblk);
+                    eng->close(TMH_K_STORAGE_SCAN, t, c.s);
+                    t = eng->mark(c.s);
+                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY>{}, st, btv, sv);
                     eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
                 }
             } else if (table != TBL_KINDS) {

@@ -1537,7 +1537,10 @@ enum OutKind : int {
     // fp32 bin position is not accurate enough, StatsView::bin64); OUT_BRT decides at run time
     OUT_B64 = 8, OUT_BRT = 16,
     // flag on OUT_STORAGE: the map pass -- no output but each (chain, block)'s composed state-of-charge map
-    OUT_MAP = 32
+    OUT_MAP = 32,
+    // flag on OUT_STORAGE: the battery kind (tmh_battery) -- per-chain parameters from memory, charge and
+    // discharge efficiency, standby drain and the loss column; the engine reports it as TMH_OUT_BATTERY
+    OUT_LOSSY = 64
 };
 constexpr int out_base(int out) { return out & 7; }
 // no trace: the statistics-only expansion's workgroup shape
@@ -1567,7 +1570,7 @@ struct IntervalsView {
 };
 constexpr int interval_cols(int out)
 {
-    return out_base(out) == OUT_STORAGE  ? TMH_STORAGE_COLS
+    return out_base(out) == OUT_STORAGE  ? ((out & OUT_LOSSY) ? TMH_BATTERY_COLS : TMH_STORAGE_COLS)
            : out_base(out) == OUT_DEMAND ? TMH_DEMAND_COLS
            : out_base(out) == OUT_REGISTERS ? TMH_REGISTERS_COLS
                                             : 4;
@@ -1615,6 +1618,64 @@ struct StorageView {
     long long* work;
     long long cap;
     int p_charge, p_discharge;
+};
+// The battery kind (tmh_battery): the storage kind's second with losses and per-chain parameters.  A chain's
+// six parameters are rows of params[6][ld] (ld: the table's), clamped into their ranges as a lane loads them,
+// so no address and no shift depends on a value in memory.  With the ask a = clamp(d, -Pd, Pc) at the meter
+// side the battery stores s = floor(a ec / 2^16) or is drained of s = -ceil(-a / ed * 2^16), the latter as a
+// multiplication by kd = ceil(2^32 / ed); s does not depend on the state of charge, so the second is still a
+// clamped addition followed by the standby drain's, and SocMap, soc_compose and soc_apply serve unchanged.
+constexpr int BAT_EFF_ONE = 1 << 16, BAT_EFF_MIN = 1 << 15, BAT_POWER_MAX = 1 << 27;
+constexpr long long BAT_CAP_MAX = (1ll << 40) - 1;
+struct BatteryParams {
+    long long cap;      // C
+    int pc, pd;         // Pc, Pd (meter side)
+    uint32_t ec, ed;    // efficiencies in 2^-16
+    uint32_t kc, kd;    // ceil(2^32 / ec), ceil(2^32 / ed): in [2^16, 2^17]
+    int sigma;          // standby drain per ok second
+};
+constexpr uint32_t bat_recip(uint32_t e) { return 0xFFFFFFFFu / e + 1u; }   // ceil(2^32 / e) for 1 <= e <= 2^16
+constexpr int bat_clamp_int(long long v, int lo, int hi) { return (int)(v < lo ? lo : v > hi ? hi : v); }
+// a lane's parameters from column i of params[6][ld]
+__device__ __forceinline__ BatteryParams battery_load(const long long* __restrict__ params, uint64_t ld, uint32_t i)
+{
+    BatteryParams p;
+    p.cap = soc_clamp(params[i], 0, BAT_CAP_MAX);
+    p.pc = bat_clamp_int(params[ld + i], 0, BAT_POWER_MAX);
+    p.pd = bat_clamp_int(params[2 * ld + i], 0, BAT_POWER_MAX);
+    p.ec = (uint32_t)bat_clamp_int(params[3 * ld + i], BAT_EFF_MIN, BAT_EFF_ONE);
+    p.ed = (uint32_t)bat_clamp_int(params[4 * ld + i], BAT_EFF_MIN, BAT_EFF_ONE);
+    p.sigma = bat_clamp_int(params[5 * ld + i], 0, BAT_POWER_MAX);
+    p.kc = bat_recip(p.ec);
+    p.kd = bat_recip(p.ed);
+    return p;
+}
+// a lane past the last chain: an empty lossless battery (never stored or flushed)
+constexpr BatteryParams battery_none() { return BatteryParams{0, 0, 0, BAT_EFF_ONE, BAT_EFF_ONE, BAT_EFF_ONE, BAT_EFF_ONE, 0}; }
+// What the ask a (|a| <= 2^27) stores (+, rounded down) or drains (-, rounded up): one 32 x 32 -> 64 bit
+// product on every lane, the sign a select.  |s| <= 2^28.
+constexpr int bat_stored(int a, const BatteryParams& p)
+{
+    const bool up = a >= 0;
+    const unsigned long long t = (unsigned long long)(uint32_t)(up ? a : -a) * (up ? p.ec : p.kd) + (up ? 0u : 65535u);
+    const int m = (int)(t >> 16);
+    return up ? m : -m;
+}
+// What the meter side sees, b, when the ask a would have moved the state of charge by s and it moved by g:
+// a itself when nothing clipped; else what g costs (filling: rounded up) or yields (emptying: rounded down),
+// never more than |a|.  g and s have a's sign or are 0.  The product runs on every lane, the clip is a select.
+constexpr int bat_meter_side(int a, int s, int g, const BatteryParams& p)
+{
+    const bool up = g > 0;
+    const unsigned long long t = (unsigned long long)(uint32_t)(up ? g : -g) * (up ? p.kc : p.ed) + (up ? 65535u : 0u);
+    const long long m = (long long)(t >> 16), aa = a >= 0 ? a : -(long long)a;
+    const int bm = (int)(m < aa ? m : aa);
+    return g == s ? a : up ? bm : -bm;
+}
+// The battery kind's view: the storage kind's (cap, p_charge, p_discharge unused) and the parameters.
+struct BatteryView {
+    StorageView st;
+    const long long* params;
 };
 // The demand registers' packed key of a second (tmh_demand): the quantised power v (0 <= v < 2^27)
 // above the complement of the second's offset o in its interval, so the maximum key is the

@@ -73,11 +73,24 @@ _TABLES = {
         run_excludes=(("_intervals", "_registers", "_demand"), "battery storage and another interval table are both "
                                                                "enabled: one of them per sim"),
         no_trace="a storage run takes no traces (trace=()): run the battery over the traces instead (storage.from_traces)"),
+    # the battery kind (enable_battery: storage with losses and per-chain parameters; fp64 sims only)
+    "battery": dict(
+        noun="battery tables", name="the battery kind",
+        enable_excludes=tuple(
+            (attr, f"{what} is enabled: one table output per sim (the battery kind runs alone)")
+            for attr, what in (("_series", "a fleet series"), ("_intervals", "interval metering"),
+                               ("_registers", "the import / export registers"), ("_demand", "the demand registers"))),
+        run_excludes=(("_intervals", "_registers", "_demand", "_storage"), "the battery kind and another interval table "
+                                                                           "are both enabled: one of them per sim"),
+        no_trace="a battery run takes no traces (trace=()): run the battery over the traces instead (battery.from_traces)"),
 }
 for _kind, _t in _TABLES.items():   # no table beside battery storage, whichever was enabled first
     if _kind != "storage":
         _t["enable_excludes"] += (("_storage", "battery storage is enabled: one table output per sim "
                                                "(battery storage runs alone)"),)
+    if _kind != "battery":
+        _t["enable_excludes"] += (("_battery", "the battery kind is enabled: one table output per sim "
+                                               "(the battery kind runs alone)"),)
 
 
 class BatchedSim:
@@ -179,6 +192,8 @@ class BatchedSim:
             setattr(self, "_" + kind, None)
         self.soc = None           # int64 [n]: the batteries' state of charge (enable_storage)
         self._storage_args = self._storage_work = self._storage_desc = None
+        self.battery_params = None   # int64 [6, n]: the batteries' parameters (enable_battery); soc and the work buffer as storage's
+        self._battery_desc = None
         self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
@@ -269,8 +284,8 @@ class BatchedSim:
     def _enable_table(self, kind, n_steps, interval_s, step0, buffer):
         """enable_intervals, enable_registers and enable_demand (_TABLES[kind])."""
         torch = _torch()
-        if kind == "storage":   # (its descriptor holds the table's: _set_storage)
-            setter = lambda eng, st: self._set_storage(st._obj if st is not None else None)
+        if kind in ("storage", "battery"):   # (its descriptor holds the table's: _set_storage, _set_battery)
+            setter = lambda eng, st: getattr(self, "_set_" + kind)(st._obj if st is not None else None)
         else:
             setter = getattr(self.L, "tmh_set_" + kind)
         if n_steps is None:
@@ -385,7 +400,8 @@ class BatchedSim:
         other table; compaction is allowed.  n_steps=None switches the output off."""
         torch = _torch()
         if n_steps is None:
-            self.soc = self._storage_work = self._storage_desc = None
+            if self._battery is None:   # (soc and the work buffer may be enable_battery's)
+                self.soc = self._storage_work = self._storage_desc = None
             return self._enable_table("storage", None, interval_s, step0, buffer)
         if self.precision != _lib.TMH_FP64:
             raise ValueError("battery storage needs precision='fp64': an fp32 engine replaces its guard-band seconds "
@@ -429,18 +445,98 @@ class BatchedSim:
         return rc
 
     def _storage_window(self, win):
-        """run(): the work buffer holds a window of `win` steps (a larger one replaces it)."""
+        """run(): the work buffer (storage's or the battery kind's) holds a window of `win` steps (a larger
+        one replaces it)."""
         need = self.L.tmh_storage_work_bytes(self.n, int(win))
         if self._storage_work.numel() < need:
             _torch().cuda.synchronize(self.device)   # (launches of earlier runs may still read the old one)
             self._storage_work = _torch().empty(need, dtype=torch_uint8(), device=self.device)
-            _lib.check(self._set_storage(self._storage))
+            if self._battery is not None:
+                _lib.check(self._set_battery(self._battery))
+            else:
+                _lib.check(self._set_storage(self._storage))
 
     def storage(self):
         """The storage table in watts and watt-hours (storage.to_watts of storage_raw): the intervals'
         keys plus energy_wh_import, energy_wh_export, energy_wh_charge, energy_wh_discharge, soc_wh and
         the self_consumption and self_sufficiency ratios, [n_intervals, n] each."""
         return self._table_watts("storage")
+
+    # ------------------------------------------------------------------ the battery kind
+    def enable_battery(self, n_steps, interval_s=900, *, capacity_wh=None, charge_w=None, discharge_w=None, charge_eff=1.0,
+                       discharge_eff=1.0, standby_w=0.0, soc0_wh=0.0, step0=None, buffer=None, soc=None, params=None):
+        """enable_storage with losses and per-chain batteries (tmhpvsim_amd.battery): each chain's battery has
+        its own capacity, charge and discharge limits (at the meter side), charge and discharge efficiency
+        (floats in [0.5, 1]) and standby drain, each argument a scalar or [n]; a capacity of 0 is a household
+        without a battery.  Returns the raw int64 tensor [n_intervals, 10, n]: storage's nine columns
+        (charged and discharged at the meter side) and the loss.  `sim.soc` is the int64 state of charge [n],
+        `sim.battery_params` the int64 parameters [6, n] on the device (battery.quantize_params).  params: a
+        ready int64 device tensor [6, n] instead of the six quantities -- it may be a column slice of a
+        larger [6, N] one whose row stride is the table's ld (buffer a slice of [n_intervals, 10, N]), and
+        its values must lie in battery.RANGES (checked here; the kernels clamp).  soc0_wh must lie in
+        [0, capacity]; a caller's soc tensor is clamped into it by the first window.  buffer, soc, step0,
+        fp64 only, no traces, no fleet series, no other table, compaction: as enable_storage.  n_steps=None
+        switches the output off."""
+        torch = _torch()
+        if n_steps is None:
+            if self._battery is not None:   # (soc and the work buffer may be enable_storage's)
+                self.soc = self._storage_work = self._battery_desc = self.battery_params = None
+            return self._enable_table("battery", None, interval_s, step0, buffer)
+        if self.precision != _lib.TMH_FP64:
+            raise ValueError("the battery kind needs precision='fp64': an fp32 engine replaces its guard-band seconds "
+                             "after the expansion, and the state of charge depends on every earlier second")
+        from . import battery
+        if int(interval_s) > battery.MAX_INTERVAL_S:
+            raise ValueError(f"enable_battery: interval_s <= {battery.MAX_INTERVAL_S}")
+        if params is None:
+            if capacity_wh is None or charge_w is None or discharge_w is None:
+                raise ValueError("enable_battery: capacity_wh, charge_w and discharge_w (or params) are required")
+            host = battery.quantize_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w, n=self.n)
+            params = torch.from_numpy(host).to(self.device)
+        else:
+            if (params.dtype != torch.int64 or params.device != self.device or tuple(params.shape) != (6, self.n)
+                    or (self.n > 1 and params.stride(1) != 1)):
+                raise ValueError(f"battery params must be an int64 [6, {self.n}] tensor on {self.device}, chains contiguous")
+            host = battery.check_params(params)
+        if soc is None:
+            soc = torch.from_numpy(battery.quantize_soc(soc0_wh, host)).to(self.device)
+        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (self.n,)
+              or (self.n > 1 and soc.stride(0) != 1)):
+            raise ValueError(f"battery soc must be a contiguous int64 [{self.n}] tensor on {self.device}")
+        kept = self._storage_args
+        self._storage_args = (soc, params)
+        try:
+            raw = self._enable_table("battery", n_steps, interval_s, step0, buffer)
+        except Exception:   # (refused: what was enabled before stays as it was)
+            self._storage_args = kept
+            raise
+        self.soc, self.battery_params = soc, params
+        return raw
+
+    def _set_battery(self, table):
+        """tmh_set_battery with the table descriptor `table` (or None); the work buffer as _set_storage's.
+        The parameters' row stride must be the table's ld (one ld for both: tmh_battery)."""
+        if table is None:
+            return self.L.tmh_set_battery(self._eng, None)
+        torch = _torch()
+        soc, params = self._storage_args
+        if int(params.stride(0)) != int(table.ld):
+            raise ValueError(f"battery params row stride {int(params.stride(0))} != the table's ld {int(table.ld)}: "
+                             "slice both from tensors of the same width")
+        if self._storage_work is None:
+            nb = self.L.tmh_storage_work_bytes(self.n, min(int(table.n_steps), 86400))
+            self._storage_work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
+        work = self._storage_work
+        bt = _lib.Battery(table, soc.data_ptr(), work.data_ptr(), work.numel(), params.data_ptr())
+        rc = self.L.tmh_set_battery(self._eng, C.byref(bt))
+        if rc == 0:
+            self._battery_desc = bt
+        return rc
+
+    def battery(self):
+        """The battery table in watts and watt-hours (battery.to_watts of battery_raw): storage's keys plus
+        energy_wh_loss and round_trip, [n_intervals, n] each."""
+        return self._table_watts("battery")
 
     def guard_records(self):
         """Tests: the fp32 guard-band records (chain, 128-s block) of the last window that run()
@@ -514,7 +610,7 @@ class BatchedSim:
         res = out if out is not None else self._alloc(n_steps, trace)
         st = self._stats_struct()
         win = max(1, min(int(window), n_steps))
-        if self._storage is not None:
+        if self._storage is not None or self._battery is not None:
             self._storage_window(win)
         if compact and n_steps > win:
             with torch.cuda.device(self.device):
