@@ -34,7 +34,9 @@
  *    fp64 engines: the intervals' columns plus what the meter reads with a battery behind
  *    it, what the battery took and gave and its state of charge at each interval's end) or
  *    the battery kind (tmh_battery: the same with charge and discharge efficiency, a standby
- *    drain, a loss column and per-chain battery parameters).
+ *    drain, a loss column and per-chain battery parameters), and beside that kind's table the
+ *    battery fleet series (tmh_set_battery_fleet: per second, summed over the chains, what the
+ *    fleet draws, feeds in, stores and charges behind its batteries).
  *  - `stream` is a hipStream_t (NULL = default stream); all work is enqueued
  *    asynchronously on it.  One engine per device; not re-entrant per engine.
  */
@@ -323,6 +325,33 @@ typedef struct tmh_battery {
     const int64_t* params;    /* device [6][ld], ld = table.ld */
 } tmh_battery;
 
+/* The battery fleet series: the fleet series behind the batteries -- what the whole batch draws from
+ * the grid and feeds in second by second once the battery kind's batteries are in, and the energy the
+ * fleet holds at that second.  An output of the battery kind beside its interval table (never instead
+ * of it): the replay pass has every quantity of tmh_battery's per-second rule in a register and reduces
+ * it across the chains.  The descriptor is tmh_series with TMH_BATTERY_FLEET_COLS columns per row:
+ * sum is device int64 [n_groups][n_steps][8], accumulated over calls (the caller zero-initialises);
+ * row s of a group holds, for step step0 + s, over the group's chains that are ok at that step (the
+ * fleet series' rule and groups: chain i of a call in group i / group_chains, 0: one group, else a
+ * multiple of 512):
+ *   [0] sum of q(pv)   [1] sum of q(meter)   [2] n_ok   [3] ok chains with the covered bit
+ *       -- tmh_series' four columns, bit for bit what tmh_set_series gives for the same chains
+ *   [4] sum of import_b     what the fleet draws from the grid behind its batteries
+ *   [5] sum of export_b     what it feeds in
+ *   [6] sum of x'           the state of charge after the second, in 2^-12 W s
+ *   [7] sum of max(b, 0)    what the batteries take at the meter side
+ * with import_b, export_b, b and x' exactly tmh_battery's.  For every row [4] - [5] == [1] - [0] + sum
+ * of b, so the fleet's net battery power follows from the row and the discharging power is [7] - sum
+ * of b; columns 4-7 are >= 0; [6] <= the sum of C over the group.  A chain that is not ok at a second
+ * (faulted, or dead from construction) adds nothing to that row, its stored energy included.
+ * Bounds: b lies between 0 and d, so per chain export_b <= max(d, 0) <= q(pv) and max(b, 0) <= q(pv),
+ * below 2^26, and import_b <= max(-d, 0) <= q(meter) (+ |q(pv)| in a daylight second whose pv is the
+ * inverter's night tare), below 2^27: 32 lanes of each fit a 32-bit partial (the three are >= 0 and
+ * summed unsigned); x' < 2^40 does not and is reduced as two 20-bit halves (32 x 2^20 each).  Integer
+ * sums: the bits do not depend on block, wave, window, batch or pipelining order and equal a
+ * sequential loop over the traces. */
+#define TMH_BATTERY_FLEET_COLS 8
+
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
 /* TMH_SERIES_FRAC_BITS and TMH_SERIES_MAX_W as the library was built with them */
@@ -517,6 +546,20 @@ int tmh_set_storage(struct tmh_engine* eng, const tmh_storage* st);
  * (tmh_set_storage) set too, in either order.  The parameters' values are not read on the
  * host: the kernels clamp them. */
 int tmh_set_battery(struct tmh_engine* eng, const tmh_battery* bt);
+/* The battery fleet series (TMH_BATTERY_FLEET_COLS above): every later expansion of this engine with the
+ * battery kind set adds its window's rows to fleet->sum, in the kind's replay pass, beside the kind's
+ * table; NULL switches it off.  The descriptor is tmh_series with eight columns per row; a setter like
+ * tmh_set_series: the struct is copied, the buffer must outlive the launches, the rows are final after
+ * the TMH_EXPAND_KERNEL half.  Refused here (TMH_E_INVAL, the messages name "battery fleet"):
+ * tmh_set_series' bad-struct cases (no buffer, a misaligned one, n_steps or n_groups 0, group_chains not
+ * 0 with one group or a multiple of 512); an fp32 engine.  Refused at a step / expansion call or a walk
+ * of that window, before any launch and naming "battery fleet": no battery kind set (tmh_set_battery);
+ * battery storage set (tmh_set_storage, the lossless kind: use the battery kind with efficiencies 1);
+ * chain ids set (compaction: a tile would mix groups, as for the series); a window not inside [step0,
+ * step0 + n_steps); n_groups * group_chains < n_chains.  Everything tmh_set_battery's step refuses stays
+ * refused in its words, tmh_set_series beside the kind included.  Statistics and the histogram are
+ * accumulated beside both when tmh_stats gives them. */
+int tmh_set_battery_fleet(struct tmh_engine* eng, const tmh_series* fleet);
 /* Tests only: the fp32 guard-band records (chain, block) the last expansion on
  * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
  * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
@@ -627,7 +670,8 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * TMH_OUT_REGISTERS (import / export registers, with or without statistics),
  * TMH_OUT_DEMAND (demand registers, with or without statistics), TMH_OUT_STORAGE (battery
  * storage: the replay pass, the last of the kind's three launches, with or without statistics),
- * TMH_OUT_BATTERY (the battery kind, likewise), plus
+ * TMH_OUT_BATTERY (the battery kind, likewise), TMH_OUT_BATTERY_FLEET (the battery kind with its fleet
+ * series: the replay pass that fills both), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
@@ -639,6 +683,7 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
 #define TMH_OUT_DEMAND 6
 #define TMH_OUT_STORAGE 7
 #define TMH_OUT_BATTERY 8
+#define TMH_OUT_BATTERY_FLEET 9
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

@@ -3,7 +3,7 @@
 kernel) of the statistics-only expansion and of the expansions with a table, same chains,
 same window, same process, the runs alternating.
 
-    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery [--chains 65536] [--steps 86400]
+    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet [--chains 65536] [--steps 86400]
                                  [--interval 900] [--rounds 5] [--precision fp32]
                                  [--start "2019-09-05 00:00:00"] [--out FILE.json]
                                  [--modules 1 --capacity-wh 5000 --charge-w 2500 --discharge-w 2500]
@@ -24,6 +24,10 @@ The runs of a kind, each with the same statistics beside its table:
   battery:   OUT_STATS, OUT_STORAGE and OUT_BATTERY on an fp64 engine -- storage's setting with --charge-eff,
              --discharge-eff and --standby-w; the battery table's identities, a loss, and battery / storage for
              the whole expansion and for each of the three launches (the same TMH_K_STORAGE_* slots time both).
+  battery_fleet: OUT_BATTERY and OUT_BATTERY_FLEET, battery's setting -- the battery kind alone and with its
+             fleet series (BatchedSim.enable_battery_fleet, one group); the two tables are equal, the rows summed
+             over each interval are the table summed over the chains; fleet / battery for the whole expansion and
+             for each launch (the replay pass fills the rows), beside the spread of the kind's own rounds.
 The script checks each run's variant, these identities (on the warm-up round's tables), that
 the statistics of all runs agree bit for bit and that every table's ok seconds equal the
 histogram's count.  One warm-up round, then --rounds timed ones.  Prints one JSON line: the
@@ -47,6 +51,8 @@ RUNS = {
     "demand": (("stats_only", None), ("registers", "registers"), ("demand", "demand")),
     "storage": (("stats_only", None), ("registers", "registers"), ("storage", "storage")),
     "battery": (("stats_only", None), ("storage", "storage"), ("battery", "battery")),
+    # (the table of both runs is the battery kind's; "battery_fleet" also enables the battery fleet series)
+    "battery_fleet": (("battery", "battery"), ("battery_fleet", "battery")),
 }
 
 
@@ -79,6 +85,15 @@ def check_tables(kind, tables, interval_s):
         assert torch.equal(bt[:, 8] != 0, bt[:, 2] > 0) and int((bt[:, 8] >> 40).max()) <= interval_s
         assert int(bt[:, 9].sum()) > 0 and int(bt[:, 6].sum()) > 0 and int(bt[:, 7].sum()) > 0
         return int((bt[:, 5] > 0).sum())
+    if kind == "battery_fleet":   # the same table with and without the fleet series; the rows against it, per interval
+        bt, fb, fl = tables["battery"], tables["battery_fleet"], tables["fleet_rows"]
+        assert torch.equal(bt, fb) and bool((fl[..., 4:] >= 0).all())
+        per = fl[0].reshape(-1, interval_s, 8).sum(dim=1) if fl.shape[1] % interval_s == 0 else None
+        if per is not None:
+            for col, tcol in ((0, 0), (1, 1), (2, 2), (3, 3), (4, 4), (5, 5), (7, 6)):
+                assert torch.equal(per[:, col], bt[:, tcol].sum(dim=1)), (col, tcol)
+        assert int(fl[..., 6].sum()) > 0 and int(fl[..., 5].sum()) > 0
+        return int((bt[:, 5] > 0).sum())
     return None
 
 
@@ -100,7 +115,7 @@ def main():
     ap.add_argument("--discharge-eff", type=float, default=0.95)
     ap.add_argument("--standby-w", type=float, default=2.0)
     a = ap.parse_args()
-    if a.kind in ("storage", "battery"):
+    if a.kind in ("storage", "battery", "battery_fleet"):
         a.precision = "fp64"   # (the kind's engines)
     import torch
     from tmhpvsim_amd import _lib
@@ -128,28 +143,35 @@ def main():
     runs = RUNS[a.kind]
     labels = [label for label, _ in runs]
 
-    def one(table):
+    fleet_rows = {}
+
+    def one(table, label=None):
+        fleet = label == "battery_fleet"
         sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=mp, precision=a.precision,
                          device="cuda:0", horizon=a.steps)
         sim.enable_stats()
         raw = getattr(sim, "enable_" + table)(a.steps, a.interval, **enable_kw.get(table, {})) if table else None
+        if fleet:
+            fleet_rows["fleet_rows"] = sim.enable_battery_fleet(a.steps)
         _lib.check(sim.L.tmh_profile_enable(sim._eng, 1))
         sim.run(a.steps, trace=(), window=a.steps)
         torch.cuda.synchronize()
         ms, launches = _lib.profile_read(sim._eng, _lib.K_EXPAND)
-        want = out_of[table] | (_lib.OUT_FP64 if a.precision == "fp64" else 0)
+        want = (_lib.OUT_BATTERY_FLEET if fleet else out_of[table]) | (_lib.OUT_FP64 if a.precision == "fp64" else 0)
         assert launches == 1 and sim.L.tmh_engine_last_expand(sim._eng) == want, (launches, want)
         if table in ("storage", "battery"):   # its three launches, once each, inside the span read above
             for name, kk in parts:
                 pms, pn = _lib.profile_read(sim._eng, kk)
                 assert pn == 1
-                (part_ms if table == a.kind else below_ms)[name].append(pms)
+                (part_ms if (label or table) == a.kind else below_ms)[name].append(pms)
         if raw is not None:
             assert int(raw[:, 2].sum()) == int(sim.hist.sum()) > 0
         return ms, sim.hist.clone(), sim.chain_acc.clone(), raw
 
-    tables = {table: one(table)[3] for _, table in runs}   # warm-up: code objects, allocator
-    export_cells = check_tables(a.kind, tables, a.interval)
+    by_label = a.kind == "battery_fleet"   # (both of its runs fill the battery kind's table)
+    tables = {(label if by_label else table): one(table, label)[3] for label, table in runs}   # warm-up: code objects, allocator
+    export_cells = check_tables(a.kind, {**tables, **fleet_rows}, a.interval)
+    fleet_rows.clear()
     del tables
     for v in list(part_ms.values()) + list(below_ms.values()):
         v.clear()   # (the warm-up round's)
@@ -157,7 +179,7 @@ def main():
     ref = None
     for _ in range(a.rounds):
         for label, table in runs:
-            ms, hist, acc, _raw = one(table)
+            ms, hist, acc, _raw = one(table, label)
             t[label].append(ms)
             if ref is None:
                 ref = (hist, acc)
@@ -168,7 +190,18 @@ def main():
                precision=a.precision, start=a.start,
                **{f"{k}_ms": t[k] for k in labels}, **{f"{k}_median_ms": med[k] for k in labels},
                **{f"{k}_range_ms": [min(t[k]), max(t[k])] for k in labels})
-    if a.kind == "intervals":
+    if a.kind == "battery_fleet":   # the battery kind with its fleet series over the kind alone: the whole expansion
+        pmed = {name: statistics.median(v) for name, v in part_ms.items()}      # and each launch (the replay pass fills
+        bmed = {name: statistics.median(v) for name, v in below_ms.items()}     # the rows), beside the spread of the
+        res.update(rounds=a.rounds, export_cells=export_cells, modules=a.modules, battery=lossy, ns_per_chain_second=ns,
+                   **{f"battery_fleet_{k}_ms": v for k, v in part_ms.items()}, **{f"battery_{k}_ms": v for k, v in below_ms.items()},
+                   **{f"battery_fleet_{k}_median_ms": v for k, v in pmed.items()},
+                   **{f"battery_{k}_median_ms": v for k, v in bmed.items()},
+                   **{f"ratio_{k}_fleet_battery": pmed[k] / bmed[k] for k in pmed},
+                   ratio_fleet_battery=med["battery_fleet"] / med["battery"],
+                   battery_spread=max(t["battery"]) / min(t["battery"]),      # kind's own rounds
+                   battery_replay_spread=max(below_ms["replay"]) / min(below_ms["replay"]))
+    elif a.kind == "intervals":
         res.update(ratio=med["with_intervals"] / med["stats_only"], ns_per_chain_second=[ns[k] for k in labels])
     else:   # the kind over the statistics, the kind over the table below it, that table over the statistics
         below = labels[1]

@@ -99,7 +99,7 @@ EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_by
            "tmh_set_walk_chains_per_row", "tmh_set_walk_lanes", "tmh_set_chain_ids", "tmh_live_chains", "tmh_state_move",
            "tmh_stream_create_cus", "tmh_stream_destroy", "tmh_set_walk_order", "tmh_engine_last_expand",
            "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals",
-           "tmh_set_registers", "tmh_set_demand", "tmh_set_storage", "tmh_storage_work_bytes", "tmh_set_battery"]
+           "tmh_set_registers", "tmh_set_demand", "tmh_set_storage", "tmh_storage_work_bytes", "tmh_set_battery", "tmh_set_battery_fleet"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
 K_STORAGE_MAP, K_STORAGE_SCAN, K_STORAGE_REPLAY = 4, 5, 6   # battery storage's three launches (inside K_EXPAND)
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
@@ -111,6 +111,7 @@ OUT_REGISTERS = 5
 OUT_DEMAND = 6
 OUT_STORAGE = 7
 OUT_BATTERY = 8
+OUT_BATTERY_FLEET = 9   # the battery kind with its fleet series (tmh_set_battery_fleet)
 
 _lib = None
 
@@ -212,6 +213,8 @@ def load():
     L.tmh_set_storage.restype = C.c_int
     L.tmh_set_battery.argtypes = [p, C.POINTER(Battery)]
     L.tmh_set_battery.restype = C.c_int
+    L.tmh_set_battery_fleet.argtypes = [p, C.POINTER(Series)]   # (tmh_series with eight columns per row)
+    L.tmh_set_battery_fleet.restype = C.c_int
     L.tmh_storage_work_bytes.argtypes = [u32, u32]
     L.tmh_storage_work_bytes.restype = sz
     L.tmh_series_frac_bits.restype = C.c_int

@@ -34,6 +34,17 @@ is the interval's SoC change.  With ec = ed = 2^16 and sigma = 0 columns 0-8 and
 clamped addition (followed by the drain's): `second_maps` gives the per-second triples that
 storage.compose / storage.apply fold, as the engine's map pass and scan do.  `from_traces` is the
 contract as a plain loop over the seconds.
+
+The battery fleet series (BatchedSim.enable_battery_fleet after enable_battery, tmh_set_battery_fleet)
+is the same second summed over the chains instead of over an interval: an int64 tensor
+[n_groups, n_steps, 8] whose row of a second holds, over the group's chains that are ok at it,
+
+    [.., 0:4] the fleet series' columns (series.COLUMNS: pv, meter, n_ok, covered)
+    [.., 4]   sum of import_b      [.., 5] sum of export_b
+    [.., 6]   sum of x' (the state of charge after the second)      [.., 7] sum of max(b, 0)
+
+with [4] - [5] == [1] - [0] + sum of b in every row.  `fleet_from_traces` is that contract as the same
+loop over the seconds, `fleet_to_watts` its rows in W and Wh per bin.
 """
 from __future__ import annotations
 
@@ -45,6 +56,8 @@ from .storage import (HI, KEY_SHIFT, LO, MAX_CAPACITY, MAX_INTERVAL_S, MAX_POWER
                       unpack_soc)
 
 COLUMNS = storage.COLUMNS + ("loss",)
+# a row of the battery fleet series (tmh_set_battery_fleet): the fleet series' columns and the battery's four
+FLEET_COLUMNS = ("pv", "meter", "n_ok", "covered", "import", "export", "soc", "charge")
 PARAMS = ("capacity", "p_charge", "p_discharge", "eff_charge", "eff_discharge", "standby")   # the rows of params
 EFF_ONE, EFF_MIN = 1 << 16, 1 << 15
 # each row's inclusive range (tmh_battery)
@@ -120,6 +133,20 @@ def second_maps(pv, meter, covered, *, params):
     return np.where(ok, a, 0), np.where(ok, lo, LO).astype(np.int64), np.where(ok, hi, HI).astype(np.int64)
 
 
+def _second(x, d, params):
+    """One second of every chain: (b, x') of the SoC x before it and d = q(pv) - q(meter), as if the second
+    were ok (the caller keeps x where it is not)."""
+    cap, pc, pd, ec, ed, sb = params
+    a = np.clip(d, -pd, pc)
+    s = _stored(a, ec, _recip(ed))
+    x1 = np.clip(x + s, 0, cap)
+    g = x1 - x
+    fill = np.minimum(a, (g * _recip(ec) + 65535) >> 16)
+    drain = -np.minimum(-a, (-g * ed) >> 16)
+    b = np.where(g == s, a, np.where(g > 0, fill, np.where(g < 0, drain, 0)))
+    return b, np.maximum(x1 - sb, 0)
+
+
 def from_traces(pv, meter, covered, interval_s, *, params, soc0, origin=0):
     """The battery table of time-major traces [n_steps, n_chains] and the SoC after them: (int64
     [n_intervals, 10, n_chains], int64 [n_chains]).  A plain loop over the seconds, vectorised over the
@@ -134,23 +161,14 @@ def from_traces(pv, meter, covered, interval_s, *, params, soc0, origin=0):
     params = check_params(params)
     if params.shape[1] != n:
         raise ValueError(f"battery params for {params.shape[1]} chains, traces of {n}")
-    cap, pc, pd, ec, ed, sb = params
-    kc, kd = _recip(ec), _recip(ed)
     out = np.zeros((base.shape[0], len(COLUMNS), n), dtype=np.int64)
     out[:, :4] = base
-    x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (n,)), 0, cap)
+    x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (n,)), 0, params[0])
     ok, d_all = _ok_d(pv, meter, covered)
     for t in range(n_steps):
         k, o = divmod(origin + t, interval_s)
         oks, d = ok[t], d_all[t]
-        a = np.clip(d, -pd, pc)
-        s = _stored(a, ec, kd)
-        x1 = np.clip(x + s, 0, cap)
-        g = x1 - x
-        fill = np.minimum(a, (g * kc + 65535) >> 16)
-        drain = -np.minimum(-a, (-g * ed) >> 16)
-        b = np.where(g == s, a, np.where(g > 0, fill, np.where(g < 0, drain, 0)))
-        xn = np.maximum(x1 - sb, 0)
+        b, xn = _second(x, d, params)
         row = out[k]
         row[4] += np.where(oks, np.maximum(b - d, 0), 0)
         row[5] += np.where(oks, np.maximum(d - b, 0), 0)
@@ -160,6 +178,67 @@ def from_traces(pv, meter, covered, interval_s, *, params, soc0, origin=0):
         row[9] += np.where(oks, b - (xn - x), 0)
         x = np.where(oks, xn, x)
     return out, x
+
+
+def fleet_from_traces(pv, meter, covered, *, params, soc0, group_chains=0):
+    """The battery fleet series of time-major traces [n_steps, n_chains] and the SoC after them: (int64
+    [n_groups, n_steps, 8], int64 [n_chains]).  The same loop over the seconds as from_traces, summed over the
+    chains of a group instead of the seconds of an interval: row t of a group holds, over its chains that are
+    ok at second t, FLEET_COLUMNS -- series.from_traces' four columns, the sums of import_b and export_b, of
+    the SoC x' after the second and of max(b, 0).  params, soc0: as from_traces; groups as series.from_traces
+    (chain i in group i // group_chains, 0: one group, else a multiple of 512; the last may be partial)."""
+    from . import series
+    pv, meter, covered = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (pv, meter, covered))
+    base = series.from_traces(pv, meter, covered, group_chains)                   # (checks the arguments)
+    n_steps, n = pv.shape
+    params = check_params(params)
+    if params.shape[1] != n:
+        raise ValueError(f"battery params for {params.shape[1]} chains, traces of {n}")
+    n_groups = base.shape[0]
+    gc = int(group_chains) or max(n, 1)
+    out = np.zeros((n_groups, n_steps, len(FLEET_COLUMNS)), dtype=np.int64)
+    out[..., :4] = base
+    x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (n,)), 0, params[0])
+    ok, d_all = _ok_d(pv, meter, covered)
+    for t in range(n_steps):
+        oks, d = ok[t], d_all[t]
+        b, xn = _second(x, d, params)
+        x = np.where(oks, xn, x)
+        cols = np.stack([np.maximum(b - d, 0), np.maximum(d - b, 0), x, np.maximum(b, 0)])
+        cols = np.where(oks, cols, 0)
+        for g in range(n_groups):
+            out[g, t, 4:] = cols[:, g * gc:(g + 1) * gc].sum(axis=1)
+    return out, x
+
+
+def fleet_to_watts(raw, bin_s=1, mean=False):
+    """float64 series of a raw battery fleet table [..., n_steps, 8]: dict of pv, meter, import_w, export_w,
+    charge_w, discharge_w (W) and soc_wh (Wh) -- fleet sums, or with mean=True the means per ok chain-second
+    -- n_ok (ok chain-seconds per bin) and covered (the fraction of them under cloud), each [..., n_bins].
+    Bins of bin_s seconds are summed as integers first, as series.to_watts does; the state of charge of a bin
+    is its seconds' mean (of the fleet's total, or per ok chain-second); a last partial bin is kept; a bin
+    without an ok chain-second gives NaN.  The discharging power is [7] - sum of b with sum of b = [4] - [5] -
+    ([1] - [0]), the row's identity."""
+    raw = np.asarray(raw.cpu() if hasattr(raw, "cpu") else raw).astype(np.int64, copy=False)
+    if raw.ndim < 2 or raw.shape[-1] != len(FLEET_COLUMNS):
+        raise ValueError("raw battery fleet series must end in the 8 columns")
+    bin_s = int(bin_s)
+    if bin_s < 1:
+        raise ValueError("bin_s must be >= 1")
+    n_steps = raw.shape[-2]
+    secs = np.ones(n_steps, dtype=np.int64)
+    if bin_s > 1 and n_steps:
+        edges = np.arange(0, n_steps, bin_s)
+        raw, secs = np.add.reduceat(raw, edges, axis=-2), np.add.reduceat(secs, edges)
+    n_ok = raw[..., 2]
+    den = np.where(n_ok > 0, n_ok, np.nan).astype(np.float64)
+    scale = float(1 << FRAC_BITS)
+    div = den * scale if mean else np.where(n_ok > 0, scale, np.nan)
+    dis = raw[..., 7] - (raw[..., 4] - raw[..., 5] - (raw[..., 1] - raw[..., 0]))
+    return {"pv": raw[..., 0] / div, "meter": raw[..., 1] / div, "import_w": raw[..., 4] / div,
+            "export_w": raw[..., 5] / div, "charge_w": raw[..., 7] / div, "discharge_w": dis / div,
+            "soc_wh": raw[..., 6] / ((div if mean else div * secs) * 3600.0),
+            "n_ok": n_ok.astype(np.float64), "covered": raw[..., 3] / den}
 
 
 def to_registers(raw):

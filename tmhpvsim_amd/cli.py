@@ -23,7 +23,7 @@ tmhpvsim/metersim.py:79-95).
     python -m tmhpvsim_amd.cli battery FILE --batch N --no-realtime --interval S --capacity-wh X[,X..] --charge-w P[,P..]
                                             --discharge-w P[,P..] [--charge-eff E[,E..]] [--discharge-eff E[,E..]]
                                             [--standby-w P[,P..]] [--soc0-wh X[,X..]] [--all-chains NPZ]
-                                            [--start T --seconds S --seed K]
+                                            [--fleet CSV [--bin S]] [--start T --seconds S --seed K]
 
 Without --batch the commands are the reference's AMQP pipelines (a fanout
 exchange carrying one JSON float per second, pvsim.py:43-84, metersim.py:13-62):
@@ -71,7 +71,10 @@ discharge efficiency in [0.5, 1], a standby drain in W).  Each battery option ta
 comma-separated list dealt to the chains round-robin (chain i gets value i mod the list's length):
 a fleet of different batteries, or a sweep of sizes across otherwise equal scenarios in one run.
 The CSV is `storage`'s with `loss_wh` (conversion and standby losses) before `n_ok`; --all-chains
-writes every chain's raw table and its arrays to an .npz.
+writes every chain's raw table and its arrays to an .npz.  --fleet CSV also writes the battery fleet series
+(tmhpvsim_amd.battery.fleet_to_watts: what the whole batch does second by second behind its batteries) as means
+per ok chain-second over bins of --bin seconds: header `time,n_ok,meter,pv,import_w,export_w,charge_w,discharge_w,
+soc_wh,covered`; without it the command's outputs are as before, byte for byte.
 There is no CPU fallback: the batch mode fails if the engine cannot run.
 """
 from __future__ import annotations
@@ -122,9 +125,10 @@ def _fleet_run(n, start, seconds, seed, precision, bin_s):
     return {k: v[0] for k, v in out.items()}
 
 
-def _table_run(kind, n, start, seconds, seed, precision, interval_s, **enable_kw):
+def _table_run(kind, n, start, seconds, seed, precision, interval_s, fleet_bin=None, **enable_kw):
     """An engine run with the interval table `kind` ("intervals", "registers", "demand", "storage" or "battery")
-    only: the raw table and its watt / watt-hour arrays.  enable_kw: the kind's own arguments."""
+    only: the raw table, its watt / watt-hour arrays and, with fleet_bin (the battery kind), the battery fleet
+    series' means per bin of fleet_bin seconds (else None).  enable_kw: the kind's own arguments."""
     from .engine import BatchedSim
     from .params import ModelParams
     import torch
@@ -134,13 +138,16 @@ def _table_run(kind, n, start, seconds, seed, precision, interval_s, **enable_kw
     sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
                      horizon=int(seconds))
     raw = getattr(sim, "enable_" + kind)(int(seconds), int(interval_s), **enable_kw)
+    if fleet_bin:
+        sim.enable_battery_fleet(int(seconds))
     sim.run(int(seconds), trace=())
     out = getattr(sim, kind)()
+    fleet = {k: v[0] for k, v in sim.battery_fleet(bin_s=int(fleet_bin), mean=True).items()} if fleet_bin else None
     bad = int((sim.status() != 0).sum())
     if bad:
         logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their "
                        f"{'intervals' if kind == 'intervals' else 'registers'} hold the seconds before the fault")
-    return raw.cpu().numpy(), out
+    return raw.cpu().numpy(), out, fleet
 
 
 def _times(start, seconds):
@@ -262,10 +269,17 @@ TABLE_CSV = {
 }
 
 
-def _table_command(kind, file, batch, start, seconds, seed, precision, interval_s, all_chains, **enable_kw):
+# the battery fleet series' CSV columns: (header, key of battery.fleet_to_watts)
+FLEET_CSV = (("n_ok", "n_ok"), ("meter", "meter"), ("pv", "pv"), ("import_w", "import_w"), ("export_w", "export_w"),
+             ("charge_w", "charge_w"), ("discharge_w", "discharge_w"), ("soc_wh", "soc_wh"), ("covered", "covered"))
+
+
+def _table_command(kind, file, batch, start, seconds, seed, precision, interval_s, all_chains, fleet=None, bin_s=1,
+                   **enable_kw):
     """The `intervals`, `registers`, `demand`, `storage` and `battery` commands: chain 0's rows to FILE, every chain
-    to the .npz."""
-    raw, out = _table_run(kind, batch, start, seconds, seed, precision, interval_s, **enable_kw)
+    to the .npz; with `fleet` (the battery command's --fleet) the battery fleet series' means per bin to that CSV."""
+    raw, out, fl = _table_run(kind, batch, start, seconds, seed, precision, interval_s,
+                              fleet_bin=bin_s if fleet else None, **enable_kw)
     t0 = dt.datetime.fromisoformat(str(start))
     rows = raw.shape[0]
     with open(file, mode="w", newline="") as fh:
@@ -276,7 +290,14 @@ def _table_command(kind, file, batch, start, seconds, seed, precision, interval_
     if all_chains:
         import numpy as np
         np.savez(all_chains, raw=raw, interval_s=interval_s, **out)
-    click.echo(f"wrote {rows} rows to {file}" + (f" and {batch} chains to {all_chains}" if all_chains else ""))
+    if fleet:
+        with open(fleet, mode="w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(["time"] + [name for name, _ in FLEET_CSV])
+            for i in range(len(fl["n_ok"])):
+                w.writerow([t0 + dt.timedelta(seconds=i * bin_s)] + [float(fl[key][i]) for _, key in FLEET_CSV])
+    click.echo(f"wrote {rows} rows to {file}" + (f" and {batch} chains to {all_chains}" if all_chains else "")
+               + (f" and {len(fl['n_ok'])} fleet rows to {fleet}" if fleet else ""))
 
 
 def table_options(f):
@@ -367,13 +388,15 @@ def _deal(vals, n):
 @click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]")
 @click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)")
 @click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)")
+@click.option("--fleet", default=None, help="also write the battery fleet series' means per bin to this CSV")
+@click.option("--bin", "bin_s", type=click.IntRange(min=1), default=1, help="--fleet: seconds per row (a last partial bin is kept)")
 def battery(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
-            charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh):
+            charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh, fleet, bin_s):
     """Battery storage with losses of chain 0 over --batch chains to FILE (CSV; battery-only fp64 engine run)."""
     logging.basicConfig(level=logging.WARN - 10 * verbose)
     _need_batch(realtime, batch, "battery")
     try:
-        _table_command("battery", file, batch, start, seconds, seed, "fp64", interval_s, all_chains,
+        _table_command("battery", file, batch, start, seconds, seed, "fp64", interval_s, all_chains, fleet=fleet, bin_s=bin_s,
                        **{k: _deal(v, batch) for k, v in dict(
                            capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
                            discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh).items()})

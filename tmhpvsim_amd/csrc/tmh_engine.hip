@@ -2110,6 +2110,89 @@ __device__ __forceinline__ void series_flush(SeriesLds* sl, const SeriesView& se
     __syncthreads();
 }
 
+// The battery fleet series' workgroup staging (OUT_FLEET only; function-local as SeriesLds): every half-wave's
+// 32-bit partial sums of the seconds of half a tile.  A (half-wave, second) slot is written exactly once between two
+// flushes, by the half's last lane, so the per-second loop issues two plain 16-byte LDS stores and no atomic, and
+// nothing needs zeroing.  The tile flushes twice (fleet_flush): once at the first group boundary at or past its
+// 64th second -- at most FLEET_SLOTS = 64 + 3 + 1 seconds, a four-second group being entered below 64 -- and at
+// its end (at most 64 seconds more), each time adding the halves' partials per value.  HALVES x 2,176 B: 17 KB for a
+// replay workgroup, so that three workgroups per CU (EXP_WAVES_LOSSY) keep their LDS with a histogram of up to
+// about 10,000 bins beside them (the launch's dynamic LDS, two bytes per bin; the default has 4,096).
+constexpr int FLEET_PARTS = 8;   // q(pv), q(meter), import_b, export_b, x' low, x' high, max(b, 0), counts
+constexpr int FLEET_HALF = BLOCK_STEPS / 2, FLEET_SLOTS = FLEET_HALF + 4;
+template <int HALVES>
+struct FleetLds {
+    __attribute__((aligned(16))) uint32_t part[HALVES][FLEET_SLOTS][FLEET_PARTS];
+};
+template <bool ON, int HALVES>
+__device__ __forceinline__ FleetLds<HALVES>* fleet_lds()
+{
+    if constexpr (ON) {
+        __shared__ FleetLds<HALVES> s;
+        return &s;
+    } else {
+        return nullptr;
+    }
+}
+// One second's contribution of a wave to slot `slot` (the second's place since the last flush), every argument 0 on lanes that are not ok: q(pv) and q(meter)
+// (signed partials, |q| < 2^26), import_b, export_b and max(b, 0) (unsigned partials, each < 2^27) and the state
+// of charge x after the second (< 2^40) as two halves of FLEET_SOC_HALF bits; nok, ncov: the wave's counts
+// (scalars), kept in the upper half-wave's slot.  PV = false: a night second, pv the literal 0 -- then d =
+// -q(meter) <= 0, the battery can only give (d <= b <= 0), and export_b and max(b, 0) are 0 as well: three
+// reductions fewer.
+template <bool PV, int HALVES>
+__device__ __forceinline__ void fleet_add(FleetLds<HALVES>* fl, uint32_t slot, int qpv, int qm, uint32_t im, uint32_t ex,
+                                          uint32_t ch, long long x, uint32_t nok, uint32_t ncov)
+{
+    const int sm = half_wave_sum(qm);
+    const uint32_t si = half_wave_sum_u(im);
+    const uint32_t xl = half_wave_sum_u((uint32_t)x & ((1u << FLEET_SOC_HALF) - 1u));
+    const uint32_t xh = half_wave_sum_u((uint32_t)((unsigned long long)x >> FLEET_SOC_HALF));
+    int sp = 0;
+    uint32_t se = 0, sc = 0;
+    if constexpr (PV) {
+        sp = half_wave_sum(qpv);
+        se = half_wave_sum_u(ex);
+        sc = half_wave_sum_u(ch);
+    }
+    if ((threadIdx.x & 31u) == 31u) {   // (threadIdx.x >> 5 < HALVES: the workgroup's size)
+        uint4* p = reinterpret_cast<uint4*>(fl->part[threadIdx.x >> 5][slot]);
+        p[0] = make_uint4((uint32_t)sp, (uint32_t)sm, si, se);
+        p[1] = make_uint4(xl, xh, sc, (threadIdx.x & 32u) ? (nok | ncov << 16) : 0u);
+    }
+}
+// Slots [0, j1 - j0) as the window's rows [j0, j1) of group g into the device table, as series_flush: rows of
+// TMH_BATTERY_FLEET_COLS int64, consecutive steps contiguous, zeros skipped; each value is the sum of the halves'
+// partials (q(pv) and q(meter) sign-extended, the state of charge put together from its two halves).  Every thread
+// of the workgroup calls it, at the same seconds (the tile's sequence of seconds is the workgroup's).
+template <int WGT>
+__device__ __forceinline__ void fleet_flush(const FleetLds<WGT / 32>* fl, const SeriesView& se, uint32_t g, uint32_t j0,
+                                            uint32_t j1)
+{
+    constexpr uint32_t FC = TMH_BATTERY_FLEET_COLS;
+    static_assert(FC == 8, "rows of eight: the series' four columns and the battery's four");
+    __syncthreads();   // the waves' last stores
+    unsigned long long* dst = se.sum + (size_t)g * se.gstride + (size_t)j0 * FC;
+    const uint32_t nv = (j1 - j0) * FC;
+    for (uint32_t i = threadIdx.x; i < nv; i += WGT) {
+        const uint32_t row = i >> 3, col = i & 7u;
+        unsigned long long v = 0;
+        for (int h = 0; h < WGT / 32; ++h) {
+            const uint32_t* p = fl->part[h][row];
+            v += col == 0   ? (unsigned long long)(long long)(int)p[0]
+                 : col == 1 ? (unsigned long long)(long long)(int)p[1]
+                 : col == 2 ? (unsigned long long)(p[7] & 0xFFFFu)
+                 : col == 3 ? (unsigned long long)(p[7] >> 16)
+                 : col == 4 ? (unsigned long long)p[2]
+                 : col == 5 ? (unsigned long long)p[3]
+                 : col == 6 ? (unsigned long long)p[4] + ((unsigned long long)p[5] << FLEET_SOC_HALF)
+                            : (unsigned long long)p[6];
+        }
+        if (v) atomicAdd(dst + i, v);
+    }
+    __syncthreads();   // (the seconds that follow overwrite the slots)
+}
+
 // One (128-second block b, chain block cblk) tile of the expansion: one work-item per
 // chain of the block (the expansion's unit of work, below).  The LDS staging areas are
 // the kernel's (one column per thread, so consecutive tiles need no barrier between them).
@@ -2128,7 +2211,8 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                             uint32_t (*cov_lds)[WGT], R (*min_lds)[WGT], uint4* held_lds,
                                             const PV64* pv_lds, const double* pv_lds_tab,
                                             const float4* nd_lds, const SeriesView& se, SeriesLds* ser_lds,
-                                            const IntervalsView& ivv, const StorageView& sto, const long long* batp)
+                                            const IntervalsView& ivv, const StorageView& sto, const long long* batp,
+                                            FleetLds<WGT / 32>* flt_lds)
 {
     constexpr bool SER = out_base(OUT) == OUT_SERIES;
     // Battery storage (fp64 only), two passes over the same per-second body:
@@ -2144,6 +2228,12 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // lane-consecutive rows), what the ask stores or drains in place of the ask, the standby drain after it,
     // and in the replay one accumulator and one column more (IVC = 10)
     constexpr bool BAT = STO && (OUT & OUT_LOSSY) != 0;
+    // FLT: the battery fleet series beside the battery kind's table, in its replay pass -- the second's q(pv),
+    // q(meter), import_b, export_b, max(b, 0) and the state of charge after it, reduced across each half-wave and
+    // added to the workgroup's row of the second (fleet_add); the tile's rows go to the device table at its end
+    // (fleet_flush; `se` views it, rows of TMH_BATTERY_FLEET_COLS)
+    constexpr bool FLT = (OUT & OUT_FLEET) != 0;
+    static_assert(!FLT || (BAT && REP), "the battery fleet series: a flag of the battery kind's replay pass only");
     static_assert(!STO || sizeof(R) == 8, "battery storage: fp64 engines only (no guard-band seconds)");
     // REG: the import / export registers -- the intervals' pieces, accumulators and flush, with
     // one more accumulator and IVC = 6 columns per cell instead of 4
@@ -2351,6 +2441,19 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         if (live) sx = sto.work[(size_t)b * 3 * n + c];
         sx0 = sx;
     }
+    // FLT: the block-relative second of the last flush (slot of a second = jb - flt_base) and the group
+    uint32_t flt_base = 0;
+    const uint32_t flt_g = FLT && se.group_chains ? cblk * (uint32_t)WGT / se.group_chains : 0u;   // (512 is a multiple of WGT)
+    // the mid-tile flush, asked before each second or four-second group that starts at j: once, at the first such
+    // start at or past the tile's 64th second (wave-uniform and the same in every wave of the workgroup)
+    auto flt_mid = [&](uint32_t j) __attribute__((always_inline)) {
+        if constexpr (FLT) {
+            if (flt_base == 0 && j - j0 >= (uint32_t)FLEET_HALF) {
+                fleet_flush<WGT>(flt_lds, se, flt_g, j0, j);
+                flt_base = j - j0;
+            }
+        }
+    };
     uint32_t iv_k = 0, iv_next = j1;
     if constexpr (IVL) {
         iv_k = __builtin_amdgcn_readfirstlane((ivv.rel0 + j0) / ivv.interval_s);
@@ -2475,6 +2578,20 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                     iv_ex += (long long)(ok ? max(d - bm, 0) : 0);
                     st_ch += (long long)(ok ? max(bm, 0) : 0);
                     st_dis += (long long)(ok ? max(-bm, 0) : 0);
+                    if constexpr (FLT) {
+                        // the second's row of the battery fleet series, as the series' (SER above): sums by wave
+                        // reduction, counts by ballot; sx after the update, 0 on lanes that are not ok
+                        const bool okl = ok && live;
+                        const uint32_t nok = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(okl));
+                        const uint32_t ncov = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(okl && covered));
+                        const uint32_t im = (uint32_t)(okl ? max(bm - d, 0) : 0);
+                        const long long xs = okl ? sx : 0ll;
+                        if (__builtin_constant_p(pv) && pv == R(0))
+                            fleet_add<false, WGT / 32>(flt_lds, jb - flt_base, 0, okl ? qm : 0, im, 0u, 0u, xs, nok, ncov);
+                        else
+                            fleet_add<true, WGT / 32>(flt_lds, jb - flt_base, okl ? qp : 0, okl ? qm : 0, im, (uint32_t)(okl ? max(d - bm, 0) : 0),
+                                            (uint32_t)(okl ? max(bm, 0) : 0), xs, nok, ncov);
+                    }
                 }
             } else if constexpr (MAP) {
                 const SocMap f = soc_compose(st_map, SocMap{a, 0, sto.cap});
@@ -2602,7 +2719,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         for (int q = 0; q < 4; ++q) {
             const R meter = meter_w<R>(w[q]);
             // (the covered bit is an output of the series only: its count column)
-            const bool covered = SER && ((cov_w >> ((j + q - j0) & 31)) & 1u);
+            const bool covered = (SER || FLT) && ((cov_w >> ((j + q - j0) & 31)) & 1u);
             finish(j + q, j + q - j0, covered, R(0), R(0), meter, meter, false, ff);
         }
     };
@@ -2655,6 +2772,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             if (((W0 + j0) & 3) == 0) {
                 if constexpr (IVL) {   // a piece that starts inside a four-second group: single seconds up to the grid
                     for (; j < je && (j & 3u); ++j) {
+                        flt_mid(j);
                         const uint64_t g = (uint64_t)(W0 + j) >> 2;
                         const uint32_t q = (uint32_t)(W0 + j) & 3u;
                         second(j, word_of(keyed_block(kp.seed, chain, g, TAG_NOISE4, 0), q),
@@ -2662,6 +2780,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                     }
                 }
                 for (; j + 4 <= je; j += 4) {
+                    flt_mid(j);
                     const uint64_t g = (uint64_t)(W0 + j) >> 2;
                     TMH_MARK("meter begin");
                     const U4 pm = keyed_block(kp.seed, chain, g, TAG_METER4, 0);
@@ -2708,6 +2827,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 }
             }
             for (; j < je; ++j) {   // a window start off the four-step grid, or a short last block or piece (rare)
+                flt_mid(j);
                 const uint64_t g = (uint64_t)(W0 + j) >> 2;
                 const uint32_t q = (uint32_t)(W0 + j) & 3u;
                 second(j, word_of(keyed_block(kp.seed, chain, g, TAG_NOISE4, 0), q),
@@ -2753,6 +2873,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     }
     if constexpr (SER)   // (group_chains is a multiple of the workgroup's chains: one group per tile)
         series_flush<WGT>(ser_lds, se, se.group_chains ? cblk * (uint32_t)WGT / se.group_chains : 0u, j0, j1);
+    if constexpr (FLT) fleet_flush<WGT>(flt_lds, se, flt_g, j0 + flt_base, j1);   // the seconds since the mid-tile flush
 }
 
 
@@ -2767,7 +2888,8 @@ using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView,
                                                           out_base(OUT) == OUT_DEMAND,
                                                       IntervalsView,
                                                       std::conditional_t<out_base(OUT) == OUT_STORAGE,
-                                                                         std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>,
+                                                                         std::conditional_t<(OUT & OUT_FLEET) != 0, BatteryFleetView,
+                                                                                            std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>>,
                                                                          TraceView>>>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
@@ -2790,7 +2912,12 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     if constexpr (out_base(OUT) == OUT_SERIES) se = ov;
     else if constexpr (out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS || out_base(OUT) == OUT_DEMAND)
         ivv = ov;
-    else if constexpr (out_base(OUT) == OUT_STORAGE && (OUT & OUT_LOSSY) != 0) {   // the battery kind: storage's view + the parameters
+    else if constexpr ((OUT & OUT_FLEET) != 0) {   // the battery kind with its fleet series: the kind's view + the series'
+        sto = ov.bt.st;
+        ivv = ov.bt.st.iv;
+        batp = ov.bt.params;
+        se = ov.se;
+    } else if constexpr (out_base(OUT) == OUT_STORAGE && (OUT & OUT_LOSSY) != 0) {   // the battery kind: storage's view + the parameters
         sto = ov.st;
         ivv = ov.st.iv;
         batp = ov.params;
@@ -2808,6 +2935,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     }
     extern __shared__ uint32_t lds_hist[];
     constexpr int WGT = exp_wg<R, OUT, SITES>();   // threads per workgroup
+    FleetLds<WGT / 32>* const flt_lds = fleet_lds<(OUT & OUT_FLEET) != 0, WGT / 32>();   // (written before it is read: no zeroing)
     __shared__ uint32_t cov_lds[4][WGT];
     __shared__ R min_lds[4][WGT];   // minute boundaries mA, mA + 1 of the block: cloudy, clear noise
     __shared__ uint4 held_lds[WGT];
@@ -2821,7 +2949,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     auto tile = [&](uint32_t b, uint32_t cblk, auto night) __attribute__((always_inline)) {
         expand_tile<R, OUT, SITES, WGT, decltype(night)::value>(
             b, cblk, kp, dp, st, chain0, n, W0, nsteps, utc0, tab64, tab32, sun, events, n_events, desc, sg, tr, sv,
-            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv, sto, batp);
+            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv, sto, batp, flt_lds);
     };
     // the workgroup's LDS histogram into the device histogram
     auto hist_flush = [&]() __attribute__((always_inline)) {
@@ -3498,6 +3626,7 @@ constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
     {TMH_BATTERY_COLS, TMH_OUT_BATTERY, "battery tables", "the battery kind"},
 };
 static_assert(TMH_OUT_BATTERY > out_base(~0) && TMH_OUT_BATTERY < TMH_OUT_SITES, "TMH_OUT_BATTERY: a code of its own below the flags");
+static_assert(TMH_OUT_BATTERY_FLEET > TMH_OUT_BATTERY && TMH_OUT_BATTERY_FLEET < TMH_OUT_SITES, "TMH_OUT_BATTERY_FLEET: likewise");
 static_assert(interval_cols(OUT_INTERVALS) == TABLE_KINDS[TBL_INTERVALS].cols &&
                   interval_cols(OUT_REGISTERS) == TABLE_KINDS[TBL_REGISTERS].cols &&
                   interval_cols(OUT_DEMAND) == TABLE_KINDS[TBL_DEMAND].cols &&
@@ -3528,6 +3657,8 @@ struct tmh_engine {
     } tables[TBL_KINDS];
     tmh_storage storage{};   // tmh_set_storage: the battery, soc and the work buffer beside tables[TBL_STORAGE]
     tmh_battery battery{};   // tmh_set_battery: soc, the work buffer and the parameters beside tables[TBL_BATTERY]
+    bool has_fleet = false;  // tmh_set_battery_fleet: the battery kind's replay pass adds its window to `fleet` too
+    tmh_series fleet{};
     // the first set kind (TBL_KINDS: none); a step is refused unless it is the only one (check_interval_tables)
     int table_kind() const
     {
@@ -4061,6 +4192,47 @@ int tmh_set_battery(struct tmh_engine* eng, const tmh_battery* bt)
     return TMH_OK;
 }
 
+// the battery fleet series: tmh_set_series' struct cases in its own words (the struct first, as the tables'
+// setters: a bad one is named whatever the engine), and the battery kind's engines only
+int tmh_set_battery_fleet(struct tmh_engine* eng, const tmh_series* fleet)
+{
+    if (fleet) {
+        if (!fleet->sum || fleet->n_steps == 0 || fleet->n_groups == 0)
+            return fail(TMH_E_INVAL, "battery fleet series needs a buffer, n_steps > 0 and n_groups > 0");
+        if ((uintptr_t)fleet->sum & 7) return fail(TMH_E_INVAL, "battery fleet series buffer must be 8-byte aligned");
+        if (fleet->group_chains % 512 != 0 || (fleet->group_chains == 0 && fleet->n_groups != 1))
+            return fail(TMH_E_INVAL, "battery fleet series group_chains %u (x %u groups): 0 with one group, or a multiple of 512",
+                        fleet->group_chains, fleet->n_groups);
+    }
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (fleet && eng->kp.precision != TMH_FP64)   // (as tmh_set_battery)
+        return fail(TMH_E_INVAL, "a battery fleet series needs an fp64 engine, as the battery kind whose replay pass fills it");
+    eng->has_fleet = fleet != nullptr;
+    eng->fleet = fleet ? *fleet : tmh_series{};
+    return TMH_OK;
+}
+
+// A step / expansion with a battery fleet series set, after check_series and check_interval_tables (what they
+// refuse stays refused in their words): what the replay pass's rows assume, before any launch.
+static int check_battery_fleet(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps)
+{
+    if (!eng->has_fleet) return TMH_OK;
+    const tmh_series& fl = eng->fleet;
+    if (eng->tables[TBL_STORAGE].set)
+        return fail(TMH_E_INVAL, "a battery fleet series cannot run beside battery storage (tmh_set_storage, the lossless "
+                                 "kind): use the battery kind with efficiencies 1");
+    if (eng->table_kind() != TBL_BATTERY)
+        return fail(TMH_E_INVAL, "a battery fleet series needs the battery kind set (tmh_set_battery): its replay pass fills it");
+    if (eng->kp.ids) return fail(TMH_E_INVAL, "a battery fleet series cannot run on compacted chains (tmh_set_chain_ids)");
+    if (step0 < fl.step0 || step0 + (int64_t)n_steps > fl.step0 + (int64_t)fl.n_steps)
+        return fail(TMH_E_INVAL, "window [%lld, +%u) outside the battery fleet series [%lld, +%u)", (long long)step0, n_steps,
+                    (long long)fl.step0, fl.n_steps);
+    if (fl.group_chains && (uint64_t)fl.n_groups * fl.group_chains < n_chains)
+        return fail(TMH_E_INVAL, "battery fleet series of %u groups x %u chains < n_chains %u", fl.n_groups, fl.group_chains,
+                    n_chains);
+    return TMH_OK;
+}
+
 // A step / expansion with an interval table set (nothing to check without one): everything the
 // kernels assume, checked on the host before any launch (tmhpvsim.h, tmh_set_intervals,
 // tmh_set_registers, tmh_set_demand).  The messages name the first set kind; with two kinds set
@@ -4472,7 +4644,13 @@ static int phase_expand(const StepCtx& c)
                                        reinterpret_cast<long long*>(bb.soc), params, eng->kp.ids, c.n_chains, c.sg.nblk);
                     eng->close(TMH_K_STORAGE_SCAN, t, c.s);
                     t = eng->mark(c.s);
-                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY>{}, st, btv, sv);
+                    if (eng->has_fleet) {   // the battery fleet series beside the table: the replay pass's OUT_FLEET instantiation
+                        launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_FLEET>{}, st,
+                               BatteryFleetView{btv, c.sev}, sv);
+                        out = TMH_OUT_BATTERY_FLEET;
+                    } else {
+                        launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY>{}, st, btv, sv);
+                    }
                     eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
                 }
             } else if (table != TBL_KINDS) {
@@ -4555,6 +4733,7 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     if (series)
         if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
     if (int rc = check_interval_tables(eng, n_chains, step0, n_steps, trace)) return rc;   // (a walk of a refused window is refused too)
+    if (int rc = check_battery_fleet(eng, n_chains, step0, n_steps)) return rc;
     const bool tp = eng->path == TMH_PATH_TIME_PARALLEL;
     if (tp && (!scratch || scratch_bytes < tmh_engine_scratch_bytes(eng, n_chains, n_steps)))
         return fail(TMH_E_INVAL, "scratch too small: %zu < %zu", scratch_bytes, tmh_engine_scratch_bytes(eng, n_chains, n_steps));
@@ -4582,6 +4761,10 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     if (series)   // the window's first row of group 0
         c.sev = SeriesView{reinterpret_cast<unsigned long long*>(eng->series.sum) + (size_t)(step0 - eng->series.step0) * 4,
                            (uint64_t)eng->series.n_steps * 4, eng->series.group_chains, 0u};
+    else if (eng->has_fleet)   // (never beside a series: check_interval_tables) the battery fleet series' rows of eight
+        c.sev = SeriesView{reinterpret_cast<unsigned long long*>(eng->fleet.sum) +
+                               (size_t)(step0 - eng->fleet.step0) * TMH_BATTERY_FLEET_COLS,
+                           (uint64_t)eng->fleet.n_steps * TMH_BATTERY_FLEET_COLS, eng->fleet.group_chains, 0u};
     if (c.table() != TBL_KINDS) {   // the whole table; the window's first step from its origin (the cells' columns:
         const tmh_intervals& t = eng->tables[c.table()].t;   // the kernels' compile-time constant)
         c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(t.sum), t.ld, (uint32_t)(step0 - t.step0), t.interval_s};
@@ -4681,6 +4864,7 @@ int tmh_run(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_cha
     if (eng->has_series)   // before the plan's launches
         if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
     if (int rc = check_interval_tables(eng, n_chains, step0, n_steps, trace)) return rc;
+    if (int rc = check_battery_fleet(eng, n_chains, step0, n_steps)) return rc;
     if (int rc = tmh_plan(eng, step0, n_steps, workspace, stream)) return rc;
     return tmh_step(eng, state, chain0, n_chains, step0, n_steps, inj, trace, stats, workspace,
                     (char*)workspace + pb, workspace_bytes - pb, stream);

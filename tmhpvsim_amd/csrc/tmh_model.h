@@ -1540,7 +1540,10 @@ enum OutKind : int {
     OUT_MAP = 32,
     // flag on OUT_STORAGE: the battery kind (tmh_battery) -- per-chain parameters from memory, charge and
     // discharge efficiency, standby drain and the loss column; the engine reports it as TMH_OUT_BATTERY
-    OUT_LOSSY = 64
+    OUT_LOSSY = 64,
+    // flag on OUT_STORAGE | OUT_LOSSY, replay pass only: the battery fleet series beside the table -- the second's
+    // quantities reduced across the chains into rows of TMH_BATTERY_FLEET_COLS sums; TMH_OUT_BATTERY_FLEET
+    OUT_FLEET = 128
 };
 constexpr int out_base(int out) { return out & 7; }
 // no trace: the statistics-only expansion's workgroup shape
@@ -1677,6 +1680,15 @@ struct BatteryView {
     StorageView st;
     const long long* params;
 };
+// The battery fleet series beside the battery kind's table (OUT_FLEET): the kind's view and the window's rows of
+// the fleet table through the series' view -- rows of TMH_BATTERY_FLEET_COLS int64 per step, `sum` at the window's
+// first step of group 0, gstride elements from a group to the next.
+struct BatteryFleetView {
+    BatteryView bt;
+    SeriesView se;
+};
+// The state of charge (0 <= x < 2^40) in two halves of FLEET_SOC_HALF bits: 32 lanes of either fit an int32 partial
+constexpr int FLEET_SOC_HALF = 20;
 // The demand registers' packed key of a second (tmh_demand): the quantised power v (0 <= v < 2^27)
 // above the complement of the second's offset o in its interval, so the maximum key is the
 // largest power at its earliest second; > 0 for every second.
@@ -1692,18 +1704,21 @@ __device__ __forceinline__ int series_q(R v)
     if constexpr (sizeof(R) == 4) return (int)rintf(v * (float)(1 << SERIES_FRAC_BITS));
     else return (int)rint(v * (double)(1 << SERIES_FRAC_BITS));
 }
+// The half-wave sums below in unsigned arithmetic (the bits of the signed sum; of values >= 0 it holds sums up to
+// 2^32 - 1: 32 x (2^27 - 1) fits)
+__device__ __forceinline__ uint32_t half_wave_sum_u(uint32_t v)
+{
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);    // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);    // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);    // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);    // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1, 3
+    return v;
+}
 // The sums of v over lanes 0-31 in lane 31 and over lanes 32-63 in lane 63 (other lanes:
 // partial sums).  Four shifted adds scan each row of 16 lanes (zeros shifted in), then
 // rows 1 and 3 add lane 15 of the row before.  32 x 2^26 fits the int32.
-__device__ __forceinline__ int half_wave_sum(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);    // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);    // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);    // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);    // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1, 3
-    return v;
-}
+__device__ __forceinline__ int half_wave_sum(int v) { return (int)half_wave_sum_u((uint32_t)v); }
 
 // held: a guard-band second whose pv / residual fixup_kernel replaces; it enters
 // the sums here (fixup_kernel adds the exact difference) but not the maximum or

@@ -194,6 +194,8 @@ class BatchedSim:
         self._storage_args = self._storage_work = self._storage_desc = None
         self.battery_params = None   # int64 [6, n]: the batteries' parameters (enable_battery); soc and the work buffer as storage's
         self._battery_desc = None
+        self.battery_fleet_raw = None   # int64 [n_groups, n_steps, 8]: the battery fleet series (enable_battery_fleet)
+        self._battery_fleet = None
         self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
@@ -481,6 +483,8 @@ class BatchedSim:
         if n_steps is None:
             if self._battery is not None:   # (soc and the work buffer may be enable_storage's)
                 self.soc = self._storage_work = self._battery_desc = self.battery_params = None
+            if self._battery_fleet is not None:   # (the kind's own output: off with it)
+                self.enable_battery_fleet(None)
             return self._enable_table("battery", None, interval_s, step0, buffer)
         if self.precision != _lib.TMH_FP64:
             raise ValueError("the battery kind needs precision='fp64': an fp32 engine replaces its guard-band seconds "
@@ -538,6 +542,50 @@ class BatchedSim:
         energy_wh_loss and round_trip, [n_intervals, n] each."""
         return self._table_watts("battery")
 
+    # ------------------------------------------------------------------ the battery fleet series
+    def enable_battery_fleet(self, n_steps, step0=None, group_chains=0, buffer=None):
+        """Beside the battery kind's table (enable_battery first), accumulate the battery fleet series
+        (tmhpvsim_amd.battery.FLEET_COLUMNS: per second and group of chains, the fleet series' four columns and
+        the exact integer sums of the import and the export behind the batteries, of the state of charge after
+        the second and of what the batteries take) of steps [step0, step0 + n_steps) in every later run.
+        step0, group_chains and buffer as enable_series, with rows of eight: `sim.battery_fleet_raw` is the
+        int64 tensor [n_groups, n_steps, 8] (several sims may add into one buffer).  run() and its window
+        pipeline carry it; compact=True is refused.  n_steps=None switches it off; so does
+        enable_battery(None)."""
+        torch = _torch()
+        if n_steps is None:
+            _lib.check(self.L.tmh_set_battery_fleet(self._eng, None))
+            self.battery_fleet_raw, self._battery_fleet = None, None
+            return None
+        if self._battery is None:
+            raise ValueError("enable_battery_fleet: call enable_battery first (the battery kind's replay pass fills "
+                             "the battery fleet series)")
+        from .battery import FLEET_COLUMNS
+        n_steps, gc, nc = int(n_steps), int(group_chains), len(FLEET_COLUMNS)
+        if n_steps < 1 or gc < 0 or gc % 512:
+            raise ValueError("enable_battery_fleet: n_steps >= 1, group_chains 0 or a multiple of 512")
+        n_groups = 1 if gc == 0 else -(-self.n // gc)
+        if buffer is None:
+            buffer = torch.zeros(n_groups, n_steps, nc, dtype=torch.int64, device=self.device)
+        elif (buffer.dtype != torch.int64 or buffer.device != self.device or not buffer.is_contiguous()
+              or buffer.dim() != 3 or buffer.shape[0] < n_groups or tuple(buffer.shape[1:]) != (n_steps, nc)):
+            raise ValueError(f"battery fleet buffer must be a contiguous int64 [>= {n_groups}, {n_steps}, {nc}] tensor "
+                             f"on {self.device}")
+        st = _lib.Series(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, gc,
+                         int(buffer.shape[0]), 0)
+        _lib.check(self.L.tmh_set_battery_fleet(self._eng, C.byref(st)))
+        self.battery_fleet_raw, self._battery_fleet = buffer, st
+        return buffer
+
+    def battery_fleet(self, bin_s=1, mean=False):
+        """The battery fleet series in watts and watt-hours (battery.fleet_to_watts of battery_fleet_raw),
+        [n_groups, n_bins] each."""
+        from .battery import fleet_to_watts
+        if self.battery_fleet_raw is None:
+            raise ValueError("no battery fleet series: call enable_battery_fleet first")
+        _torch().cuda.synchronize(self.device)
+        return fleet_to_watts(self.battery_fleet_raw, bin_s=bin_s, mean=mean)
+
     def guard_records(self):
         """Tests: the fp32 guard-band records (chain, 128-s block) of the last window that run()
         issued as a single tmh_run (tmh_test_guard_records; synchronises the device)."""
@@ -594,6 +642,12 @@ class BatchedSim:
                 raise ValueError(t["no_trace"])
             if self.step < tb.step0 or self.step + n_steps > tb.step0 + tb.n_steps:
                 raise ValueError(f"steps [{self.step}, +{n_steps}) outside the {t['noun']} [{tb.step0}, +{tb.n_steps})")
+        if self._battery_fleet is not None:   # (the library refuses each too, window by window)
+            if compact:
+                raise ValueError("a battery fleet series cannot run compacted (a compacted tile would mix groups)")
+            s0, sn = self._battery_fleet.step0, self._battery_fleet.n_steps
+            if self.step < s0 or self.step + n_steps > s0 + sn:
+                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the battery fleet series [{s0}, +{sn})")
         if n_steps > ROLL_MAX:   # one rolling clock covers at most ROLL_MAX steps: run in pieces (same bits)
             res = out if out is not None else self._alloc(n_steps, trace)
             done = 0
