@@ -3,7 +3,8 @@
 kernel) of the statistics-only expansion and of the expansions with a table, same chains,
 same window, same process, the runs alternating.
 
-    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet [--chains 65536] [--steps 86400]
+    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet|battery_sweep
+                                 [--variants 5] [--chains 65536] [--steps 86400]
                                  [--interval 900] [--rounds 5] [--precision fp32]
                                  [--start "2019-09-05 00:00:00"] [--out FILE.json]
                                  [--modules 1 --capacity-wh 5000 --charge-w 2500 --discharge-w 2500]
@@ -28,6 +29,13 @@ The runs of a kind, each with the same statistics beside its table:
              fleet series (BatchedSim.enable_battery_fleet, one group); the two tables are equal, the rows summed
              over each interval are the table summed over the chains; fleet / battery for the whole expansion and
              for each launch (the replay pass fills the rows), beside the spread of the kind's own rounds.
+  battery_sweep: OUT_BATTERY and OUT_BATTERY_SWEEP, battery's setting, no statistics -- the unchanged battery kind
+             (one battery of --capacity-wh per chain) and the sweep over --variants K capacities spread +-20 % around
+             it, alternating; variant (K - 1) / 2 has the kind's own capacity and its table and soc are the kind's bit
+             for bit, and columns 0-3 agree in every variant.  The kind's three launches are timed for both (the
+             sweep's slots sum its groups' launches); the yardstick is K x the battery kind's median of the same run:
+             ratio_sweep_k_battery = sweep / (K x battery) for the whole expansion and per launch, beside the spread
+             of each run's own rounds.
 The script checks each run's variant, these identities (on the warm-up round's tables), that
 the statistics of all runs agree bit for bit and that every table's ok seconds equal the
 histogram's count.  One warm-up round, then --rounds timed ones.  Prints one JSON line: the
@@ -53,6 +61,7 @@ RUNS = {
     "battery": (("stats_only", None), ("storage", "storage"), ("battery", "battery")),
     # (the table of both runs is the battery kind's; "battery_fleet" also enables the battery fleet series)
     "battery_fleet": (("battery", "battery"), ("battery_fleet", "battery")),
+    "battery_sweep": (("battery", "battery"), ("battery_sweep", "battery_sweep")),   # (sweep_cost: a loop of its own)
 }
 
 
@@ -97,6 +106,78 @@ def check_tables(kind, tables, interval_s):
     return None
 
 
+def sweep_cost(a, mp, lossy):
+    """--kind battery_sweep: the battery kind and the sweep over a.variants capacities, alternating."""
+    import torch
+    from tmhpvsim_amd import _lib
+    from tmhpvsim_amd.engine import BatchedSim
+    K = a.variants
+    caps = [a.capacity_wh * (0.8 + 0.4 * v / max(K - 1, 1)) for v in range(K)] if K > 1 else [a.capacity_wh]
+    mid = (K - 1) // 2
+    caps[mid] = a.capacity_wh
+    soc0 = [c / 2 for c in caps]   # (half full, as the kind's: the variants differ from their first second)
+    parts = (("map", _lib.K_STORAGE_MAP), ("scan", _lib.K_STORAGE_SCAN), ("replay", _lib.K_STORAGE_REPLAY))
+    groups = None
+
+    def one(label):
+        nonlocal groups
+        sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=mp, precision="fp64", device="cuda:0", horizon=a.steps)
+        if label == "battery":
+            raw = sim.enable_battery(a.steps, a.interval, **lossy)
+        else:
+            raw = sim.enable_battery_sweep(a.steps, a.interval, **{**lossy, "capacity_wh": caps, "soc0_wh": soc0})
+        _lib.check(sim.L.tmh_profile_enable(sim._eng, 1))
+        sim.run(a.steps, trace=(), window=a.steps)
+        torch.cuda.synchronize()
+        ms, launches = _lib.profile_read(sim._eng, _lib.K_EXPAND)
+        want = (_lib.OUT_BATTERY if label == "battery" else _lib.OUT_BATTERY_SWEEP) | _lib.OUT_FP64
+        assert launches == 1 and sim.L.tmh_engine_last_expand(sim._eng) == want, (launches, want)
+        pm = {}
+        for name, kk in parts:
+            pm[name], pn = _lib.profile_read(sim._eng, kk)
+            if label == "battery":
+                assert pn == 1
+            else:
+                groups = pn
+        return ms, pm, raw, sim.soc.clone()
+
+    def check(bt, sw):   # the warm-up round's tables: the middle variant is the kind's, columns 0-3 every variant's
+        assert torch.equal(sw[2][mid], bt[2]) and torch.equal(sw[3][mid], bt[3])
+        for v in range(K):
+            t = sw[2][v]
+            assert torch.equal(t[:, :4], bt[2][:, :4]) and bool((t[:, 4:8] >= 0).all()) and bool((t[:, 9] >= 0).all())
+            assert torch.equal(t[:, 4] - t[:, 5], t[:, 1] - t[:, 0] + t[:, 6] - t[:, 7])
+            assert v == mid or not torch.equal(t[:, 4:], bt[2][:, 4:])
+        assert int(bt[2][:, 6].sum()) > 0 and int(bt[2][:, 7].sum()) > 0 and int(bt[2][:, 9].sum()) > 0
+
+    check(one("battery"), one("battery_sweep"))   # warm-up: code objects, allocator
+    labels = ("battery", "battery_sweep")
+    t = {k: [] for k in labels}
+    pt = {k: {name: [] for name, _ in parts} for k in labels}
+    for _ in range(a.rounds):
+        for label in labels:
+            ms, pm, _raw, _soc = one(label)
+            t[label].append(ms)
+            for name in pm:
+                pt[label][name].append(pm[name])
+            del _raw, _soc
+    med = {k: statistics.median(t[k]) for k in labels}
+    pmed = {k: {name: statistics.median(v) for name, v in pt[k].items()} for k in labels}
+    res = dict(device=torch.cuda.get_device_name(0), chains=a.chains, steps=a.steps, interval_s=a.interval, precision="fp64",
+               start=a.start, rounds=a.rounds, modules=a.modules, battery=lossy, variants=K, capacities_wh=caps,
+               launch_groups=groups,
+               **{f"{k}_ms": t[k] for k in labels}, **{f"{k}_median_ms": med[k] for k in labels},
+               **{f"{k}_{name}_ms": v for k in labels for name, v in pt[k].items()},
+               **{f"{k}_{name}_median_ms": v for k in labels for name, v in pmed[k].items()},
+               **{f"{k}_spread": max(t[k]) / min(t[k]) for k in labels},
+               **{f"{k}_replay_spread": max(pt[k]["replay"]) / min(pt[k]["replay"]) for k in labels},
+               yardstick_ms=K * med["battery"], sweep_ms_per_variant=med["battery_sweep"] / K,
+               ratio_sweep_k_battery=med["battery_sweep"] / (K * med["battery"]),
+               **{f"ratio_{name}_sweep_k_battery": pmed["battery_sweep"][name] / (K * pmed["battery"][name]) for name, _ in parts},
+               build_stamp=_lib.loaded_stamp())
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", choices=tuple(RUNS), required=True)
@@ -114,8 +195,9 @@ def main():
     ap.add_argument("--charge-eff", type=float, default=0.95)
     ap.add_argument("--discharge-eff", type=float, default=0.95)
     ap.add_argument("--standby-w", type=float, default=2.0)
+    ap.add_argument("--variants", type=int, default=5, help="--kind battery_sweep: the batteries per chain")
     a = ap.parse_args()
-    if a.kind in ("storage", "battery", "battery_fleet"):
+    if a.kind in ("storage", "battery", "battery_fleet", "battery_sweep"):
         a.precision = "fp64"   # (the kind's engines)
     import torch
     from tmhpvsim_amd import _lib
@@ -140,6 +222,13 @@ def main():
     battery = dict(capacity_wh=a.capacity_wh, charge_w=a.charge_w, discharge_w=a.discharge_w, soc0_wh=a.capacity_wh / 2)
     lossy = dict(battery, charge_eff=a.charge_eff, discharge_eff=a.discharge_eff, standby_w=a.standby_w)
     enable_kw = {"storage": battery, "battery": lossy}
+    if a.kind == "battery_sweep":
+        line = json.dumps(sweep_cost(a, mp, lossy))
+        print(line)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     runs = RUNS[a.kind]
     labels = [label for label, _ in runs]
 

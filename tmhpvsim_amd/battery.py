@@ -211,6 +211,128 @@ def fleet_from_traces(pv, meter, covered, *, params, soc0, group_chains=0):
     return out, x
 
 
+SWEEP_MAX = 16   # TMH_BATTERY_SWEEP_MAX: the variants of one battery sweep
+
+
+def check_sweep_params(params):
+    """Sweep parameters as an int64 [K, 6, n] array, 1 <= K <= SWEEP_MAX, every variant inside tmh_battery's
+    ranges (check_params per variant; ValueError otherwise)."""
+    params = np.asarray(params.cpu() if hasattr(params, "cpu") else params)
+    if params.ndim != 3 or params.shape[1] != len(PARAMS) or params.dtype != np.int64:
+        raise ValueError("battery sweep params must be an int64 [K, 6, n] array")
+    if not 1 <= params.shape[0] <= SWEEP_MAX:
+        raise ValueError(f"battery sweep: {params.shape[0]} variants outside [1, {SWEEP_MAX}]")
+    for p in params:
+        check_params(p)
+    return params
+
+
+def quantize_sweep_params(capacity_wh, charge_w, discharge_w, charge_eff=1.0, discharge_eff=1.0, standby_w=0.0, *, n,
+                          n_variants=None):
+    """The int64 [K, 6, n] parameters of a battery sweep: each quantity a scalar (every variant and chain), a
+    sequence of K values (one per variant, uniform over the chains) or a [K, n] array; quantised per variant
+    by quantize_params.  K is n_variants when given, else the longest argument's length; ValueError when an
+    argument's length is neither 1 nor K or K is outside [1, SWEEP_MAX]."""
+    args = [np.asarray(v, dtype=np.float64) for v in (capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w)]
+    if any(a.ndim > 2 for a in args):
+        raise ValueError("battery sweep quantities are scalars, [K] sequences or [K, n] arrays")
+    k = int(n_variants) if n_variants is not None else max([a.shape[0] for a in args if a.ndim] or [1])
+    if not 1 <= k <= SWEEP_MAX:
+        raise ValueError(f"battery sweep: {k} variants outside [1, {SWEEP_MAX}]")
+    for name, a in zip(PARAMS, args):
+        if a.ndim and a.shape[0] not in (1, k):
+            raise ValueError(f"battery sweep {name}: {a.shape[0]} values for {k} variants")
+        if a.ndim == 2 and a.shape[1] not in (1, int(n)):
+            raise ValueError(f"battery sweep {name}: {a.shape[1]} values for {n} chains")
+    rows = [np.broadcast_to(a if a.ndim == 2 else a.reshape(-1, 1), (k, a.shape[1] if a.ndim == 2 else 1)) for a in args]
+    return np.stack([quantize_params(*(r[v] for r in rows), n=int(n)) for v in range(k)])
+
+
+def quantize_sweep_soc(soc0_wh, params):
+    """The starting SoC [K, n] of a sweep's batteries from watt-hours (a scalar, [K] or [K, n]); ValueError
+    outside [0, C]."""
+    k, _, n = params.shape
+    a = np.asarray(soc0_wh, dtype=np.float64)
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)
+    a = np.broadcast_to(a, (k, n))
+    return np.stack([quantize_soc(a[v], params[v]) for v in range(k)])
+
+
+def sweep_from_traces(pv, meter, covered, interval_s, *, params, soc0, origin=0):
+    """The battery sweep of time-major traces [n_steps, n_chains]: every chain behind each of K batteries --
+    (int64 [K, n_intervals, 10, n_chains], int64 [K, n_chains]), variant v what from_traces gives for params[v]
+    and soc0[v].  One loop over the seconds with the state [K, n]: the second's rule is written out here on
+    [K, n] arrays, apart from from_traces and _second, so that comparing the two compares two derivations.
+    params: int64 [K, 6, n_chains]; soc0: a scalar, [K, 1] or [K, n_chains], clamped into [0, C]."""
+    pv, meter, covered = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (pv, meter, covered))
+    base = intervals.from_traces(pv, meter, covered, interval_s, origin=origin)      # (checks the arguments)
+    interval_s, origin = int(interval_s), int(origin)
+    if interval_s > MAX_INTERVAL_S:
+        raise ValueError("interval_s <= 2^23 - 1")
+    n_steps, n = pv.shape
+    params = check_sweep_params(params)
+    if params.shape[2] != n:
+        raise ValueError(f"battery sweep params for {params.shape[2]} chains, traces of {n}")
+    K = params.shape[0]
+    cap, pc, pd, ec, ed, sb = (params[:, r] for r in range(6))              # [K, n] each
+    kc, kd = ((1 << 32) - 1) // ec + 1, ((1 << 32) - 1) // ed + 1
+    out = np.zeros((K, base.shape[0], len(COLUMNS), n), dtype=np.int64)
+    out[:, :, :4] = base[None]
+    x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (K, n)), 0, cap)
+    nan = np.isnan(pv) | np.isnan(meter) | (covered == 255)
+    qd = np.where(nan, 0, quantize(pv) - quantize(meter)).astype(np.int64)
+    for t in range(n_steps):
+        k, o = divmod(origin + t, interval_s)
+        oks, d = ~nan[t][None], qd[t][None]                                 # [1, n] against the variants' [K, n]
+        ask = np.minimum(np.maximum(d, -pd), pc)
+        up = ask >= 0
+        mag = np.abs(ask)
+        stored = np.where(up, (mag * ec) >> 16, -((mag * kd + 65535) >> 16))
+        x1 = np.minimum(np.maximum(x + stored, 0), cap)
+        moved = x1 - x
+        cost = np.where(moved > 0, (moved * kc + 65535) >> 16, (-moved * ed) >> 16)   # at the meter side, unsigned
+        clipped = np.sign(moved) * np.minimum(mag, cost)
+        b = np.where(moved == stored, ask, clipped)
+        xn = np.maximum(x1 - sb, 0)
+        cell = out[:, k]
+        cell[:, 4] += np.where(oks, np.maximum(b - d, 0), 0)
+        cell[:, 5] += np.where(oks, np.maximum(d - b, 0), 0)
+        cell[:, 6] += np.where(oks, np.maximum(b, 0), 0)
+        cell[:, 7] += np.where(oks, np.maximum(-b, 0), 0)
+        cell[:, 8] = np.where(oks, ((o + 1) << KEY_SHIFT) | xn, cell[:, 8])
+        cell[:, 9] += np.where(oks, b - (xn - x), 0)
+        x = np.where(oks, xn, x)
+    return out, x
+
+
+def sweep_summary(raw, interval_s, params, fleet=False):
+    """Per variant and chain, over all the intervals of a raw sweep table [K, n_intervals, 10, n] with the
+    parameters [K, 6, n]: dict of float64 [K, n] arrays (fleet=True: [K], of the integer totals over the chains,
+    the capacity's included) -- energy_wh_pv, energy_wh_meter, energy_wh_import,
+    energy_wh_export, energy_wh_charge, energy_wh_discharge, energy_wh_loss (Wh), self_consumption = (pv -
+    export) / pv, self_sufficiency = (meter - import) / meter (NaN where the denominator is 0) and full_cycles =
+    discharged Wh / capacity (NaN for a chain without a battery, C = 0).  The columns are summed over the
+    intervals as integers first and turned into floats once, as fleet_to_watts does.  (interval_s: the table's,
+    checked only; the sums do not depend on it.)"""
+    raw = np.asarray(raw.cpu() if hasattr(raw, "cpu") else raw).astype(np.int64, copy=False)
+    params = check_sweep_params(params)
+    if raw.ndim != 4 or raw.shape[2] != len(COLUMNS) or raw.shape[0] != params.shape[0] or raw.shape[3] != params.shape[2]:
+        raise ValueError("raw battery sweep table must be [K, n_intervals, 10, n] with params [K, 6, n]")
+    if int(interval_s) < 1:
+        raise ValueError("interval_s must be >= 1")
+    tot, cap = raw.sum(axis=1), params[:, 0]                               # [K, 10, n] (column 8 is a key: unused)
+    if fleet:
+        tot, cap = tot.sum(axis=2), cap.sum(axis=1)
+    e = float(1 << FRAC_BITS) * 3600.0
+    pv, meter, imp, exp, ch, dis, loss = (tot[:, c] for c in (0, 1, 4, 5, 6, 7, 9))
+    nz = lambda a: np.where(a != 0, a, np.nan).astype(np.float64)
+    return {"energy_wh_pv": pv / e, "energy_wh_meter": meter / e, "energy_wh_import": imp / e,
+            "energy_wh_export": exp / e, "energy_wh_charge": ch / e, "energy_wh_discharge": dis / e,
+            "energy_wh_loss": loss / e, "self_consumption": (pv - exp) / nz(pv),
+            "self_sufficiency": (meter - imp) / nz(meter), "full_cycles": dis / nz(cap)}
+
+
 def fleet_to_watts(raw, bin_s=1, mean=False):
     """float64 series of a raw battery fleet table [..., n_steps, 8]: dict of pv, meter, import_w, export_w,
     charge_w, discharge_w (W) and soc_wh (Wh) -- fleet sums, or with mean=True the means per ok chain-second

@@ -85,6 +85,11 @@ constexpr int EXP_WAVES_TRACE = 7, EXP_WAVES_STATS = 6, EXP_WAVES_F64 = 4, EXP_W
 //    workgroups) it spilled 213 VGPRs against storage's 81 and ran 87.5 ms where storage's replay runs 51.2 ms;
 //    at 3 it spills 24 and runs 47.1 ms (Battery losses)
 constexpr int EXP_WAVES_LOSSY = 3;
+//  the battery sweep's two passes (fp64 single-site, SWEEP_KV = 4 variants per lane), in 256-chain workgroups: 2 =
+//    at most 256 VGPRs; the map pass takes 209 and the replay 240, neither spills.  At 3 waves (168 VGPRs) the map
+//    pass spilled 98 VGPRs, the cliff the battery kind's replay met at 4 (Battery sweep)
+constexpr int EXP_WAVES_SWEEP_MAP = 2, EXP_WAVES_SWEEP_REPLAY = 2;
+constexpr bool out_sweep(int out) { return (out & OUT_SWEEP) != 0; }
 constexpr bool out_lossy_replay(int out) { return out_base(out) == OUT_STORAGE && (out & OUT_LOSSY) && !(out & OUT_MAP); }
 constexpr int FIX_WAVES_SITES = 1;   // min waves per SIMD of the per-site fixup (its fp64 redo recomputes the site's geometry)
 
@@ -2029,7 +2034,7 @@ constexpr int exp_tile_order()
 template <typename R, int OUT, bool SITES>
 constexpr int exp_wg()
 {
-    return out_lossy_replay(OUT) ? 256 : out_no_trace(OUT) && !SITES ? EXP_WG_STATS : 256;
+    return out_lossy_replay(OUT) || out_sweep(OUT) ? 256 : out_no_trace(OUT) && !SITES ? EXP_WG_STATS : 256;
 }
 // the LDS histogram as 16-bit bin pairs when one tile (WG chains x 128 s) cannot fill a
 // 16-bit bin, else one 32-bit word per bin
@@ -2042,6 +2047,7 @@ template <typename R, int OUT, bool SITES>
 constexpr int exp_waves()
 {
     return SITES                             ? EXP_WAVES_SITES
+           : out_sweep(OUT)                   ? ((OUT & OUT_MAP) ? EXP_WAVES_SWEEP_MAP : EXP_WAVES_SWEEP_REPLAY)
            : out_lossy_replay(OUT)            ? EXP_WAVES_LOSSY
            : sizeof(R) == 8                   ? EXP_WAVES_F64
            : out_base(OUT) == OUT_TRACE3      ? EXP_WAVES_TRACE
@@ -2212,7 +2218,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                             const PV64* pv_lds, const double* pv_lds_tab,
                                             const float4* nd_lds, const SeriesView& se, SeriesLds* ser_lds,
                                             const IntervalsView& ivv, const StorageView& sto, const long long* batp,
-                                            FleetLds<WGT / 32>* flt_lds)
+                                            FleetLds<WGT / 32>* flt_lds, const SweepView& swv)
 {
     constexpr bool SER = out_base(OUT) == OUT_SERIES;
     // Battery storage (fp64 only), two passes over the same per-second body:
@@ -2234,6 +2240,13 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // (fleet_flush; `se` views it, rows of TMH_BATTERY_FLEET_COLS)
     constexpr bool FLT = (OUT & OUT_FLEET) != 0;
     static_assert(!FLT || (BAT && REP), "the battery fleet series: a flag of the battery kind's replay pass only");
+    // SWP: the battery sweep on the battery kind's two passes -- the per-second body and d = q(pv) - q(meter) once
+    // per second, then KV batteries' seconds from it: KV parameter sets, KV maps (MAP) or KV states of charge
+    // and piece sums (REP) per lane, one iv_pv and one iv_m; variants swv.nv .. KV - 1 of a short group are empty
+    // batteries in registers that are never loaded, stored or flushed and whose seconds are skipped
+    constexpr bool SWP = (OUT & OUT_SWEEP) != 0;
+    constexpr int KV = SWP ? SWEEP_KV : 1;
+    static_assert(!SWP || (BAT && !FLT && !SITES), "the battery sweep: a flag of the battery kind's passes, single site");
     static_assert(!STO || sizeof(R) == 8, "battery storage: fp64 engines only (no guard-band seconds)");
     // REG: the import / export registers -- the intervals' pieces, accumulators and flush, with
     // one more accumulator and IVC = 6 columns per cell instead of 4
@@ -2433,13 +2446,32 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     long long sx = 0, sx0 = 0, st_ch = 0, st_dis = 0;
     BatteryParams bp = battery_none();
     long long bat_hi = 0;   // the second's map after the standby drain: {s - sigma, 0, max(C - sigma, 0)}
-    if constexpr (BAT) {
+    if constexpr (BAT && !SWP) {
         if (live) bp = battery_load(batp, ivv.ld, gid(kp.ids, c));
         bat_hi = max(bp.cap - (long long)bp.sigma, 0ll);
     }
-    if constexpr (REP) {
+    if constexpr (REP && !SWP) {
         if (live) sx = sto.work[(size_t)b * 3 * n + c];
         sx0 = sx;
+    }
+    // the sweep's per-variant state, as the battery kind's above: sw_map (MAP), sw_x, sw_x0, sw_ex, sw_ch, sw_dis (REP)
+    SocMap sw_map[KV];
+    BatteryParams sw_bp[KV];
+    long long sw_hi[KV], sw_x[KV], sw_x0[KV], sw_ex[KV], sw_ch[KV], sw_dis[KV];
+    if constexpr (SWP) {
+#pragma unroll
+        for (int v = 0; v < KV; ++v) {
+            const bool on = live && (uint32_t)v < swv.nv;
+            sw_map[v] = soc_identity();
+            sw_bp[v] = battery_none();
+            if (on) sw_bp[v] = battery_load(batp + (size_t)v * 6 * ivv.ld, ivv.ld, gid(kp.ids, c));
+            sw_hi[v] = max(sw_bp[v].cap - (long long)sw_bp[v].sigma, 0ll);
+            sw_x[v] = 0;
+            if constexpr (REP)
+                if (on) sw_x[v] = sto.work[(size_t)v * swv.wstride + (size_t)b * 3 * n + c];
+            sw_x0[v] = sw_x[v];
+            sw_ex[v] = sw_ch[v] = sw_dis[v] = 0;
+        }
     }
     // FLT: the block-relative second of the last flush (slot of a second = jb - flt_base) and the group
     uint32_t flt_base = 0;
@@ -2461,6 +2493,53 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         iv_next = __builtin_amdgcn_readfirstlane((uint32_t)min(nb, (uint64_t)j1));
     }
     auto iv_flush = [&](uint32_t pa, uint32_t pb) __attribute__((always_inline)) {
+        if constexpr (SWP && REP) {
+            // the sweep: the piece's ten columns into every variant's table -- columns 0-3 the same in each,
+            // the battery's from the variant's own sums and state of charge (the battery kind's flush below)
+            if (live) {
+                const int32_t lo = (int32_t)(pa - j0), hi = min((int32_t)pb, fault_eff) - (int32_t)j0;
+                const uint32_t ob = ivv.rel0 + j0 - iv_k * ivv.interval_s;
+                uint32_t nc = 0;
+                if (hi > lo) {
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        const int32_t wl = max(lo - 32 * w, 0), wh = min(hi - 32 * w, 32);
+                        if (wh > wl)
+                            nc += __popc(cov_lds[w][threadIdx.x] & ((wh - wl == 32 ? ~0u : ((1u << (wh - wl)) - 1u)) << wl));
+                    }
+                }
+#pragma unroll
+                for (int v = 0; v < KV; ++v) {
+                    if ((uint32_t)v < swv.nv) {
+                        unsigned long long* cell = ivv.sum + (size_t)v * swv.tstride + (size_t)iv_k * IVC * ivv.ld + gid(kp.ids, c);
+                        const long long net = sw_ch[v] - sw_dis[v], im = sw_ex[v] + net - (iv_pv - iv_m),
+                                        loss = net - (sw_x[v] - sw_x0[v]);
+                        if (iv_pv) atomicAdd(cell, (unsigned long long)iv_pv);
+                        if (iv_m) atomicAdd(cell + ivv.ld, (unsigned long long)iv_m);
+                        if (im) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)im);
+                        if (sw_ex[v]) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)sw_ex[v]);
+                        if (sw_ch[v]) atomicAdd(cell + 6 * ivv.ld, (unsigned long long)sw_ch[v]);
+                        if (sw_dis[v]) atomicAdd(cell + 7 * ivv.ld, (unsigned long long)sw_dis[v]);
+                        if (loss) atomicAdd(cell + 9 * ivv.ld, (unsigned long long)loss);
+                        if (hi > lo) {
+                            atomicAdd(cell + 2 * ivv.ld, (unsigned long long)(hi - lo));
+                            __hip_atomic_fetch_max(cell + 8 * ivv.ld, soc_key(ob + (uint32_t)(hi - 1), sw_x[v]),
+                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if (nc) atomicAdd(cell + 3 * ivv.ld, (unsigned long long)nc);
+                        }
+                    }
+                }
+            }
+            iv_pv = 0;
+            iv_m = 0;
+#pragma unroll
+            for (int v = 0; v < KV; ++v) {
+                sw_ex[v] = sw_ch[v] = sw_dis[v] = 0;
+                sw_x0[v] = sw_x[v];
+            }
+            ++iv_k;
+            return;
+        }
         if (live) {
             unsigned long long* cell = ivv.sum + (size_t)iv_k * IVC * ivv.ld + gid(kp.ids, c);
             if (iv_pv) atomicAdd(cell, (unsigned long long)iv_pv);
@@ -2559,7 +2638,32 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             if (!(__builtin_constant_p(pv) && pv == R(0))) qp = series_q<R>(pv);
             const int d = qp - qm;
             const long long a = (long long)soc_ask(d, sto.p_charge, sto.p_discharge);
-            if constexpr (BAT) {
+            if constexpr (SWP) {
+                // the sweep: the battery kind's second (below) of each variant from the one d
+                if constexpr (REP) {
+                    iv_m += (long long)(ok ? qm : 0);
+                    if (!(__builtin_constant_p(pv) && pv == R(0))) iv_pv += (long long)(ok ? qp : 0);
+                }
+#pragma unroll
+                for (int v = 0; v < KV; ++v) {
+                    if (v > 0 && (uint32_t)v >= swv.nv) continue;   // a short group's missing variants: a scalar branch
+                    const BatteryParams& p = sw_bp[v];
+                    const int ab = soc_ask(d, p.pc, p.pd), s = bat_stored(ab, p);
+                    if constexpr (MAP) {
+                        const SocMap f = soc_compose(sw_map[v], SocMap{(long long)(s - p.sigma), 0, sw_hi[v]});
+                        sw_map[v].a = ok ? f.a : sw_map[v].a;
+                        sw_map[v].lo = ok ? f.lo : sw_map[v].lo;
+                        sw_map[v].hi = ok ? f.hi : sw_map[v].hi;
+                    } else {
+                        const long long x1 = soc_clamp(sw_x[v] + s, 0, p.cap);
+                        const int bm = bat_meter_side(ab, s, (int)(x1 - sw_x[v]), p);
+                        sw_x[v] = ok ? max(x1 - (long long)p.sigma, 0ll) : sw_x[v];
+                        sw_ex[v] += (long long)(ok ? max(d - bm, 0) : 0);
+                        sw_ch[v] += (long long)(ok ? max(bm, 0) : 0);
+                        sw_dis[v] += (long long)(ok ? max(-bm, 0) : 0);
+                    }
+                }
+            } else if constexpr (BAT) {
                 // the battery kind (tmh_battery): what the lane's own ask stores or drains, then the standby
                 // drain; the map pass composes the two clamped additions as one, the replay pass takes the
                 // meter side b from how far the state of charge really moved
@@ -2855,6 +2959,20 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                               cov_lds[3][threadIdx.x])};
         }
     }
+    if constexpr (MAP && SWP) {   // the block's map of each variant, as the battery kind's below, in the variant's work buffer
+        if (live) {
+#pragma unroll
+            for (int v = 0; v < KV; ++v) {
+                if ((uint32_t)v < swv.nv) {
+                    long long* w = sto.work + (size_t)v * swv.wstride + (size_t)b * 3 * n + c;
+                    w[0] = sw_map[v].a;
+                    w[n] = sw_map[v].lo;
+                    w[2 * (size_t)n] = sw_map[v].hi;
+                }
+            }
+        }
+        return;
+    }
     if constexpr (MAP) {   // the block's map, lane-consecutive ([block][3][n]); the launch carries no statistics
         if (live) {
             long long* w = sto.work + (size_t)b * 3 * n + c;
@@ -2888,8 +3006,9 @@ using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView,
                                                           out_base(OUT) == OUT_DEMAND,
                                                       IntervalsView,
                                                       std::conditional_t<out_base(OUT) == OUT_STORAGE,
+                                                                         std::conditional_t<(OUT & OUT_SWEEP) != 0, SweepView,
                                                                          std::conditional_t<(OUT & OUT_FLEET) != 0, BatteryFleetView,
-                                                                                            std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>>,
+                                                                                            std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>>>,
                                                                          TraceView>>>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
@@ -2909,6 +3028,13 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     IntervalsView ivv{};
     StorageView sto{};
     const long long* batp = nullptr;
+    SweepView swv{};
+    if constexpr ((OUT & OUT_SWEEP) != 0) {   // the battery sweep: the battery kind's view of the group's first variant + the strides
+        swv = ov;
+        sto = ov.bt.st;
+        ivv = ov.bt.st.iv;
+        batp = ov.bt.params;
+    } else
     if constexpr (out_base(OUT) == OUT_SERIES) se = ov;
     else if constexpr (out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS || out_base(OUT) == OUT_DEMAND)
         ivv = ov;
@@ -2949,7 +3075,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     auto tile = [&](uint32_t b, uint32_t cblk, auto night) __attribute__((always_inline)) {
         expand_tile<R, OUT, SITES, WGT, decltype(night)::value>(
             b, cblk, kp, dp, st, chain0, n, W0, nsteps, utc0, tab64, tab32, sun, events, n_events, desc, sg, tr, sv,
-            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv, sto, batp, flt_lds);
+            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv, sto, batp, flt_lds, swv);
     };
     // the workgroup's LDS histogram into the device histogram
     auto hist_flush = [&]() __attribute__((always_inline)) {
@@ -3094,6 +3220,16 @@ __global__ __launch_bounds__(256) void battery_scan_kernel(long long* __restrict
                                                            const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk)
 {
     storage_scan<true>(work, soc, params, ids, n, nblk);
+}
+
+// the battery sweep: battery_scan_kernel's walk per (chain, variant), the variant the grid's y
+__global__ __launch_bounds__(256) void battery_sweep_scan_kernel(long long* __restrict__ work, long long* __restrict__ soc,
+                                                                 const long long* __restrict__ params,
+                                                                 const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk,
+                                                                 uint64_t wstride, uint64_t ld)
+{
+    const size_t v = blockIdx.y;
+    storage_scan<true>(work + v * wstride, soc + v * ld, params + v * 6 * ld, ids, n, nblk);
 }
 
 // ------------------------------------------------------------ compaction
@@ -3608,7 +3744,7 @@ void with_real(bool f64, F&& f)
 // one kind per engine at a step.  A kind is its column count, the expansion's and the fixup's
 // output, and the words the refusals name it by; a new kind is a row here, its columns in
 // expand_tile and the fixup, and its exported setter.
-enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_KINDS };
+enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_KINDS };
 struct TableKindInfo {
     int cols, out;      // out: TMH_OUT_* as tmh_engine_last_expand reports it (the expansion's OutKind but for TBL_BATTERY)
     const char* what;   // in the setter's and the checks' messages
@@ -3624,14 +3760,19 @@ constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
     // the battery kind (tmh_battery: losses and per-chain parameters; tmh_engine::battery): storage's three
     // launches on the OUT_STORAGE | OUT_LOSSY instantiations, reported as TMH_OUT_BATTERY
     {TMH_BATTERY_COLS, TMH_OUT_BATTERY, "battery tables", "the battery kind"},
+    // the battery sweep (tmh_battery_sweep: n_variants batteries per chain; tmh_engine::sweep): the battery kind's
+    // three launches per group of SWEEP_KV variants on the OUT_SWEEP instantiations, TMH_OUT_BATTERY_SWEEP
+    {TMH_BATTERY_COLS, TMH_OUT_BATTERY_SWEEP, "battery sweep tables", "the battery sweep"},
 };
 static_assert(TMH_OUT_BATTERY > out_base(~0) && TMH_OUT_BATTERY < TMH_OUT_SITES, "TMH_OUT_BATTERY: a code of its own below the flags");
 static_assert(TMH_OUT_BATTERY_FLEET > TMH_OUT_BATTERY && TMH_OUT_BATTERY_FLEET < TMH_OUT_SITES, "TMH_OUT_BATTERY_FLEET: likewise");
+static_assert(TMH_OUT_BATTERY_SWEEP > TMH_OUT_BATTERY_FLEET && TMH_OUT_BATTERY_SWEEP < TMH_OUT_SITES, "TMH_OUT_BATTERY_SWEEP: likewise");
 static_assert(interval_cols(OUT_INTERVALS) == TABLE_KINDS[TBL_INTERVALS].cols &&
                   interval_cols(OUT_REGISTERS) == TABLE_KINDS[TBL_REGISTERS].cols &&
                   interval_cols(OUT_DEMAND) == TABLE_KINDS[TBL_DEMAND].cols &&
                   interval_cols(OUT_STORAGE) == TABLE_KINDS[TBL_STORAGE].cols &&
-                  interval_cols(OUT_STORAGE | OUT_LOSSY) == TABLE_KINDS[TBL_BATTERY].cols,
+                  interval_cols(OUT_STORAGE | OUT_LOSSY) == TABLE_KINDS[TBL_BATTERY].cols &&
+                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_SWEEP) == TABLE_KINDS[TBL_SWEEP].cols,
               "the kernels' cells");
 
 }  // namespace
@@ -3657,6 +3798,7 @@ struct tmh_engine {
     } tables[TBL_KINDS];
     tmh_storage storage{};   // tmh_set_storage: the battery, soc and the work buffer beside tables[TBL_STORAGE]
     tmh_battery battery{};   // tmh_set_battery: soc, the work buffer and the parameters beside tables[TBL_BATTERY]
+    tmh_battery_sweep sweep{};   // tmh_set_battery_sweep: the variants' soc, work buffer and parameters beside tables[TBL_SWEEP]
     bool has_fleet = false;  // tmh_set_battery_fleet: the battery kind's replay pass adds its window to `fleet` too
     tmh_series fleet{};
     // the first set kind (TBL_KINDS: none); a step is refused unless it is the only one (check_interval_tables)
@@ -4192,6 +4334,43 @@ int tmh_set_battery(struct tmh_engine* eng, const tmh_battery* bt)
     return TMH_OK;
 }
 
+// the battery sweep: tmh_set_battery's checks in its own words, and the variant count
+size_t tmh_battery_sweep_work_bytes(uint32_t n_chains, uint32_t n_steps, uint32_t n_variants)
+{
+    return (size_t)n_variants * tmh_storage_work_bytes(n_chains, n_steps);
+}
+int tmh_set_battery_sweep(struct tmh_engine* eng, const tmh_battery_sweep* sw)
+{
+    if (!sw) {
+        if (int rc = set_interval_table(eng, TBL_SWEEP, nullptr)) return rc;
+        eng->sweep = tmh_battery_sweep{};
+        return TMH_OK;
+    }
+    const char* what = TABLE_KINDS[TBL_SWEEP].what;
+    if (!sw->table.sum || sw->table.n_steps == 0 || sw->table.ld == 0 || ((uintptr_t)sw->table.sum & 7) ||
+        sw->table.interval_s == 0)   // (the struct's cases, in the setter's words)
+        return set_interval_table(nullptr, TBL_SWEEP, &sw->table);
+    if (sw->table.interval_s > (1u << 23) - 1)
+        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
+                    sw->table.interval_s);
+    if (sw->n_variants == 0 || sw->n_variants > TMH_BATTERY_SWEEP_MAX)
+        return fail(TMH_E_INVAL, "%s: n_variants %u outside [1, %d]", what, sw->n_variants, TMH_BATTERY_SWEEP_MAX);
+    if (!sw->soc || ((uintptr_t)sw->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer [n_variants][ld]", what);
+    if (!sw->work || ((uintptr_t)sw->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
+    if (!sw->params || ((uintptr_t)sw->params & 7))
+        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor [n_variants][6][ld]", what);
+    if (sw->work_bytes < tmh_battery_sweep_work_bytes(1, 1, sw->n_variants))
+        return fail(TMH_E_INVAL, "%s work buffer too small: %zu < %zu", what, sw->work_bytes,
+                    tmh_battery_sweep_work_bytes(1, 1, sw->n_variants));
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (eng->kp.precision != TMH_FP64)   // (as tmh_set_battery)
+        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
+                                 "expansion, and the state of charge depends on every earlier second)", what);
+    if (int rc = set_interval_table(eng, TBL_SWEEP, &sw->table)) return rc;
+    eng->sweep = *sw;
+    return TMH_OK;
+}
+
 // the battery fleet series: tmh_set_series' struct cases in its own words (the struct first, as the tables'
 // setters: a bad one is named whatever the engine), and the battery kind's engines only
 int tmh_set_battery_fleet(struct tmh_engine* eng, const tmh_series* fleet)
@@ -4249,6 +4428,18 @@ static int check_interval_tables(const tmh_engine* eng, uint32_t n_chains, int64
     if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
         return fail(TMH_E_INVAL, "%s are set: no traces in the same call (a caller with traces can sum them)", what);
     if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
+    if (eng->tables[TBL_SWEEP].set) {   // the battery sweep runs alone (kind: the first set one, so another table when there is one)
+        if (kind != TBL_SWEEP)
+            return fail(TMH_E_INVAL, "the battery sweep and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
+        if (eng->has_fleet)
+            return fail(TMH_E_INVAL, "the battery sweep and a battery fleet series are both set: the fleet series is the battery "
+                                     "kind's (one battery per chain)");
+        if (eng->kp.sites)
+            return fail(TMH_E_INVAL, "the battery sweep cannot run with per-chain sites (tmh_set_sites)");
+        if (eng->sweep.work_bytes < tmh_battery_sweep_work_bytes(n_chains, n_steps, eng->sweep.n_variants))
+            return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->sweep.work_bytes,
+                        tmh_battery_sweep_work_bytes(n_chains, n_steps, eng->sweep.n_variants));
+    }
     if (eng->tables[TBL_BATTERY].set && kind != TBL_BATTERY)   // (kind: the first set one, so another table, storage included)
         return fail(TMH_E_INVAL, "the battery kind and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
     if (kind == TBL_BATTERY && eng->battery.work_bytes < tmh_storage_work_bytes(n_chains, n_steps))
@@ -4652,6 +4843,43 @@ static int phase_expand(const StepCtx& c)
                         launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY>{}, st, btv, sv);
                     }
                     eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
+                }
+            } else if (table == TBL_SWEEP) {
+                // the battery sweep (fp64, one site: tmh_set_battery_sweep): the battery kind's three launches per
+                // group of up to SWEEP_KV variants, group after group in stream order, each variant with its own
+                // table, work buffer, soc row and parameters; the statistics go to the first group's replay
+                // launch alone (the per-second body is the same in every group: they would count twice)
+                if constexpr (!F32 && !S) {
+                    const tmh_battery_sweep& sw = eng->sweep;
+                    const uint64_t ld = c.ivv.ld;
+                    const uint64_t n_iv = ((uint64_t)eng->tables[TBL_SWEEP].t.n_steps + c.ivv.interval_s - 1) / c.ivv.interval_s;
+                    const uint64_t tstride = n_iv * TMH_BATTERY_COLS * ld;
+                    const uint64_t wstride = tmh_storage_work_bytes(c.n_chains, c.n_steps) / sizeof(long long);
+                    for (uint32_t v0 = 0; v0 < sw.n_variants; v0 += SWEEP_KV) {
+                        const uint32_t nv = std::min<uint32_t>(SWEEP_KV, sw.n_variants - v0);
+                        IntervalsView iv = c.ivv;
+                        iv.sum += (size_t)v0 * tstride;
+                        long long* const work = reinterpret_cast<long long*>(sw.work) + (size_t)v0 * wstride;
+                        long long* const soc = reinterpret_cast<long long*>(sw.soc) + (size_t)v0 * ld;
+                        const long long* const params = reinterpret_cast<const long long*>(sw.params) + (size_t)v0 * 6 * ld;
+                        const BatteryView btv{StorageView{iv, work, 0, 0, 0}, params};
+                        const SweepView swv{btv, tstride, wstride, nv, 0u};
+                        const StatsView& gsv = v0 == 0 ? sv : StatsView{};
+                        // a group of one variant is the battery kind itself: its own instantiations, at their
+                        // occupancy, instead of SWEEP_KV - 1 idle sets of registers at the sweep's
+                        hipEvent_t t = eng->mark(c.s);
+                        if (nv == 1) launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_MAP>{}, st, btv, StatsView{});
+                        else launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_MAP | OUT_SWEEP>{}, st, swv, StatsView{});
+                        eng->close(TMH_K_STORAGE_MAP, t, c.s);
+                        t = eng->mark(c.s);
+                        hipLaunchKernelGGL(battery_sweep_scan_kernel, dim3(c.cb(), nv), dim3(256), 0, c.s, work, soc, params,
+                                           eng->kp.ids, c.n_chains, c.sg.nblk, wstride, ld);
+                        eng->close(TMH_K_STORAGE_SCAN, t, c.s);
+                        t = eng->mark(c.s);
+                        if (nv == 1) launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY>{}, st, btv, gsv);
+                        else launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_SWEEP>{}, st, swv, gsv);
+                        eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
+                    }
                 }
             } else if (table != TBL_KINDS) {
                 // an interval table (+ statistics when given, binned as the statistics-only kernel of the

@@ -1543,7 +1543,10 @@ enum OutKind : int {
     OUT_LOSSY = 64,
     // flag on OUT_STORAGE | OUT_LOSSY, replay pass only: the battery fleet series beside the table -- the second's
     // quantities reduced across the chains into rows of TMH_BATTERY_FLEET_COLS sums; TMH_OUT_BATTERY_FLEET
-    OUT_FLEET = 128
+    OUT_FLEET = 128,
+    // flag on OUT_STORAGE | OUT_LOSSY, both passes: the battery sweep (tmh_battery_sweep) -- a lane carries up to
+    // SWEEP_KV batteries of its chain through one pass over the seconds; TMH_OUT_BATTERY_SWEEP
+    OUT_SWEEP = 256
 };
 constexpr int out_base(int out) { return out & 7; }
 // no trace: the statistics-only expansion's workgroup shape
@@ -1686,6 +1689,17 @@ struct BatteryView {
 struct BatteryFleetView {
     BatteryView bt;
     SeriesView se;
+};
+// The battery sweep (OUT_SWEEP): one launch's group of nv <= SWEEP_KV variants of every chain.  `bt` is the battery
+// kind's view of the group's first variant; variant v's table lies tstride elements, its work buffer wstride
+// elements and its parameters 6 * ld elements after variant v - 1's.  Variants nv .. SWEEP_KV - 1 of a short last
+// group are empty lossless batteries in registers: never loaded, stored or flushed, their seconds skipped (nv is
+// wave-uniform: scalar branches).  A group of one variant runs the battery kind's own instantiations instead.
+constexpr int SWEEP_KV = 4;
+struct SweepView {
+    BatteryView bt;
+    uint64_t tstride, wstride;
+    uint32_t nv, pad;
 };
 // The state of charge (0 <= x < 2^40) in two halves of FLEET_SOC_HALF bits: 32 lanes of either fit an int32 partial
 constexpr int FLEET_SOC_HALF = 20;

@@ -91,6 +91,9 @@ for _kind, _t in _TABLES.items():   # no table beside battery storage, whichever
     if _kind != "battery":
         _t["enable_excludes"] += (("_battery", "the battery kind is enabled: one table output per sim "
                                                "(the battery kind runs alone)"),)
+    # (enable_battery_sweep: the battery sweep, a kind with descriptor and attributes of its own)
+    _t["enable_excludes"] += (("_battery_sweep", "the battery sweep is enabled: one table output per sim "
+                                                 "(the battery sweep runs alone)"),)
 
 
 class BatchedSim:
@@ -196,6 +199,8 @@ class BatchedSim:
         self._battery_desc = None
         self.battery_fleet_raw = None   # int64 [n_groups, n_steps, 8]: the battery fleet series (enable_battery_fleet)
         self._battery_fleet = None
+        self.battery_sweep_raw = None   # int64 [K, n_intervals, 10, n]: the battery sweep's tables (enable_battery_sweep)
+        self._battery_sweep = self._sweep_args = self._sweep_work = self._sweep_desc = None
         self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
@@ -542,6 +547,107 @@ class BatchedSim:
         energy_wh_loss and round_trip, [n_intervals, n] each."""
         return self._table_watts("battery")
 
+    # ------------------------------------------------------------------ the battery sweep
+    def enable_battery_sweep(self, n_steps, interval_s=900, *, n_variants=None, capacity_wh=None, charge_w=None,
+                             discharge_w=None, charge_eff=1.0, discharge_eff=1.0, standby_w=0.0, soc0_wh=0.0, step0=None,
+                             buffer=None, soc=None, params=None):
+        """enable_battery for K candidate batteries per chain in one run (tmhpvsim_amd.battery, tmh_battery_sweep):
+        every chain -- the same pv and meter second for second -- behind each of K batteries, variant v's table
+        and state of charge bit for bit what enable_battery gives for its parameters.  Each quantity is a scalar,
+        a sequence of K values (one per variant, uniform over the chains) or a [K, n] array
+        (battery.quantize_sweep_params); or pass params, a ready int64 device tensor [K, 6, n] (checked with
+        battery.check_params per variant).  Returns the raw int64 tensor [K, n_intervals, 10, n];
+        `sim.soc` is the int64 [K, n] state of charge, `sim.battery_params` the parameters [K, 6, n].  buffer,
+        soc, params: tensors of those shapes to use, possibly column slices of wider [.., N] tensors of one width.
+        fp64 only, no traces, no fleet series, no battery fleet series, no other table, no per-chain sites;
+        compaction is allowed.  n_steps=None switches the output off."""
+        torch = _torch()
+        L = self.L
+        if n_steps is None:
+            _lib.check(L.tmh_set_battery_sweep(self._eng, None))
+            if self._battery_sweep is not None:
+                self.soc = self.battery_params = None
+            self.battery_sweep_raw = self._battery_sweep = self._sweep_args = self._sweep_work = self._sweep_desc = None
+            return None
+        if self.precision != _lib.TMH_FP64:
+            raise ValueError("the battery sweep needs precision='fp64': an fp32 engine replaces its guard-band seconds "
+                             "after the expansion, and the state of charge depends on every earlier second")
+        if self._series is not None:
+            raise ValueError("a fleet series is enabled: one table output per sim (the battery sweep runs alone)")
+        if self._battery_fleet is not None:
+            raise ValueError("a battery fleet series is enabled: it is the battery kind's (the battery sweep runs alone)")
+        for kind, t in _TABLES.items():
+            if getattr(self, "_" + kind) is not None:
+                raise ValueError(f"{t['name']} is enabled: one table output per sim (the battery sweep runs alone)")
+        if self.sites is not None:
+            raise ValueError("the battery sweep cannot run with per-chain sites")
+        from . import battery
+        n_steps, interval_s = int(n_steps), int(interval_s)
+        if n_steps < 1 or interval_s < 1 or interval_s > battery.MAX_INTERVAL_S:
+            raise ValueError(f"enable_battery_sweep: n_steps >= 1 and 1 <= interval_s <= {battery.MAX_INTERVAL_S}")
+        if params is None:
+            if capacity_wh is None or charge_w is None or discharge_w is None:
+                raise ValueError("enable_battery_sweep: capacity_wh, charge_w and discharge_w (or params) are required")
+            host = battery.quantize_sweep_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
+                                                 n=self.n, n_variants=n_variants)
+            params = torch.from_numpy(host).to(self.device)
+        else:
+            if (params.dtype != torch.int64 or params.device != self.device or params.dim() != 3
+                    or tuple(params.shape[1:]) != (6, self.n) or (self.n > 1 and params.stride(2) != 1)):
+                raise ValueError(f"battery sweep params must be an int64 [K, 6, {self.n}] tensor on {self.device}, chains contiguous")
+            host = battery.check_sweep_params(params)
+        K = int(host.shape[0])
+        if n_variants is not None and int(n_variants) != K:
+            raise ValueError(f"enable_battery_sweep: n_variants {n_variants} but parameters of {K} variants")
+        if soc is None:
+            soc = torch.from_numpy(battery.quantize_sweep_soc(soc0_wh, host)).to(self.device)
+        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (K, self.n)
+              or (self.n > 1 and soc.stride(1) != 1)):
+            raise ValueError(f"battery sweep soc must be an int64 [{K}, {self.n}] tensor on {self.device}, chains contiguous")
+        nk, nc = battery.n_intervals(n_steps, interval_s), len(battery.COLUMNS)
+        if buffer is None:
+            buffer = torch.zeros(K, nk, nc, self.n, dtype=torch.int64, device=self.device)
+        elif buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (K, nk, nc, self.n):
+            raise ValueError(f"battery sweep buffer must be an int64 [{K}, {nk}, {nc}, {self.n}] tensor on {self.device}")
+        ld = int(buffer.stride(2))
+        if (ld < self.n or (self.n > 1 and buffer.stride(3) != 1) or (nk > 1 and buffer.stride(1) != nc * ld)
+                or (K > 1 and buffer.stride(0) != nk * nc * ld)):
+            raise ValueError(f"battery sweep buffer strides {tuple(buffer.stride())}: need ({nk * nc} ld, {nc} ld, ld, 1) "
+                             f"with ld >= {self.n}")
+        if int(params.stride(1)) != ld or (K > 1 and (int(params.stride(0)) != 6 * ld or int(soc.stride(0)) != ld)):
+            raise ValueError(f"battery sweep params strides {tuple(params.stride())}, soc strides {tuple(soc.stride())}: need "
+                             f"(6 ld, ld, 1) and (ld, 1) with the table's ld {ld}: slice them from tensors of the same width")
+        table = _lib.Intervals(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
+        nb = L.tmh_battery_sweep_work_bytes(self.n, min(n_steps, 86400), K)
+        work = self._sweep_work
+        if work is None or work.numel() < nb:
+            work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
+        sw = _lib.BatterySweep(table, soc.data_ptr(), work.data_ptr(), work.numel(), params.data_ptr(), K)
+        _lib.check(L.tmh_set_battery_sweep(self._eng, C.byref(sw)))
+        self._battery_sweep, self._sweep_desc, self._sweep_args, self._sweep_work = table, sw, (soc, params), work
+        self.battery_sweep_raw, self.soc, self.battery_params = buffer, soc, params
+        return buffer
+
+    def _sweep_window(self, win):
+        """run(): the sweep's work buffer holds a window of `win` steps (a larger one is allocated and the
+        descriptor set again; the sim has synchronised nothing: the old buffer's launches are in stream order)."""
+        sw = self._sweep_desc
+        need = self.L.tmh_battery_sweep_work_bytes(self.n, int(win), int(sw.n_variants))
+        if self._sweep_work.numel() < need:
+            _torch().cuda.synchronize(self.device)
+            self._sweep_work = _torch().empty(need, dtype=torch_uint8(), device=self.device)
+            sw.work, sw.work_bytes = self._sweep_work.data_ptr(), self._sweep_work.numel()
+            _lib.check(self.L.tmh_set_battery_sweep(self._eng, C.byref(sw)))
+
+    def battery_sweep(self):
+        """The sweep's tables in watts and watt-hours: a list of battery.to_watts dicts, one per variant."""
+        from .battery import to_watts
+        if self.battery_sweep_raw is None:
+            raise ValueError("no battery sweep tables: call enable_battery_sweep first")
+        _torch().cuda.synchronize(self.device)
+        t = self._battery_sweep
+        return [to_watts(raw, t.interval_s, n_steps=t.n_steps) for raw in self.battery_sweep_raw]
+
     # ------------------------------------------------------------------ the battery fleet series
     def enable_battery_fleet(self, n_steps, step0=None, group_chains=0, buffer=None):
         """Beside the battery kind's table (enable_battery first), accumulate the battery fleet series
@@ -642,6 +748,15 @@ class BatchedSim:
                 raise ValueError(t["no_trace"])
             if self.step < tb.step0 or self.step + n_steps > tb.step0 + tb.n_steps:
                 raise ValueError(f"steps [{self.step}, +{n_steps}) outside the {t['noun']} [{tb.step0}, +{tb.n_steps})")
+        if self._battery_sweep is not None:   # (likewise; compact=True is allowed)
+            tb = self._battery_sweep
+            if self._series is not None:
+                raise ValueError("the battery sweep and a fleet series are both enabled: one of the two per sim")
+            if trace:
+                raise ValueError("a battery sweep run takes no traces (trace=()): run the batteries over the traces instead "
+                                 "(battery.sweep_from_traces)")
+            if self.step < tb.step0 or self.step + n_steps > tb.step0 + tb.n_steps:
+                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the battery sweep tables [{tb.step0}, +{tb.n_steps})")
         if self._battery_fleet is not None:   # (the library refuses each too, window by window)
             if compact:
                 raise ValueError("a battery fleet series cannot run compacted (a compacted tile would mix groups)")
@@ -666,6 +781,8 @@ class BatchedSim:
         win = max(1, min(int(window), n_steps))
         if self._storage is not None or self._battery is not None:
             self._storage_window(win)
+        if self._battery_sweep is not None:
+            self._sweep_window(win)
         if compact and n_steps > win:
             with torch.cuda.device(self.device):
                 self._run_compacted(n_steps, win, st)
