@@ -38,7 +38,9 @@
  *    battery fleet series (tmh_set_battery_fleet: per second, summed over the chains, what the
  *    fleet draws, feeds in, stores and charges behind its batteries), or the battery sweep
  *    (tmh_battery_sweep: the battery kind's table and state of charge for each of up to
- *    TMH_BATTERY_SWEEP_MAX candidate batteries per chain, in one run).
+ *    TMH_BATTERY_SWEEP_MAX candidate batteries per chain, in one run), or battery dispatch
+ *    (tmh_dispatch: the battery kind with a charge threshold, a discharge threshold and a
+ *    feed-in limit per chain, the curtailed energy and the peaks behind the battery).
  *  - `stream` is a hipStream_t (NULL = default stream); all work is enqueued
  *    asynchronously on it.  One engine per device; not re-entrant per engine.
  */
@@ -384,6 +386,56 @@ typedef struct tmh_battery_sweep {
     uint32_t n_variants;      /* 1 .. TMH_BATTERY_SWEEP_MAX */
 } tmh_battery_sweep;
 
+/* Battery dispatch: the battery kind (tmh_battery above) under another control rule than greedy
+ * self-consumption.  The battery charges only from the surplus above a threshold, discharges only into the
+ * deficit above a threshold, and what is left of the surplus is fed in up to a limit, the rest curtailed.
+ * tmh_battery stays as it is; this kind reproduces it bit for bit in columns 0-9 and soc when every chain has
+ * Tc = Td = 0 and L = 2^27, and its column 10 is then 0.  Integers in the series' units as above.
+ * params: device int64 [9][ld] of the caller, laid out and read as tmh_battery's; rows 0-5 are tmh_battery's
+ * exactly (C, Pc, Pd, ec, ed, sigma), then
+ *   row 6  charge threshold Tc: the battery charges only from the surplus above it       0 .. 2^27
+ *   row 7  discharge threshold Td: it discharges only into the deficit above it          0 .. 2^27
+ *   row 8  feed-in limit L; 2^27 means none, since a second's surplus stays below 2^26    0 .. 2^27
+ * each read per chain and clamped into its range as a lane loads it; no address depends on a value.  For an
+ * ok second with d = q(pv) - q(meter) and the SoC x before it:
+ *   a  = d >= 0 ?  min(max(d - Tc, 0), Pc)  :  -min(max(-d - Td, 0), Pd)       asked at the meter side
+ *   s, x1, g, b, x'   exactly tmh_battery's rule applied to this a
+ *   r  = d - b                      what is left at the meter (b lies between 0 and d: r has d's sign or is 0)
+ *   import_b  = max(-r, 0)          surplus = max(r, 0)
+ *   export_b  = min(surplus, L)     fed in
+ *   curtailed = surplus - export_b  what the inverter throws away
+ *   loss      = b - (x' - x)
+ * A second that is not ok leaves x unchanged and adds nothing.  The ask depends on d and the chain's constants
+ * only, so the second's map of x is tmh_battery's pair of clamped additions: its three launches carry over.
+ * table.sum: device int64 [n_intervals][TMH_DISPATCH_COLS][ld], zero-initialised by the caller.
+ * Over the ok seconds of interval k:
+ *   [0..3] tmh_intervals' columns exactly            (added; [0] stays the available PV: produced = [0] - [10])
+ *   [4] sum of import_b    [5] sum of export_b       (added; export_b after the limit)
+ *   [6] sum of max(b, 0)   [7] sum of max(-b, 0)     (added)
+ *   [8] tmh_storage's SoC key                        (maximum)
+ *   [9] sum of loss        [10] sum of curtailed     (added)
+ *   [11] peak import behind the battery: the maximum of tmh_demand's key (v << 32) | (0xFFFFFFFF - o), v = import_b
+ *   [12] peak feed-in: the same key with v = export_b
+ * [11] and [12]: 0 means no ok second; an interval without feed-in holds key(0, its first ok second), as
+ * tmh_demand.  For every cell [4] - [5] == [1] - [0] + [6] - [7] + [10], columns 4-7, 9 and 10 are >= 0,
+ * [6] - [7] - [9] is the interval's SoC change and the peak in [12] is <= L.  Reductions: with Tc = Td = 0 and
+ * L = 2^27, columns 0-9 and soc are tmh_set_battery's bit for bit and column 10 is 0; with C = 0 and L = 2^27,
+ * columns 11 and 12 are the fp64 demand kind's columns 6 and 7; with C = 0 and any L, [5] + [10] is the
+ * registers' export.  (The two C = 0 reductions are exact for ec = 2^16.  With ec < 2^16 an ask of exactly one
+ * unit stores s = 0, so g == s and tmh_battery's rule gives b = a = 1: that unit is taken from the surplus and
+ * lost, in this kind as in tmh_battery, so such a second's export_b is one unit below the registers'.)  The bits do not depend on windows, pipelining, batches, column slices or compaction and
+ * equal a sequential loop over the traces.  fp64 engines only, as tmh_battery.  soc, work and work_bytes:
+ * tmh_battery's (tmh_storage_work_bytes). */
+#define TMH_DISPATCH_COLS 13
+#define TMH_DISPATCH_PARAMS 9
+typedef struct tmh_dispatch {
+    tmh_intervals table;      /* sum is [n_intervals][13][ld] */
+    int64_t* soc;             /* device [ld]: as tmh_battery's */
+    void* work;               /* device scratch */
+    size_t work_bytes;        /* >= tmh_storage_work_bytes(n_chains, n_steps) of the largest window */
+    const int64_t* params;    /* device [9][ld], ld = table.ld */
+} tmh_dispatch;
+
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
 /* TMH_SERIES_FRAC_BITS and TMH_SERIES_MAX_W as the library was built with them */
@@ -607,6 +659,15 @@ int tmh_set_battery_fleet(struct tmh_engine* eng, const tmh_series* fleet);
  * tmh_set_battery_fleet set; per-chain sites (tmh_set_sites). */
 size_t tmh_battery_sweep_work_bytes(uint32_t n_chains, uint32_t n_steps, uint32_t n_variants);
 int tmh_set_battery_sweep(struct tmh_engine* eng, const tmh_battery_sweep* sw);
+/* Battery dispatch (tmh_dispatch above): as tmh_set_battery, with nine parameter rows and thirteen columns.
+ * Every later expansion clamps dp->soc into [0, C], advances it over its window and adds the window to
+ * dp->table.sum in the battery kind's three launches (the same TMH_K_STORAGE_* slots time them); NULL
+ * switches it off.  Refused here (TMH_E_INVAL, the messages name "dispatch"): everything tmh_set_battery
+ * refuses.  Refused at a step / expansion call or a walk of that window, before any launch: everything
+ * tmh_set_battery's step refuses; any other table kind set too, in either order (battery storage, the
+ * battery kind and the battery sweep included); a fleet series set too; tmh_set_battery_fleet set too.  The
+ * parameters' values are not read on the host: the kernels clamp them. */
+int tmh_set_dispatch(struct tmh_engine* eng, const tmh_dispatch* dp);
 /* Tests only: the fp32 guard-band records (chain, block) the last expansion on
  * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
  * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
@@ -719,7 +780,8 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * TMH_OUT_DEMAND (demand registers, with or without statistics), TMH_OUT_STORAGE (battery
  * storage: the replay pass, the last of the kind's three launches, with or without statistics),
  * TMH_OUT_BATTERY (the battery kind, likewise), TMH_OUT_BATTERY_FLEET (the battery kind with its fleet
- * series: the replay pass that fills both), TMH_OUT_BATTERY_SWEEP (the battery sweep), plus
+ * series: the replay pass that fills both), TMH_OUT_BATTERY_SWEEP (the battery sweep),
+ * TMH_OUT_DISPATCH (battery dispatch: its replay pass, with or without statistics), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
@@ -733,6 +795,7 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
 #define TMH_OUT_BATTERY 8
 #define TMH_OUT_BATTERY_FLEET 9
 #define TMH_OUT_BATTERY_SWEEP 10
+#define TMH_OUT_DISPATCH 11
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

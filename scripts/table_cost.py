@@ -3,12 +3,13 @@
 kernel) of the statistics-only expansion and of the expansions with a table, same chains,
 same window, same process, the runs alternating.
 
-    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet|battery_sweep
+    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet|battery_sweep|dispatch
                                  [--variants 5] [--chains 65536] [--steps 86400]
                                  [--interval 900] [--rounds 5] [--precision fp32]
                                  [--start "2019-09-05 00:00:00"] [--out FILE.json]
                                  [--modules 1 --capacity-wh 5000 --charge-w 2500 --discharge-w 2500]
                                  [--charge-eff 0.95 --discharge-eff 0.95 --standby-w 2]
+                                 [--charge-above-w 500 --discharge-above-w 200 --feed-in-limit-w 1000]
 
 The runs of a kind, each with the same statistics beside its table:
   intervals: OUT_STATS and OUT_INTERVALS;
@@ -36,6 +37,12 @@ The runs of a kind, each with the same statistics beside its table:
              sweep's slots sum its groups' launches); the yardstick is K x the battery kind's median of the same run:
              ratio_sweep_k_battery = sweep / (K x battery) for the whole expansion and per launch, beside the spread
              of each run's own rounds.
+  dispatch:  OUT_BATTERY and OUT_DISPATCH, battery's setting with statistics beside both -- the battery kind and battery
+             dispatch with the same batteries plus --charge-above-w, --discharge-above-w and --feed-in-limit-w,
+             alternating; the script checks that the thresholds and the limit bind (less is charged and discharged
+             than under the battery kind, energy is curtailed, the peak fed in is the limit) and the dispatch
+             table's identities.  The kind's three launches are timed for both; dispatch / battery for the whole
+             expansion and per launch, with medians and ranges, beside the spread of the battery kind's own rounds.
 The script checks each run's variant, these identities (on the warm-up round's tables), that
 the statistics of all runs agree bit for bit and that every table's ok seconds equal the
 histogram's count.  One warm-up round, then --rounds timed ones.  Prints one JSON line: the
@@ -62,6 +69,7 @@ RUNS = {
     # (the table of both runs is the battery kind's; "battery_fleet" also enables the battery fleet series)
     "battery_fleet": (("battery", "battery"), ("battery_fleet", "battery")),
     "battery_sweep": (("battery", "battery"), ("battery_sweep", "battery_sweep")),   # (sweep_cost: a loop of its own)
+    "dispatch": (("battery", "battery"), ("dispatch", "dispatch")),                  # (dispatch_cost: likewise)
 }
 
 
@@ -178,6 +186,72 @@ def sweep_cost(a, mp, lossy):
     return res
 
 
+def dispatch_cost(a, mp, lossy):
+    """--kind dispatch: the battery kind and battery dispatch over the same batteries, alternating."""
+    import torch
+    from tmhpvsim_amd import _lib
+    from tmhpvsim_amd.engine import BatchedSim
+    rule = dict(charge_above_w=a.charge_above_w, discharge_above_w=a.discharge_above_w, feed_in_limit_w=a.feed_in_limit_w)
+    parts = (("map", _lib.K_STORAGE_MAP), ("scan", _lib.K_STORAGE_SCAN), ("replay", _lib.K_STORAGE_REPLAY))
+    labels = ("battery", "dispatch")
+
+    def one(label):
+        sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=mp, precision="fp64", device="cuda:0", horizon=a.steps)
+        sim.enable_stats()
+        raw = sim.enable_battery(a.steps, a.interval, **lossy) if label == "battery" else \
+            sim.enable_dispatch(a.steps, a.interval, **lossy, **rule)
+        _lib.check(sim.L.tmh_profile_enable(sim._eng, 1))
+        sim.run(a.steps, trace=(), window=a.steps)
+        torch.cuda.synchronize()
+        ms, launches = _lib.profile_read(sim._eng, _lib.K_EXPAND)
+        want = (_lib.OUT_BATTERY if label == "battery" else _lib.OUT_DISPATCH) | _lib.OUT_FP64
+        assert launches == 1 and sim.L.tmh_engine_last_expand(sim._eng) == want, (launches, want)
+        pm = {}
+        for name, kk in parts:
+            pm[name], pn = _lib.profile_read(sim._eng, kk)
+            assert pn == 1
+        assert int(raw[:, 2].sum()) == int(sim.hist.sum()) > 0
+        return ms, pm, raw, sim.hist.clone()
+
+    def check(bt, dp):   # the warm-up round's tables: the same seconds, the rule binds, the dispatch table's identities
+        b, d = bt[2], dp[2]
+        assert torch.equal(d[:, :4], b[:, :4]) and torch.equal(bt[3], dp[3])
+        assert bool((d[:, 4:8] >= 0).all()) and bool((d[:, 9:11] >= 0).all())
+        assert torch.equal(d[:, 4] - d[:, 5], d[:, 1] - d[:, 0] + d[:, 6] - d[:, 7] + d[:, 10])
+        assert torch.equal(d[:, 11] != 0, d[:, 2] > 0) and torch.equal(d[:, 12] != 0, d[:, 2] > 0)
+        lim = int(round(a.feed_in_limit_w * 4096))
+        assert int((d[:, 12] >> 32).max()) == lim and int(d[:, 10].sum()) > 0                    # the limit binds
+        assert 0 < int(d[:, 6].sum()) < int(b[:, 6].sum()) and 0 < int(d[:, 7].sum()) < int(b[:, 7].sum())   # the thresholds bind
+        return dict(curtailed_share=int(d[:, 10].sum()) / int(d[:, 0].sum()), curtail_cells=int((d[:, 10] > 0).sum()),
+                    charge_dispatch_over_battery=int(d[:, 6].sum()) / int(b[:, 6].sum()),
+                    discharge_dispatch_over_battery=int(d[:, 7].sum()) / int(b[:, 7].sum()))
+
+    binds = check(one("battery"), one("dispatch"))   # warm-up: code objects, allocator
+    t = {k: [] for k in labels}
+    pt = {k: {name: [] for name, _ in parts} for k in labels}
+    for _ in range(a.rounds):
+        for label in labels:
+            ms, pm, _raw, _hist = one(label)
+            t[label].append(ms)
+            for name in pm:
+                pt[label][name].append(pm[name])
+            del _raw, _hist
+    med = {k: statistics.median(t[k]) for k in labels}
+    pmed = {k: {name: statistics.median(v) for name, v in pt[k].items()} for k in labels}
+    return dict(device=torch.cuda.get_device_name(0), chains=a.chains, steps=a.steps, interval_s=a.interval, precision="fp64",
+                start=a.start, rounds=a.rounds, modules=a.modules, battery=lossy, rule=rule, **binds,
+                **{f"{k}_ms": t[k] for k in labels}, **{f"{k}_median_ms": med[k] for k in labels},
+                **{f"{k}_range_ms": [min(t[k]), max(t[k])] for k in labels},
+                **{f"{k}_{name}_ms": v for k in labels for name, v in pt[k].items()},
+                **{f"{k}_{name}_median_ms": v for k in labels for name, v in pmed[k].items()},
+                **{f"{k}_{name}_range_ms": [min(v), max(v)] for k in labels for name, v in pt[k].items()},
+                ratio_dispatch_battery=med["dispatch"] / med["battery"],
+                **{f"ratio_{name}_dispatch_battery": pmed["dispatch"][name] / pmed["battery"][name] for name, _ in parts},
+                battery_spread=max(t["battery"]) / min(t["battery"]),
+                **{f"battery_{name}_spread": max(v) / min(v) for name, v in pt["battery"].items()},
+                build_stamp=_lib.loaded_stamp())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", choices=tuple(RUNS), required=True)
@@ -196,8 +270,11 @@ def main():
     ap.add_argument("--discharge-eff", type=float, default=0.95)
     ap.add_argument("--standby-w", type=float, default=2.0)
     ap.add_argument("--variants", type=int, default=5, help="--kind battery_sweep: the batteries per chain")
+    ap.add_argument("--charge-above-w", type=float, default=500.0, help="--kind dispatch: the charge threshold")
+    ap.add_argument("--discharge-above-w", type=float, default=200.0, help="--kind dispatch: the discharge threshold")
+    ap.add_argument("--feed-in-limit-w", type=float, default=1000.0, help="--kind dispatch: the feed-in limit")
     a = ap.parse_args()
-    if a.kind in ("storage", "battery", "battery_fleet", "battery_sweep"):
+    if a.kind in ("storage", "battery", "battery_fleet", "battery_sweep", "dispatch"):
         a.precision = "fp64"   # (the kind's engines)
     import torch
     from tmhpvsim_amd import _lib
@@ -222,8 +299,8 @@ def main():
     battery = dict(capacity_wh=a.capacity_wh, charge_w=a.charge_w, discharge_w=a.discharge_w, soc0_wh=a.capacity_wh / 2)
     lossy = dict(battery, charge_eff=a.charge_eff, discharge_eff=a.discharge_eff, standby_w=a.standby_w)
     enable_kw = {"storage": battery, "battery": lossy}
-    if a.kind == "battery_sweep":
-        line = json.dumps(sweep_cost(a, mp, lossy))
+    if a.kind in ("battery_sweep", "dispatch"):
+        line = json.dumps(sweep_cost(a, mp, lossy) if a.kind == "battery_sweep" else dispatch_cost(a, mp, lossy))
         print(line)
         if a.out:
             with open(a.out, "w") as fh:

@@ -24,6 +24,9 @@ tmhpvsim/metersim.py:79-95).
                                             --discharge-w P[,P..] [--charge-eff E[,E..]] [--discharge-eff E[,E..]]
                                             [--standby-w P[,P..]] [--soc0-wh X[,X..]] [--all-chains NPZ]
                                             [--fleet CSV [--bin S]] [--start T --seconds S --seed K]
+    python -m tmhpvsim_amd.cli dispatch FILE --batch N --no-realtime --interval S <the battery command's options>
+                                             [--charge-above-w P[,P..]] [--discharge-above-w P[,P..]]
+                                             [--feed-in-limit-w P|none[,..]] [--all-chains NPZ]
 
 Without --batch the commands are the reference's AMQP pipelines (a fanout
 exchange carrying one JSON float per second, pvsim.py:43-84, metersim.py:13-62):
@@ -75,6 +78,12 @@ writes every chain's raw table and its arrays to an .npz.  --fleet CSV also writ
 (tmhpvsim_amd.battery.fleet_to_watts: what the whole batch does second by second behind its batteries) as means
 per ok chain-second over bins of --bin seconds: header `time,n_ok,meter,pv,import_w,export_w,charge_w,discharge_w,
 soc_wh,covered`; without it the command's outputs are as before, byte for byte.
+`dispatch` is `battery` under thresholds and a feed-in limit (tmhpvsim_amd.dispatch): the battery charges only
+from the surplus above --charge-above-w, discharges only into the deficit above --discharge-above-w, and what is
+left of the surplus is fed in up to --feed-in-limit-w (`none`, the default: no limit), the rest curtailed.  Lists
+are dealt round-robin as `battery` deals them.  The CSV is `battery`'s with `curtailed_wh,peak_import_w,
+peak_export_w` after `n_ok` (export_wh is what was fed in after the limit, pv_wh the available PV); --all-chains
+writes every chain's raw table and its arrays to an .npz.
 There is no CPU fallback: the batch mode fails if the engine cannot run.
 """
 from __future__ import annotations
@@ -126,7 +135,7 @@ def _fleet_run(n, start, seconds, seed, precision, bin_s):
 
 
 def _table_run(kind, n, start, seconds, seed, precision, interval_s, fleet_bin=None, **enable_kw):
-    """An engine run with the interval table `kind` ("intervals", "registers", "demand", "storage" or "battery")
+    """An engine run with the interval table `kind` ("intervals", "registers", "demand", "storage", "battery" or "dispatch")
     only: the raw table, its watt / watt-hour arrays and, with fleet_bin (the battery kind), the battery fleet
     series' means per bin of fleet_bin seconds (else None).  enable_kw: the kind's own arguments."""
     from .engine import BatchedSim
@@ -267,6 +276,8 @@ TABLE_CSV = {
                 ("meter_wh", "energy_wh_meter"), ("charge_wh", "energy_wh_charge"), ("discharge_wh", "energy_wh_discharge"),
                 ("soc_wh", "soc_wh"), ("loss_wh", "energy_wh_loss"), ("n_ok", "n_ok")),
 }
+TABLE_CSV["dispatch"] = TABLE_CSV["battery"] + (("curtailed_wh", "energy_wh_curtailed"), ("peak_import_w", "peak_w_import"),
+                                                ("peak_export_w", "peak_w_export"))
 
 
 # the battery fleet series' CSV columns: (header, key of battery.fleet_to_watts)
@@ -276,7 +287,7 @@ FLEET_CSV = (("n_ok", "n_ok"), ("meter", "meter"), ("pv", "pv"), ("import_w", "i
 
 def _table_command(kind, file, batch, start, seconds, seed, precision, interval_s, all_chains, fleet=None, bin_s=1,
                    **enable_kw):
-    """The `intervals`, `registers`, `demand`, `storage` and `battery` commands: chain 0's rows to FILE, every chain
+    """The `intervals`, `registers`, `demand`, `storage`, `battery` and `dispatch` commands: chain 0's rows to FILE, every chain
     to the .npz; with `fleet` (the battery command's --fleet) the battery fleet series' means per bin to that CSV."""
     raw, out, fl = _table_run(kind, batch, start, seconds, seed, precision, interval_s,
                               fleet_bin=bin_s if fleet else None, **enable_kw)
@@ -401,6 +412,48 @@ def battery(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, 
                            capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
                            discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh).items()})
     except ValueError as e:   # (a quantity outside its range: battery.quantize_params)
+        raise click.ClickException(str(e))
+
+
+def _dealt_limit(ctx, param, value):
+    """--feed-in-limit-w: one value or a comma-separated list, each a number of watts or `none` (no limit)."""
+    if value is None:
+        return [None]
+    try:
+        return [None if v.strip().lower() == "none" else float(v) for v in str(value).split(",")]
+    except ValueError:
+        raise click.BadParameter("a number, `none`, or a comma-separated list of them")
+
+
+@main.command()
+@click.argument("file")
+@common
+@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
+@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
+              help="seconds per metering interval (a last partial interval is kept)")
+@click.option("--capacity-wh", callback=_dealt, required=True, help="battery capacity (Wh); a list is dealt to the chains")
+@click.option("--charge-w", callback=_dealt, required=True, help="charge power limit at the meter side (W)")
+@click.option("--discharge-w", callback=_dealt, required=True, help="discharge power limit at the meter side (W)")
+@click.option("--charge-eff", callback=_dealt, default="1.0", help="charge efficiency in [0.5, 1]")
+@click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]")
+@click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)")
+@click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)")
+@click.option("--charge-above-w", callback=_dealt, default="0.0", help="charge only from the surplus above this (W)")
+@click.option("--discharge-above-w", callback=_dealt, default="0.0", help="discharge only into the deficit above this (W)")
+@click.option("--feed-in-limit-w", callback=_dealt_limit, default=None, help="feed-in limit (W); `none`: no limit (the default)")
+def dispatch(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
+             charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh, charge_above_w, discharge_above_w,
+             feed_in_limit_w):
+    """Battery dispatch (thresholds, a feed-in limit) of chain 0 over --batch chains to FILE (CSV; fp64 engine run)."""
+    logging.basicConfig(level=logging.WARN - 10 * verbose)
+    _need_batch(realtime, batch, "dispatch")
+    try:
+        _table_command("dispatch", file, batch, start, seconds, seed, "fp64", interval_s, all_chains,
+                       **{k: _deal(v, batch) for k, v in dict(
+                           capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
+                           discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh, charge_above_w=charge_above_w,
+                           discharge_above_w=discharge_above_w, feed_in_limit_w=feed_in_limit_w).items()})
+    except ValueError as e:   # (a quantity outside its range: dispatch.quantize_params)
         raise click.ClickException(str(e))
 
 

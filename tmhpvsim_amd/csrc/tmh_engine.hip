@@ -91,6 +91,10 @@ constexpr int EXP_WAVES_LOSSY = 3;
 constexpr int EXP_WAVES_SWEEP_MAP = 2, EXP_WAVES_SWEEP_REPLAY = 2;
 constexpr bool out_sweep(int out) { return (out & OUT_SWEEP) != 0; }
 constexpr bool out_lossy_replay(int out) { return out_base(out) == OUT_STORAGE && (out & OUT_LOSSY) && !(out & OUT_MAP); }
+//  battery dispatch's replay pass (fp64 single-site) runs at the battery kind's shape, EXP_WAVES_LOSSY: one more
+//    64-bit sum, the two running peaks with their seconds and three more parameters live across the per-second
+//    loop take its spills from 24 to 105 VGPRs (144 B of scratch) and it runs 59.6 ms where the battery kind's
+//    replay runs 46.7 ms; at 2 waves (203 VGPRs, no spill, no scratch) it ran 62.5 ms (Battery dispatch)
 constexpr int FIX_WAVES_SITES = 1;   // min waves per SIMD of the per-site fixup (its fp64 redo recomputes the site's geometry)
 
 struct BlockDesc {                 // as of the step before the block start; -1 = none in the window
@@ -2247,6 +2251,11 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     constexpr bool SWP = (OUT & OUT_SWEEP) != 0;
     constexpr int KV = SWP ? SWEEP_KV : 1;
     static_assert(!SWP || (BAT && !FLT && !SITES), "the battery sweep: a flag of the battery kind's passes, single site");
+    // DSP: battery dispatch on the battery kind's two passes -- the lane's three more parameters (dispatch_load),
+    // dispatch_ask in place of soc_ask, and in the replay the feed-in limit: one more 64-bit sum (the curtailed
+    // energy), the demand kind's running peaks fed with import_b and export_b, and IVC = 13
+    constexpr bool DSP = (OUT & OUT_DISPATCH) != 0;
+    static_assert(!DSP || (BAT && !FLT && !SWP), "battery dispatch: a flag of the battery kind's passes, no fleet series, no sweep");
     static_assert(!STO || sizeof(R) == 8, "battery storage: fp64 engines only (no guard-band seconds)");
     // REG: the import / export registers -- the intervals' pieces, accumulators and flush, with
     // one more accumulator and IVC = 6 columns per cell instead of 4
@@ -2450,6 +2459,14 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         if (live) bp = battery_load(batp, ivv.ld, gid(kp.ids, c));
         bat_hi = max(bp.cap - (long long)bp.sigma, 0ll);
     }
+    // battery dispatch: the thresholds and the limit, and the piece's sum of the curtailed energy (REP).  Per second
+    // import_b - export_b - curtailed = b - d, so over the piece import_b = export_b + curtailed + (st_ch -
+    // st_dis) - (iv_pv - iv_m); the peaks are the demand kind's dm_im / dm_ex with their seconds.
+    DispatchParams dsp = dispatch_none();
+    long long ds_cu = 0;
+    if constexpr (DSP) {
+        if (live) dsp = dispatch_load(batp, ivv.ld, gid(kp.ids, c));
+    }
     if constexpr (REP && !SWP) {
         if (live) sx = sto.work[(size_t)b * 3 * n + c];
         sx0 = sx;
@@ -2549,7 +2566,15 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 if (im) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)im);
                 if (iv_ex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)iv_ex);
             }
-            if constexpr (BAT && REP) {
+            if constexpr (DSP && REP) {
+                const long long net = st_ch - st_dis, im = iv_ex + ds_cu + net - (iv_pv - iv_m), loss = net - (sx - sx0);
+                if (im) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)im);
+                if (iv_ex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)iv_ex);
+                if (st_ch) atomicAdd(cell + 6 * ivv.ld, (unsigned long long)st_ch);
+                if (st_dis) atomicAdd(cell + 7 * ivv.ld, (unsigned long long)st_dis);
+                if (loss) atomicAdd(cell + 9 * ivv.ld, (unsigned long long)loss);
+                if (ds_cu) atomicAdd(cell + 10 * ivv.ld, (unsigned long long)ds_cu);
+            } else if constexpr (BAT && REP) {
                 const long long net = st_ch - st_dis, im = iv_ex + net - (iv_pv - iv_m), loss = net - (sx - sx0);
                 if (im) atomicAdd(cell + 4 * ivv.ld, (unsigned long long)im);
                 if (iv_ex) atomicAdd(cell + 5 * ivv.ld, (unsigned long long)iv_ex);
@@ -2571,6 +2596,13 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                     const uint32_t ob = ivv.rel0 + j0 - iv_k * ivv.interval_s;
                     __hip_atomic_fetch_max(cell + 8 * ivv.ld, soc_key(ob + (uint32_t)(hi - 1), sx), __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT);
+                }
+                if constexpr (DSP && REP) {   // the peaks behind the battery: the demand kind's keys (below) in columns 11, 12
+                    const uint32_t ob = ivv.rel0 + j0 - iv_k * ivv.interval_s;
+                    const unsigned long long kim = demand_key((uint32_t)dm_im, ob + (dm_im > 0 ? dm_imj : (uint32_t)lo));
+                    const unsigned long long kex = demand_key((uint32_t)dm_ex, ob + (dm_ex > 0 ? dm_exj : (uint32_t)lo));
+                    __hip_atomic_fetch_max(cell + 11 * ivv.ld, kim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_max(cell + 12 * ivv.ld, kex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 if constexpr (DEM) {
                     // offset of the block's first second in interval iv_k (mod 2^32: the piece's
@@ -2599,8 +2631,9 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             st_ch = 0;
             sx0 = sx;
             if constexpr (BAT) st_dis = 0;
+            if constexpr (DSP) ds_cu = 0;
         }
-        if constexpr (DEM) {
+        if constexpr (DEM || (DSP && REP)) {
             dm_im = 0;
             dm_ex = 0;
         }
@@ -2667,7 +2700,11 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 // the battery kind (tmh_battery): what the lane's own ask stores or drains, then the standby
                 // drain; the map pass composes the two clamped additions as one, the replay pass takes the
                 // meter side b from how far the state of charge really moved
-                const int ab = soc_ask(d, bp.pc, bp.pd), s = bat_stored(ab, bp);
+                // (battery dispatch: its thresholded ask in place of the greedy one, the rest of the second unchanged)
+                int ab;
+                if constexpr (DSP) ab = dispatch_ask(d, dsp.tc, dsp.td, bp.pc, bp.pd);
+                else ab = soc_ask(d, bp.pc, bp.pd);
+                const int s = bat_stored(ab, bp);
                 if constexpr (MAP) {
                     const SocMap f = soc_compose(st_map, SocMap{(long long)(s - bp.sigma), 0, bat_hi});
                     st_map.a = ok ? f.a : st_map.a;
@@ -2679,7 +2716,23 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                     sx = ok ? max(x1 - (long long)bp.sigma, 0ll) : sx;
                     iv_m += (long long)(ok ? qm : 0);
                     if (!(__builtin_constant_p(pv) && pv == R(0))) iv_pv += (long long)(ok ? qp : 0);
-                    iv_ex += (long long)(ok ? max(d - bm, 0) : 0);
+                    if constexpr (DSP) {
+                        // what is left at the meter, r = d - b: the deficit is the import, the surplus is fed in up
+                        // to the limit and curtailed above it.  A night second's literal pv = 0 has d <= 0 and b in
+                        // [d, 0] (q(meter) >= 0), so no surplus: it neither exports nor curtails.
+                        const int r = d - bm, vi = ok ? max(-r, 0) : 0;
+                        dm_imj = vi > dm_im ? jb : dm_imj;
+                        dm_im = max(vi, dm_im);
+                        if (!(__builtin_constant_p(pv) && pv == R(0))) {
+                            const int su = ok ? max(r, 0) : 0, ve = min(su, dsp.lim);
+                            iv_ex += (long long)ve;
+                            ds_cu += (long long)(su - ve);
+                            dm_exj = ve > dm_ex ? jb : dm_exj;
+                            dm_ex = max(ve, dm_ex);
+                        }
+                    } else {
+                        iv_ex += (long long)(ok ? max(d - bm, 0) : 0);
+                    }
                     st_ch += (long long)(ok ? max(bm, 0) : 0);
                     st_dis += (long long)(ok ? max(-bm, 0) : 0);
                     if constexpr (FLT) {
@@ -3744,7 +3797,7 @@ void with_real(bool f64, F&& f)
 // one kind per engine at a step.  A kind is its column count, the expansion's and the fixup's
 // output, and the words the refusals name it by; a new kind is a row here, its columns in
 // expand_tile and the fixup, and its exported setter.
-enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_KINDS };
+enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_KINDS };
 struct TableKindInfo {
     int cols, out;      // out: TMH_OUT_* as tmh_engine_last_expand reports it (the expansion's OutKind but for TBL_BATTERY)
     const char* what;   // in the setter's and the checks' messages
@@ -3763,16 +3816,21 @@ constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
     // the battery sweep (tmh_battery_sweep: n_variants batteries per chain; tmh_engine::sweep): the battery kind's
     // three launches per group of SWEEP_KV variants on the OUT_SWEEP instantiations, TMH_OUT_BATTERY_SWEEP
     {TMH_BATTERY_COLS, TMH_OUT_BATTERY_SWEEP, "battery sweep tables", "the battery sweep"},
+    // battery dispatch (tmh_dispatch: thresholds and a feed-in limit per chain; tmh_engine::dispatch): the battery
+    // kind's three launches on the OUT_DISPATCH instantiations, TMH_OUT_DISPATCH
+    {TMH_DISPATCH_COLS, TMH_OUT_DISPATCH, "battery dispatch tables", "battery dispatch"},
 };
 static_assert(TMH_OUT_BATTERY > out_base(~0) && TMH_OUT_BATTERY < TMH_OUT_SITES, "TMH_OUT_BATTERY: a code of its own below the flags");
 static_assert(TMH_OUT_BATTERY_FLEET > TMH_OUT_BATTERY && TMH_OUT_BATTERY_FLEET < TMH_OUT_SITES, "TMH_OUT_BATTERY_FLEET: likewise");
 static_assert(TMH_OUT_BATTERY_SWEEP > TMH_OUT_BATTERY_FLEET && TMH_OUT_BATTERY_SWEEP < TMH_OUT_SITES, "TMH_OUT_BATTERY_SWEEP: likewise");
+static_assert(TMH_OUT_DISPATCH > TMH_OUT_BATTERY_SWEEP && TMH_OUT_DISPATCH < TMH_OUT_SITES, "TMH_OUT_DISPATCH: likewise");
 static_assert(interval_cols(OUT_INTERVALS) == TABLE_KINDS[TBL_INTERVALS].cols &&
                   interval_cols(OUT_REGISTERS) == TABLE_KINDS[TBL_REGISTERS].cols &&
                   interval_cols(OUT_DEMAND) == TABLE_KINDS[TBL_DEMAND].cols &&
                   interval_cols(OUT_STORAGE) == TABLE_KINDS[TBL_STORAGE].cols &&
                   interval_cols(OUT_STORAGE | OUT_LOSSY) == TABLE_KINDS[TBL_BATTERY].cols &&
-                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_SWEEP) == TABLE_KINDS[TBL_SWEEP].cols,
+                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_SWEEP) == TABLE_KINDS[TBL_SWEEP].cols &&
+                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH) == TABLE_KINDS[TBL_DISPATCH].cols,
               "the kernels' cells");
 
 }  // namespace
@@ -3799,6 +3857,7 @@ struct tmh_engine {
     tmh_storage storage{};   // tmh_set_storage: the battery, soc and the work buffer beside tables[TBL_STORAGE]
     tmh_battery battery{};   // tmh_set_battery: soc, the work buffer and the parameters beside tables[TBL_BATTERY]
     tmh_battery_sweep sweep{};   // tmh_set_battery_sweep: the variants' soc, work buffer and parameters beside tables[TBL_SWEEP]
+    tmh_dispatch dispatch{};   // tmh_set_dispatch: soc, the work buffer and the parameters beside tables[TBL_DISPATCH]
     bool has_fleet = false;  // tmh_set_battery_fleet: the battery kind's replay pass adds its window to `fleet` too
     tmh_series fleet{};
     // the first set kind (TBL_KINDS: none); a step is refused unless it is the only one (check_interval_tables)
@@ -4371,6 +4430,34 @@ int tmh_set_battery_sweep(struct tmh_engine* eng, const tmh_battery_sweep* sw)
     return TMH_OK;
 }
 
+// battery dispatch: tmh_set_battery's checks in its own words, nine parameter rows
+int tmh_set_dispatch(struct tmh_engine* eng, const tmh_dispatch* dp)
+{
+    if (!dp) {
+        if (int rc = set_interval_table(eng, TBL_DISPATCH, nullptr)) return rc;
+        eng->dispatch = tmh_dispatch{};
+        return TMH_OK;
+    }
+    const char* what = TABLE_KINDS[TBL_DISPATCH].what;
+    if (!dp->table.sum || dp->table.n_steps == 0 || dp->table.ld == 0 || ((uintptr_t)dp->table.sum & 7) ||
+        dp->table.interval_s == 0)   // (the struct's cases, in the setter's words)
+        return set_interval_table(nullptr, TBL_DISPATCH, &dp->table);
+    if (dp->table.interval_s > (1u << 23) - 1)
+        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
+                    dp->table.interval_s);
+    if (!dp->soc || ((uintptr_t)dp->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer", what);
+    if (!dp->work || ((uintptr_t)dp->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
+    if (!dp->params || ((uintptr_t)dp->params & 7))
+        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor [%d][ld]", what, TMH_DISPATCH_PARAMS);
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (eng->kp.precision != TMH_FP64)   // (as tmh_set_battery)
+        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
+                                 "expansion, and the state of charge depends on every earlier second)", what);
+    if (int rc = set_interval_table(eng, TBL_DISPATCH, &dp->table)) return rc;
+    eng->dispatch = *dp;
+    return TMH_OK;
+}
+
 // the battery fleet series: tmh_set_series' struct cases in its own words (the struct first, as the tables'
 // setters: a bad one is named whatever the engine), and the battery kind's engines only
 int tmh_set_battery_fleet(struct tmh_engine* eng, const tmh_series* fleet)
@@ -4427,6 +4514,17 @@ static int check_interval_tables(const tmh_engine* eng, uint32_t n_chains, int64
                has_demand = eng->tables[TBL_DEMAND].set;
     if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
         return fail(TMH_E_INVAL, "%s are set: no traces in the same call (a caller with traces can sum them)", what);
+    if (eng->tables[TBL_DISPATCH].set) {   // battery dispatch runs alone (kind: the first set one, so another table when there is one)
+        const char* dsp = TABLE_KINDS[TBL_DISPATCH].name;
+        if (kind != TBL_DISPATCH)
+            return fail(TMH_E_INVAL, "%s and %s are both set: one table kind per engine", dsp, TABLE_KINDS[kind].name);
+        if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
+        if (eng->has_fleet)
+            return fail(TMH_E_INVAL, "%s and a battery fleet series are both set: the fleet series is the battery kind's", dsp);
+        if (eng->dispatch.work_bytes < tmh_storage_work_bytes(n_chains, n_steps))
+            return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->dispatch.work_bytes,
+                        tmh_storage_work_bytes(n_chains, n_steps));
+    }
     if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
     if (eng->tables[TBL_SWEEP].set) {   // the battery sweep runs alone (kind: the first set one, so another table when there is one)
         if (kind != TBL_SWEEP)
@@ -4842,6 +4940,25 @@ static int phase_expand(const StepCtx& c)
                     } else {
                         launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY>{}, st, btv, sv);
                     }
+                    eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
+                }
+            } else if (table == TBL_DISPATCH) {
+                // battery dispatch (fp64: tmh_set_dispatch): the battery kind's three launches with the OUT_DISPATCH
+                // map and replay passes; the scan is the battery kind's own (params rows 0-5 sit where its rows
+                // sit); the same timers
+                if constexpr (!F32) {
+                    const tmh_dispatch& dd = eng->dispatch;
+                    const long long* params = reinterpret_cast<const long long*>(dd.params);
+                    const BatteryView btv{StorageView{c.ivv, reinterpret_cast<long long*>(dd.work), 0, 0, 0}, params};
+                    hipEvent_t t = eng->mark(c.s);
+                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_MAP>{}, st, btv, StatsView{});
+                    eng->close(TMH_K_STORAGE_MAP, t, c.s);
+                    t = eng->mark(c.s);
+                    hipLaunchKernelGGL(battery_scan_kernel, dim3(c.cb()), dim3(256), 0, c.s, btv.st.work,
+                                       reinterpret_cast<long long*>(dd.soc), params, eng->kp.ids, c.n_chains, c.sg.nblk);
+                    eng->close(TMH_K_STORAGE_SCAN, t, c.s);
+                    t = eng->mark(c.s);
+                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH>{}, st, btv, sv);
                     eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
                 }
             } else if (table == TBL_SWEEP) {

@@ -1546,7 +1546,11 @@ enum OutKind : int {
     OUT_FLEET = 128,
     // flag on OUT_STORAGE | OUT_LOSSY, both passes: the battery sweep (tmh_battery_sweep) -- a lane carries up to
     // SWEEP_KV batteries of its chain through one pass over the seconds; TMH_OUT_BATTERY_SWEEP
-    OUT_SWEEP = 256
+    OUT_SWEEP = 256,
+    // flag on OUT_STORAGE | OUT_LOSSY, both passes: battery dispatch (tmh_dispatch) -- the battery kind with a
+    // charge threshold, a discharge threshold and a feed-in limit per chain (params rows 6-8), the curtailed
+    // energy and the two peak keys behind the battery (13 columns); TMH_OUT_DISPATCH
+    OUT_DISPATCH = 512
 };
 constexpr int out_base(int out) { return out & 7; }
 // no trace: the statistics-only expansion's workgroup shape
@@ -1576,7 +1580,7 @@ struct IntervalsView {
 };
 constexpr int interval_cols(int out)
 {
-    return out_base(out) == OUT_STORAGE  ? ((out & OUT_LOSSY) ? TMH_BATTERY_COLS : TMH_STORAGE_COLS)
+    return out_base(out) == OUT_STORAGE  ? ((out & OUT_DISPATCH) ? TMH_DISPATCH_COLS : (out & OUT_LOSSY) ? TMH_BATTERY_COLS : TMH_STORAGE_COLS)
            : out_base(out) == OUT_DEMAND ? TMH_DEMAND_COLS
            : out_base(out) == OUT_REGISTERS ? TMH_REGISTERS_COLS
                                             : 4;
@@ -1608,6 +1612,14 @@ constexpr int soc_ask(int d, int p_charge, int p_discharge)
 {
     const int m = d > -p_discharge ? d : -p_discharge;
     return m < p_charge ? m : p_charge;
+}
+// Battery dispatch (tmh_dispatch): the battery charges only from the surplus above Tc and discharges only into
+// the deficit above Td, within the same limits.  The ask still depends on d and per-chain constants only, never
+// on the state of charge, so the second stays a clamped addition.  Tc = Td = 0 is soc_ask.
+constexpr int dispatch_ask(int d, int tc, int td, int p_charge, int p_discharge)
+{
+    const int up = d - tc > 0 ? d - tc : 0, dn = -d - td > 0 ? -d - td : 0;
+    return d >= 0 ? (up < p_charge ? up : p_charge) : -(dn < p_discharge ? dn : p_discharge);
 }
 // The SoC key of table column 8: the second's offset o in its interval (+ 1, so every key is positive)
 // above the state of charge after it (0 <= x < 2^40); the maximum key is the interval's last ok second's.
@@ -1678,7 +1690,25 @@ constexpr int bat_meter_side(int a, int s, int g, const BatteryParams& p)
     const int bm = (int)(m < aa ? m : aa);
     return g == s ? a : up ? bm : -bm;
 }
-// The battery kind's view: the storage kind's (cap, p_charge, p_discharge unused) and the parameters.
+// Battery dispatch's three parameters beside the battery's six: rows 6-8 of params[9][ld], each clamped into
+// [0, 2^27] as a lane loads it (DISPATCH_NO_LIMIT = 2^27: a second's surplus stays below 2^26).  Loaded by the
+// OUT_DISPATCH instantiations only.
+constexpr int DISPATCH_NO_LIMIT = BAT_POWER_MAX;
+struct DispatchParams {
+    int tc, td;   // Tc, Td: the charge and the discharge threshold
+    int lim;      // L: the feed-in limit
+};
+__device__ __forceinline__ DispatchParams dispatch_load(const long long* __restrict__ params, uint64_t ld, uint32_t i)
+{
+    DispatchParams p;
+    p.tc = bat_clamp_int(params[6 * ld + i], 0, DISPATCH_NO_LIMIT);
+    p.td = bat_clamp_int(params[7 * ld + i], 0, DISPATCH_NO_LIMIT);
+    p.lim = bat_clamp_int(params[8 * ld + i], 0, DISPATCH_NO_LIMIT);
+    return p;
+}
+constexpr DispatchParams dispatch_none() { return DispatchParams{0, 0, DISPATCH_NO_LIMIT}; }
+// The battery kind's view: the storage kind's (cap, p_charge, p_discharge unused) and the parameters ([6][ld];
+// battery dispatch: [9][ld], the battery's rows first).
 struct BatteryView {
     StorageView st;
     const long long* params;

@@ -1,0 +1,190 @@
+"""Battery dispatch: the battery kind under thresholds and a feed-in limit (tmh_dispatch).
+
+`battery` runs one control rule, greedy self-consumption: the battery takes every surplus watt and gives
+into every deficit watt.  Here each chain's battery charges only from the surplus above a threshold Tc,
+discharges only into the deficit above a threshold Td, and what is left of the surplus is fed in up to a
+limit L, the rest curtailed -- a household under a 70 % or 60 % feed-in limit, a battery that charges only
+from what would be curtailed, a battery that caps the import peak.  The parameters are the nine rows of an
+int64 array params [9, n] (`quantize_params`): battery.PARAMS' six, then Tc, Td and L in 2^-FRAC_BITS W;
+L = NO_LIMIT = 2^27 means no limit, since a second's surplus stays below 2^26.  An ok second with
+d = q(pv) - q(meter) and the SoC x before it:
+
+    a  = d >= 0 ?  min(max(d - Tc, 0), Pc)  :  -min(max(-d - Td, 0), Pd)      asked at the meter side
+    s, x1, g, b, x'   exactly battery's rule applied to this a
+    r  = d - b                       what is left at the meter (b lies between 0 and d)
+    import_b  = max(-r, 0)           surplus = max(r, 0)
+    export_b  = min(surplus, L)      fed in
+    curtailed = surplus - export_b   what the inverter throws away
+    loss      = b - (x' - x)
+
+A second that is not ok leaves x unchanged and adds nothing.  The engine fills an int64 tensor
+[n_intervals, 13, n] (BatchedSim.enable_dispatch, tmh_set_dispatch; fp64 engines only):
+
+    [k, 0:4, i]  the interval table's columns (pv, meter, n_ok, covered); [0] stays the available PV,
+                 what was produced is [0] - [10]
+    [k, 4, i]    sum of import_b          [k, 5, i] sum of export_b (after the limit)
+    [k, 6, i]    sum of max(b, 0)         [k, 7, i] sum of max(-b, 0)
+    [k, 8, i]    storage's SoC key        [k, 9, i] sum of loss
+    [k, 10, i]   sum of curtailed
+    [k, 11, i]   peak import behind the battery: the maximum of demand's key(import_b, o)
+    [k, 12, i]   peak feed-in: the maximum of key(export_b, o)
+
+In every cell [4] - [5] == [1] - [0] + [6] - [7] + [10], columns 4-7, 9 and 10 are >= 0, [6] - [7] - [9] is
+the interval's SoC change and the peak in [12] is <= L.  With Tc = Td = 0 and L = NO_LIMIT columns 0-9 and the
+SoC are `battery`'s bit for bit and column 10 is 0; with C = 0 and L = NO_LIMIT columns 11 and 12 are `demand`'s
+6 and 7; with C = 0 and any L, [5] + [10] is the registers' export.  The ask depends on d and the chain's
+constants only, so the second is still a clamped addition followed by the drain's: `second_maps` gives the
+triples that storage.compose / storage.apply fold.  `from_traces` is the contract as a plain loop.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import battery, demand, intervals
+from .battery import (FRAC_BITS, HI, KEY_SHIFT, LO, MAX_INTERVAL_S, MAX_POWER, MAX_W, apply, compose,   # noqa: F401
+                      n_intervals, quantize, quantize_soc, unpack_soc)
+
+COLUMNS = battery.COLUMNS + ("curtailed", "peak_import", "peak_export")
+PARAMS = battery.PARAMS + ("charge_above", "discharge_above", "feed_in_limit")   # the rows of params
+NO_LIMIT = MAX_POWER   # row 8: no feed-in limit
+# each row's inclusive range (tmh_dispatch)
+RANGES = battery.RANGES + ((0, MAX_POWER),) * 3
+
+
+def check_params(params):
+    """params as an int64 [9, n] array, every row inside its range (ValueError otherwise)."""
+    params = np.asarray(params.cpu() if hasattr(params, "cpu") else params)
+    if params.ndim != 2 or params.shape[0] != len(PARAMS) or params.dtype != np.int64:
+        raise ValueError("dispatch params must be an int64 [9, n] array")
+    for name, row, (lo, hi) in zip(PARAMS, params, RANGES):
+        if row.size and (int(row.min()) < lo or int(row.max()) > hi):
+            raise ValueError(f"dispatch {name} outside [{lo}, {hi}]: [{int(row.min())}, {int(row.max())}]")
+    return params
+
+
+def quantize_params(capacity_wh, charge_w, discharge_w, charge_eff=1.0, discharge_eff=1.0, standby_w=0.0,
+                    charge_above_w=0.0, discharge_above_w=0.0, feed_in_limit_w=None, n=None):
+    """The int64 [9, n] parameters: battery.quantize_params' six rows, then the two thresholds and the feed-in
+    limit in W (times 2^FRAC_BITS, rounded half to even), each a scalar or [n].  feed_in_limit_w=None (or
+    an entry that is None in a sequence) means no limit.  Raises ValueError on anything outside tmh_dispatch's
+    ranges (NaN included)."""
+    p = float(1 << FRAC_BITS)
+    if feed_in_limit_w is None:
+        feed_in_limit_w = NO_LIMIT / p
+    elif not np.isscalar(feed_in_limit_w):
+        feed_in_limit_w = [NO_LIMIT / p if v is None else v for v in feed_in_limit_w]
+    extra = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (charge_above_w, discharge_above_w, feed_in_limit_w)]
+    if any(a.ndim != 1 for a in extra):
+        raise ValueError("dispatch quantities are scalars or [n] arrays")
+    if n is None:
+        first = [np.atleast_1d(np.asarray(v)) for v in (capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w)]
+        n = max(a.shape[0] for a in first + extra)
+    out = np.empty((len(PARAMS), int(n)), dtype=np.int64)
+    out[:6] = battery.quantize_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w, n=n)
+    for r, (name, a, (lo, hi)) in enumerate(zip(PARAMS[6:], extra, RANGES[6:]), start=6):
+        if a.shape[0] not in (1, n):
+            raise ValueError(f"dispatch {name}: {a.shape[0]} values for {n} chains")
+        q = np.rint(a * p)
+        if not bool(((q >= lo) & (q <= hi)).all()):   # (NaN fails both)
+            raise ValueError(f"dispatch {name} {a[~((q >= lo) & (q <= hi))][0]!r} outside [{lo / p:.6g}, {hi / p:.6g}]")
+        out[r] = q.astype(np.int64)
+    return out
+
+
+def _ask(d, params):
+    """a of the second's d: the surplus above Tc up to Pc, or the deficit above Td up to Pd (negative)."""
+    pc, pd, tc, td = params[1], params[2], params[6], params[7]
+    return np.where(d >= 0, np.minimum(np.maximum(d - tc, 0), pc), -np.minimum(np.maximum(-d - td, 0), pd))
+
+
+def second_maps(pv, meter, covered, *, params):
+    """The per-second triples of traces [n_steps, n] with the parameters [9, n]: battery.second_maps' with
+    the thresholded ask; int64 arrays [n_steps, n] each (storage.compose, storage.apply)."""
+    pv, meter, covered = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (pv, meter, covered))
+    params = check_params(params)
+    cap, ec, ed, sb = params[0], params[3], params[4], params[5]
+    ok, d = battery._ok_d(pv, meter, covered)
+    s = battery._stored(_ask(d, params), ec, battery._recip(ed))
+    a, lo, hi = compose((s, 0, np.broadcast_to(cap, s.shape)), (-sb, 0, cap))
+    return np.where(ok, a, 0), np.where(ok, lo, LO).astype(np.int64), np.where(ok, hi, HI).astype(np.int64)
+
+
+def _second(x, d, params):
+    """One second of every chain: (b, x') of the SoC x before it and d, as if the second were ok."""
+    cap, pc, pd, ec, ed, sb = params[:6]
+    a = _ask(d, params)
+    s = battery._stored(a, ec, battery._recip(ed))
+    x1 = np.clip(x + s, 0, cap)
+    g = x1 - x
+    fill = np.minimum(a, (g * battery._recip(ec) + 65535) >> 16)
+    drain = -np.minimum(-a, (-g * ed) >> 16)
+    b = np.where(g == s, a, np.where(g > 0, fill, np.where(g < 0, drain, 0)))
+    return b, np.maximum(x1 - sb, 0)
+
+
+def from_traces(pv, meter, covered, interval_s, *, params, soc0, origin=0):
+    """The dispatch table of time-major traces [n_steps, n_chains] and the SoC after them: (int64
+    [n_intervals, 13, n_chains], int64 [n_chains]).  A plain loop over the seconds, vectorised over the
+    chains.  params: int64 [9, n_chains] inside their ranges; soc0: the SoC before the first second, a
+    scalar or [n_chains], clamped into [0, C]; ok seconds, interval_s and origin as intervals.from_traces."""
+    pv, meter, covered = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (pv, meter, covered))
+    base = intervals.from_traces(pv, meter, covered, interval_s, origin=origin)      # (checks the arguments)
+    interval_s, origin = int(interval_s), int(origin)
+    if interval_s > MAX_INTERVAL_S:
+        raise ValueError("interval_s <= 2^23 - 1")
+    n_steps, n = pv.shape
+    params = check_params(params)
+    if params.shape[1] != n:
+        raise ValueError(f"dispatch params for {params.shape[1]} chains, traces of {n}")
+    lim = params[8]
+    out = np.zeros((base.shape[0], len(COLUMNS), n), dtype=np.int64)
+    out[:, :4] = base
+    x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (n,)), 0, params[0])
+    ok, d_all = battery._ok_d(pv, meter, covered)
+    for t in range(n_steps):
+        k, o = divmod(origin + t, interval_s)
+        oks, d = ok[t], d_all[t]
+        b, xn = _second(x, d, params)
+        r = d - b
+        imp, sur = np.maximum(-r, 0), np.maximum(r, 0)
+        exp = np.minimum(sur, lim)
+        row = out[k]
+        row[4] += np.where(oks, imp, 0)
+        row[5] += np.where(oks, exp, 0)
+        row[6] += np.where(oks, np.maximum(b, 0), 0)
+        row[7] += np.where(oks, np.maximum(-b, 0), 0)
+        row[8] = np.where(oks, ((o + 1) << KEY_SHIFT) | xn, row[8])                 # later seconds have larger keys
+        row[9] += np.where(oks, b - (xn - x), 0)
+        row[10] += np.where(oks, sur - exp, 0)
+        row[11] = np.maximum(row[11], np.where(oks, demand.pack(imp, o), 0))
+        row[12] = np.maximum(row[12], np.where(oks, demand.pack(exp, o), 0))
+        x = np.where(oks, xn, x)
+    return out, x
+
+
+def to_battery(raw):
+    """The battery table [n_intervals, 10, n] inside a dispatch table (its first ten columns; a view)."""
+    if raw.ndim != 3 or raw.shape[1] != len(COLUMNS):
+        raise ValueError("raw dispatch table must be [n_intervals, 13, n]")
+    return raw[:, :10]
+
+
+def to_watts(raw, interval_s, n_steps=None):
+    """float64 views of a raw table [n_intervals, 13, n]: battery.to_watts' keys plus energy_wh_curtailed (Wh
+    the inverter threw away above the feed-in limit), curtailed_share = curtailed / available PV (NaN without
+    PV), peak_w_import and peak_w_export (W, behind the battery and after the limit) and t_peak_import and
+    t_peak_export (seconds into the interval of the earliest second at the peak; NaN without an ok second).
+    energy_wh_pv stays the available PV; self_consumption counts what was used on site or stored, so the
+    curtailed energy is taken out of it as the export is: (pv - export - curtailed) / pv, battery's ratio
+    where nothing is curtailed.  n_steps, when given, is checked against the interval count."""
+    raw = np.asarray(raw.cpu() if hasattr(raw, "cpu") else raw).astype(np.int64, copy=False)
+    out = battery.to_watts(to_battery(raw), interval_s, n_steps=n_steps)
+    e, scale = float(1 << FRAC_BITS) * 3600.0, float(1 << FRAC_BITS)
+    qpv = np.where(raw[:, 0] != 0, raw[:, 0], np.nan).astype(np.float64)
+    out.update({"energy_wh_curtailed": raw[:, 10] / e, "curtailed_share": raw[:, 10] / qpv,
+                "self_consumption": (raw[:, 0] - raw[:, 5] - raw[:, 10]) / qpv})
+    for name, col in (("import", 11), ("export", 12)):
+        v, o = demand.unpack(raw[:, col])
+        out["peak_w_" + name] = v / scale
+        out["t_peak_" + name] = np.where(o >= 0, o, np.nan).astype(np.float64)
+    return out

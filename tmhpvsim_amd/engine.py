@@ -83,6 +83,17 @@ _TABLES = {
         run_excludes=(("_intervals", "_registers", "_demand", "_storage"), "the battery kind and another interval table "
                                                                            "are both enabled: one of them per sim"),
         no_trace="a battery run takes no traces (trace=()): run the battery over the traces instead (battery.from_traces)"),
+    # battery dispatch (enable_dispatch: the battery kind with thresholds and a feed-in limit; fp64 sims only)
+    "dispatch": dict(
+        noun="dispatch tables", name="battery dispatch",
+        enable_excludes=tuple(
+            (attr, f"{what} is enabled: one table output per sim (battery dispatch runs alone)")
+            for attr, what in (("_series", "a fleet series"), ("_intervals", "interval metering"),
+                               ("_registers", "the import / export registers"), ("_demand", "the demand registers"),
+                               ("_battery_fleet", "a battery fleet series"))),
+        run_excludes=(("_intervals", "_registers", "_demand", "_storage", "_battery"),
+                      "battery dispatch and another interval table are both enabled: one of them per sim"),
+        no_trace="a dispatch run takes no traces (trace=()): run the battery over the traces instead (dispatch.from_traces)"),
 }
 for _kind, _t in _TABLES.items():   # no table beside battery storage, whichever was enabled first
     if _kind != "storage":
@@ -91,6 +102,9 @@ for _kind, _t in _TABLES.items():   # no table beside battery storage, whichever
     if _kind != "battery":
         _t["enable_excludes"] += (("_battery", "the battery kind is enabled: one table output per sim "
                                                "(the battery kind runs alone)"),)
+    if _kind != "dispatch":
+        _t["enable_excludes"] += (("_dispatch", "battery dispatch is enabled: one table output per sim "
+                                                "(battery dispatch runs alone)"),)
     # (enable_battery_sweep: the battery sweep, a kind with descriptor and attributes of its own)
     _t["enable_excludes"] += (("_battery_sweep", "the battery sweep is enabled: one table output per sim "
                                                  "(the battery sweep runs alone)"),)
@@ -197,6 +211,8 @@ class BatchedSim:
         self._storage_args = self._storage_work = self._storage_desc = None
         self.battery_params = None   # int64 [6, n]: the batteries' parameters (enable_battery); soc and the work buffer as storage's
         self._battery_desc = None
+        self.dispatch_params = None   # int64 [9, n]: the batteries' and the dispatch rule's parameters (enable_dispatch)
+        self._dispatch_desc = None
         self.battery_fleet_raw = None   # int64 [n_groups, n_steps, 8]: the battery fleet series (enable_battery_fleet)
         self._battery_fleet = None
         self.battery_sweep_raw = None   # int64 [K, n_intervals, 10, n]: the battery sweep's tables (enable_battery_sweep)
@@ -291,7 +307,7 @@ class BatchedSim:
     def _enable_table(self, kind, n_steps, interval_s, step0, buffer):
         """enable_intervals, enable_registers and enable_demand (_TABLES[kind])."""
         torch = _torch()
-        if kind in ("storage", "battery"):   # (its descriptor holds the table's: _set_storage, _set_battery)
+        if kind in ("storage", "battery", "dispatch"):   # (its descriptor holds the table's: _set_storage, _set_battery, _set_dispatch)
             setter = lambda eng, st: getattr(self, "_set_" + kind)(st._obj if st is not None else None)
         else:
             setter = getattr(self.L, "tmh_set_" + kind)
@@ -407,7 +423,7 @@ class BatchedSim:
         other table; compaction is allowed.  n_steps=None switches the output off."""
         torch = _torch()
         if n_steps is None:
-            if self._battery is None:   # (soc and the work buffer may be enable_battery's)
+            if self._battery is None and self._dispatch is None:   # (soc and the work buffer may be enable_battery's or enable_dispatch's)
                 self.soc = self._storage_work = self._storage_desc = None
             return self._enable_table("storage", None, interval_s, step0, buffer)
         if self.precision != _lib.TMH_FP64:
@@ -452,14 +468,16 @@ class BatchedSim:
         return rc
 
     def _storage_window(self, win):
-        """run(): the work buffer (storage's or the battery kind's) holds a window of `win` steps (a larger
-        one replaces it)."""
+        """run(): the work buffer (storage's, the battery kind's or battery dispatch's) holds a window of `win`
+        steps (a larger one replaces it)."""
         need = self.L.tmh_storage_work_bytes(self.n, int(win))
         if self._storage_work.numel() < need:
             _torch().cuda.synchronize(self.device)   # (launches of earlier runs may still read the old one)
             self._storage_work = _torch().empty(need, dtype=torch_uint8(), device=self.device)
             if self._battery is not None:
                 _lib.check(self._set_battery(self._battery))
+            elif self._dispatch is not None:
+                _lib.check(self._set_dispatch(self._dispatch))
             else:
                 _lib.check(self._set_storage(self._storage))
 
@@ -546,6 +564,84 @@ class BatchedSim:
         """The battery table in watts and watt-hours (battery.to_watts of battery_raw): storage's keys plus
         energy_wh_loss and round_trip, [n_intervals, n] each."""
         return self._table_watts("battery")
+
+    # ------------------------------------------------------------------ battery dispatch
+    def enable_dispatch(self, n_steps, interval_s=900, *, capacity_wh=None, charge_w=None, discharge_w=None, charge_eff=1.0,
+                        discharge_eff=1.0, standby_w=0.0, charge_above_w=0.0, discharge_above_w=0.0, feed_in_limit_w=None,
+                        soc0_wh=0.0, params=None, soc=None, buffer=None, step0=None):
+        """enable_battery under another control rule than greedy self-consumption (tmhpvsim_amd.dispatch): each
+        chain's battery charges only from the surplus above charge_above_w, discharges only into the deficit
+        above discharge_above_w, and what is left of the surplus is fed in up to feed_in_limit_w (None: no
+        limit), the rest curtailed; each quantity a scalar or [n].  Returns the raw int64 tensor
+        [n_intervals, 13, n]: the battery kind's ten columns (the export after the limit), the curtailed energy
+        and the peak import and peak feed-in behind the battery as demand keys.  `sim.soc` is the int64 state
+        of charge [n], `sim.dispatch_params` the int64 parameters [9, n] on the device
+        (dispatch.quantize_params).  params: a ready int64 device tensor [9, n] instead of the quantities -- it
+        may be a column slice of a larger [9, N] one whose row stride is the table's ld (buffer a slice of
+        [n_intervals, 13, N]); its values must lie in dispatch.RANGES (checked here; the kernels clamp).
+        soc0_wh, soc, buffer, step0, fp64 only, no traces, no fleet series, no battery fleet series, no other
+        table, compaction: as enable_battery.  n_steps=None switches the output off."""
+        torch = _torch()
+        if n_steps is None:
+            if self._dispatch is not None:   # (soc and the work buffer may be another kind's)
+                self.soc = self._storage_work = self._dispatch_desc = self.dispatch_params = None
+            return self._enable_table("dispatch", None, interval_s, step0, buffer)
+        if self.precision != _lib.TMH_FP64:
+            raise ValueError("battery dispatch needs precision='fp64': an fp32 engine replaces its guard-band seconds "
+                             "after the expansion, and the state of charge depends on every earlier second")
+        from . import dispatch
+        if int(interval_s) > dispatch.MAX_INTERVAL_S:
+            raise ValueError(f"enable_dispatch: interval_s <= {dispatch.MAX_INTERVAL_S}")
+        if params is None:
+            if capacity_wh is None or charge_w is None or discharge_w is None:
+                raise ValueError("enable_dispatch: capacity_wh, charge_w and discharge_w (or params) are required")
+            host = dispatch.quantize_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
+                                            charge_above_w, discharge_above_w, feed_in_limit_w, n=self.n)
+            params = torch.from_numpy(host).to(self.device)
+        else:
+            if (params.dtype != torch.int64 or params.device != self.device or tuple(params.shape) != (9, self.n)
+                    or (self.n > 1 and params.stride(1) != 1)):
+                raise ValueError(f"dispatch params must be an int64 [9, {self.n}] tensor on {self.device}, chains contiguous")
+            host = dispatch.check_params(params)
+        if soc is None:
+            soc = torch.from_numpy(dispatch.quantize_soc(soc0_wh, host)).to(self.device)
+        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (self.n,)
+              or (self.n > 1 and soc.stride(0) != 1)):
+            raise ValueError(f"dispatch soc must be a contiguous int64 [{self.n}] tensor on {self.device}")
+        kept = self._storage_args
+        self._storage_args = (soc, params)
+        try:
+            raw = self._enable_table("dispatch", n_steps, interval_s, step0, buffer)
+        except Exception:   # (refused: what was enabled before stays as it was)
+            self._storage_args = kept
+            raise
+        self.soc, self.dispatch_params = soc, params
+        return raw
+
+    def _set_dispatch(self, table):
+        """tmh_set_dispatch with the table descriptor `table` (or None); the work buffer as _set_storage's.
+        The parameters' row stride must be the table's ld (one ld for both: tmh_dispatch)."""
+        if table is None:
+            return self.L.tmh_set_dispatch(self._eng, None)
+        torch = _torch()
+        soc, params = self._storage_args
+        if int(params.stride(0)) != int(table.ld):
+            raise ValueError(f"dispatch params row stride {int(params.stride(0))} != the table's ld {int(table.ld)}: "
+                             "slice both from tensors of the same width")
+        if self._storage_work is None:
+            nb = self.L.tmh_storage_work_bytes(self.n, min(int(table.n_steps), 86400))
+            self._storage_work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
+        work = self._storage_work
+        dp = _lib.Dispatch(table, soc.data_ptr(), work.data_ptr(), work.numel(), params.data_ptr())
+        rc = self.L.tmh_set_dispatch(self._eng, C.byref(dp))
+        if rc == 0:
+            self._dispatch_desc = dp
+        return rc
+
+    def dispatch(self):
+        """The dispatch table in watts and watt-hours (dispatch.to_watts of dispatch_raw): the battery kind's keys
+        plus energy_wh_curtailed, curtailed_share and the peaks behind the battery, [n_intervals, n] each."""
+        return self._table_watts("dispatch")
 
     # ------------------------------------------------------------------ the battery sweep
     def enable_battery_sweep(self, n_steps, interval_s=900, *, n_variants=None, capacity_wh=None, charge_w=None,
@@ -779,7 +875,7 @@ class BatchedSim:
         res = out if out is not None else self._alloc(n_steps, trace)
         st = self._stats_struct()
         win = max(1, min(int(window), n_steps))
-        if self._storage is not None or self._battery is not None:
+        if self._storage is not None or self._battery is not None or self._dispatch is not None:
             self._storage_window(win)
         if self._battery_sweep is not None:
             self._sweep_window(win)
