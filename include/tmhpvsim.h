@@ -808,6 +808,16 @@ int tmh_engine_last_expand(const struct tmh_engine* eng);
  * 17 the segment walk's cloud-length power pow(x[i], a) as the walk calls it. */
 int tmh_probe(int fn, double a, const double* x, double* out, uint32_t n, void* stream);
 
+/* The per-second PV chain on given geometry rows, for parity tests (a test hook like tmh_probe; additive,
+ * TMH_ABI_VERSION stays 1).  rows: [n][TMH_GEOM_FIELDS] fp64 in the layout of the plan's table (real rows, or
+ * rows with fields planted at a discontinuity of the chain); csi: [n] fp64; out: [n][3] fp64 --
+ *   out[i][0]  the fp64 chain on row i with the engine's folded constants,
+ *   out[i][1]  the fp32 chain on the fp32 row the single-site table holds for row i (the same conversion),
+ *   out[i][2]  1 when that fp32 second lies in a guard band (the kernels recompute it in fp64), else 0.
+ * The night flag is not consulted: the chain runs on every row given.  All device pointers. */
+int tmh_probe_pv(struct tmh_engine* eng, const double* rows, const double* csi, double* out, uint32_t n,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,9 @@ def lib():
             getattr(L, name).argtypes = args
         L.orc_pv.restype = d
         L.orc_pv.argtypes = [p, C.c_int64, C.c_int, C.c_int, d]
+        L.orc_pv_row.restype = d
+        L.orc_pv_row.argtypes = [p, p, d]
+        L.orc_pv_row_parts.argtypes = [p, p, p, C.c_uint32, p, p]
         L.orc_geometry.argtypes = [p, C.c_int64, C.c_int, C.c_int, p]
         L.orc_solpos.argtypes = [C.c_int64, d, d, d, d, p, p, p]
         L.orc_constants.argtypes = [p]
@@ -225,6 +228,30 @@ def philox(ctr, key):
     o = np.zeros(4, dtype=np.uint32)
     lib().orc_philox(_ptr(c), _ptr(k), _ptr(o))
     return o
+
+
+def geometry(P, utc, doy, leap):
+    """The oracle's geom_t (sixteen doubles) of params P at one instant."""
+    g = np.zeros(16)
+    lib().orc_geometry(C.byref(P), int(utc), int(doy), int(leap), _ptr(g))
+    return g
+
+
+def pv_row(P, geom16, csi):
+    """pv_power of params P on one given geometry row (geom_t's sixteen doubles)."""
+    g = np.ascontiguousarray(geom16, dtype=np.float64)
+    assert g.shape == (16,)
+    return lib().orc_pv_row(C.byref(P), _ptr(g), float(csi))
+
+
+def pv_row_parts(P, geom16, csi):
+    """pv_power on n given rows [n, 16] and clear-sky indices [n]: (pv, kt, p_dc), each [n]."""
+    g = np.ascontiguousarray(geom16, dtype=np.float64)
+    c = np.ascontiguousarray(csi, dtype=np.float64)
+    assert g.ndim == 2 and g.shape == (len(c), 16)
+    pv, parts = np.empty(len(c)), np.empty((len(c), 2))
+    lib().orc_pv_row_parts(C.byref(P), _ptr(g), _ptr(c), len(c), _ptr(pv), _ptr(parts))
+    return pv, parts[:, 0].copy(), parts[:, 1].copy()
 
 
 def solpos(utc, lat, lon, pressure=100920.0, temp=12.0):

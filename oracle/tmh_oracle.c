@@ -656,8 +656,9 @@ static void geometry(const orc_params* P, int64_t utc, int doy, int leap, geom_t
     g->f2 = f2;
 }
 
-/* per chain-second stochastic part: pvmodel.py:53-80 */
-static double pv_power(const orc_params* P, const geom_t* g, double csi)
+/* per chain-second stochastic part: pvmodel.py:53-80; parts (or NULL): the clearness index kt and
+ * the DC power p_dc on the way, the quantities the chain's two discontinuities test */
+static double pv_power_parts(const orc_params* P, const geom_t* g, double csi, double* parts)
 {
     const double* m = P->module;
     const double* iv = P->inverter;
@@ -707,6 +708,10 @@ static double pv_power(const orc_params* P, const geom_t* g, double csi)
     double vmp = m[13] + m[17] * m[22] * delta * logEe + m[18] * m[22] * (dl * dl) + Bvmpo * (tcell - 25.0);
     if (!isnan(vmp)) vmp = vmp > 0.0 ? vmp : 0.0;
     double pdc = imp * vmp;
+    if (parts) {
+        parts[0] = kt;
+        parts[1] = pdc;
+    }
     /* snlinverter */
     double A = iv[1] * (1.0 + iv[5] * (vmp - iv[2]));
     double B = iv[3] * (1.0 + iv[6] * (vmp - iv[2]));
@@ -717,6 +722,27 @@ static double pv_power(const orc_params* P, const geom_t* g, double csi)
     /* ac.clip(lower=0.).fillna(0.) */
     if (isnan(ac)) return 0.0;
     return ac > 0.0 ? ac : 0.0;
+}
+
+static double pv_power(const orc_params* P, const geom_t* g, double csi) { return pv_power_parts(P, g, csi, NULL); }
+
+/* pv_power on a given geometry row (geom16: geom_t's sixteen doubles, orc_geometry's order) */
+double orc_pv_row(const orc_params* P, const double* geom16, double csi)
+{
+    geom_t g;
+    memcpy(&g, geom16, sizeof(g));
+    return pv_power(P, &g, csi);
+}
+
+/* the same for n rows and clear-sky indices: pv[i], and parts2[2 i], parts2[2 i + 1] = kt, p_dc */
+void orc_pv_row_parts(const orc_params* P, const double* geom16, const double* csi, uint32_t n, double* pv,
+                      double* parts2)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        geom_t g;
+        memcpy(&g, geom16 + 16 * (size_t)i, sizeof(g));
+        pv[i] = pv_power_parts(P, &g, csi[i], parts2 ? parts2 + 2 * (size_t)i : NULL);
+    }
 }
 
 void orc_geometry(const orc_params* P, int64_t utc, int doy, int leap, double* out16)

@@ -303,10 +303,27 @@ def test_c5_slice_time_parallel_equals_sequential_and_oracle():
     _check_vs_oracle(out, ref, "fp64")
 
 
-def test_geometry_table_vs_oracle():
-    from tmhpvsim_amd.params import ModelParams
-    mp = ModelParams()
-    steps, start, tz = 86400, "2019-09-05 00:00:00", "Europe/Berlin"
+# the engine's own site and day (geom_kernel's single-site table): Munich as the reference has it, then a
+# southern site facing north, a polar day, a high site on the equator lying flat, and a site at the date
+# line facing east (the true solar time wraps there)
+GEOMETRY_CASES = {
+    "munich": (dict(), "2019-09-05 00:00:00", "Europe/Berlin"),
+    "sydney": (dict(latitude=-33.87, longitude=151.21, tilt=30.0, surface_azimuth=0.0), "2019-12-21 00:00:00",
+               "Australia/Sydney"),
+    "tromso": (dict(latitude=69.65, longitude=18.96), "2019-06-21 00:00:00", "Europe/Oslo"),
+    "quito": (dict(latitude=-0.18, longitude=-78.47, altitude=2850.0, tilt=0.0), "2019-03-20 00:00:00",
+              "America/Guayaquil"),
+    "date_line": (dict(latitude=-17.7, longitude=179.99, surface_azimuth=90.0), "2019-09-05 00:00:00", "Pacific/Fiji"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(GEOMETRY_CASES))
+def test_geometry_table_vs_oracle(case):
+    import dataclasses
+    from tmhpvsim_amd.params import ModelParams, Site
+    site, start, tz = GEOMETRY_CASES[case]
+    mp = ModelParams(site=dataclasses.replace(Site(), **site))
+    steps = 86400
     sim = _sim(1, start, tz=tz, mp=mp, horizon=steps)
     tab = sim.geometry(0, steps).cpu().numpy()
     cal, utc = O.calendar(start, steps, tz)

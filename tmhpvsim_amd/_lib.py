@@ -115,7 +115,7 @@ EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_by
            "tmh_stream_create_cus", "tmh_stream_destroy", "tmh_set_walk_order", "tmh_engine_last_expand",
            "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals",
            "tmh_set_registers", "tmh_set_demand", "tmh_set_storage", "tmh_storage_work_bytes", "tmh_set_battery", "tmh_set_battery_fleet",
-           "tmh_set_battery_sweep", "tmh_battery_sweep_work_bytes", "tmh_set_dispatch"]
+           "tmh_set_battery_sweep", "tmh_battery_sweep_work_bytes", "tmh_set_dispatch", "tmh_probe_pv"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
 K_STORAGE_MAP, K_STORAGE_SCAN, K_STORAGE_REPLAY = 4, 5, 6   # battery storage's three launches (inside K_EXPAND)
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
@@ -263,6 +263,9 @@ def load():
         L.tmh_expand_part.argtypes = [p, p, u64, u32, i64, u32, C.POINTER(UStream), C.POINTER(Trace),
                                       C.POINTER(Stats), p, p, sz, C.c_int, p]
     L.tmh_probe.argtypes = [C.c_int, C.c_double, p, p, u32, p]
+    if hasattr(L, "tmh_probe_pv"):   # (absent from earlier builds, which same-box A/B runs still load)
+        L.tmh_probe_pv.argtypes = [p, p, p, p, u32, p]
+        L.tmh_probe_pv.restype = C.c_int
     L.tmh_profile_enable.argtypes = [p, C.c_int]
     L.tmh_set_shape_tables.argtypes = [p, p, p, u32]
     L.tmh_set_sites.argtypes = [p, p, p, u32]

@@ -416,21 +416,8 @@ __global__ __launch_bounds__(256, BUILD_WAVES) void geom_kernel(GParams gp, int6
     if (g[G_DISCOK] != 0.0) fl |= FL_DISCOK;
     g[G_FLAGS] = (double)fl;
     double* o64 = tab64 + (size_t)j * ROW;
-    float* o32 = tab32 + (size_t)j * ROW32;
     for (int i = 0; i < ROW; ++i) o64[i] = g[i];
-    const int fr[3] = {G_MINF, G_HOURF, G_DAYF}, fc[3] = {G32_MINF_C, G32_HOURF_C, G32_DAYF_C};
-    for (int i = 0; i < 3; ++i) {   // (1 - f, f) pairs, 1 - f rounded in fp32 as the kernels computed it
-        const float f = (float)g[fr[i]];
-        o32[fc[i]] = 1.0f - f;
-        o32[fc[i] + 1] = f;
-    }
-    for (int i = G_COSZ; i <= G_LAST; ++i) o32[i + G32] = (float)g[i];
-    o32[G_FLAGS + G32] = __uint_as_float(fl);
-    o32[G_I0H + G32] = (float)(1.0 / g[G_I0H]);   // fp32 path multiplies by reciprocals
-    o32[G_DNIEXTRA + G32] = (float)(1.0 / g[G_DNIEXTRA]);
-    o32[G_AM + G32] = (float)(g[G_AM] * LOG2E);   // exp(c am) = exp2(c * am log2 e)
-    o32[G_F1 + G32] = (float)(g[G_F1] * 1e-3);    // Ee = F1 (...) / 1000 with the division folded in
-    o32[G_RB + G32] = (float)(g[G_RB] - g[G_TERM2]);   // sky = dhi (term2 + AI (Rb - term2))
+    table_row32(g, fl, tab32 + (size_t)j * ROW32);
 }
 
 // The kind of each four-step group (first row j with (step0 + j) % 4 == 0, j + 3 < n) of a
@@ -3613,6 +3600,28 @@ __global__ void probe_kernel(int fn, double a, const double* x, double* out, uin
     out[i] = v;
 }
 
+// tmh_probe_pv: the per-second PV chain on given rows, with the engine's folded constants -- the fp64
+// chain on the row as it stands, and the fp32 chain (per-lane rows: pv_power_f<false>) on the row
+// the single-site fp32 table would hold for it (table_row32; DISC's zenith test from the row's
+// G_DISCOK as geom_kernel sets FL_DISCOK), with its guard-band flag.  No night shortcut: the
+// chain runs on every row given.
+__global__ __launch_bounds__(256) void probe_pv_kernel(const PV64 pv64, const PVF pvf, const double* __restrict__ rows,
+                                                       const double* __restrict__ csi, double* __restrict__ out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* g = rows + (size_t)i * ROW;
+    const bool discok = g[G_DISCOK] != 0.0;
+    float r32[ROW32];
+    table_row32(g, discok ? FL_DISCOK : 0u, r32);
+    const PV64* p = &pv64;
+    bool risky = false;
+    const float pv32 = pv_power_f<false>(pvf, r32 + G32, (float)csi[i], discok, risky);
+    out[3 * (size_t)i] = pv_power_d(p, g, csi[i], nullptr);
+    out[3 * (size_t)i + 1] = (double)pv32;
+    out[3 * (size_t)i + 2] = risky ? 1.0 : 0.0;
+}
+
 // ------------------------------------------------------------ host side
 thread_local std::string g_err;
 
@@ -5236,6 +5245,16 @@ int tmh_probe(int fn, double a, const double* x, double* out, uint32_t n, void* 
     if (n == 0) return TMH_OK;
     hipLaunchKernelGGL(probe_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, fn, a, x, out, n);
     return hip_check(hipGetLastError(), "probe_kernel launch");
+}
+
+int tmh_probe_pv(struct tmh_engine* eng, const double* rows, const double* csi, double* out, uint32_t n, void* stream)
+{
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (!rows || !csi || !out) return fail(TMH_E_INVAL, "NULL probe buffers");
+    if (n == 0) return TMH_OK;
+    hipLaunchKernelGGL(probe_pv_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, eng->kp.pv64,
+                       eng->kp.pvf, rows, csi, out, n);
+    return hip_check(hipGetLastError(), "probe_pv_kernel launch");
 }
 
 }  // extern "C"

@@ -968,6 +968,15 @@ __device__ __forceinline__ double hour_angle(const SiteK& k, const double* sun)
     return rad(tst / 4.0 - 180.0);
 }
 
+// 1 / x (x > 0, normal) from the fp32 hardware reciprocal and one Newton step in fp64: ~3e-14 relative, two
+// fmas.  The fp32 rows' reciprocals that feed DISC (the airmasses, 1 / I0h) take it: at low sun DISC's
+// Kn_c - Kn cancels and a relative error of the airmass or of kt comes out 25 to 50 times larger in the power.
+__device__ __forceinline__ double rcp_refined(double x)
+{
+    const double r = (double)__builtin_amdgcn_rcpf((float)x);
+    return fma(fma(-x, r, 1.0), r, r);
+}
+
 // site_geom from the hour angle's sine and cosine (sha, cha) at this sun row
 template <bool FULL, bool F32 = false, typename TP = const double*>
 __device__ __forceinline__ bool site_geom_hc(const SiteK& k, const double* sun, double tl, const double* m, double* g,
@@ -1028,13 +1037,11 @@ __device__ __forceinline__ bool site_geom_hc(const SiteK& k, const double* sun, 
     } else
         g[G_CSIMAX] = 27.21 * exp(-114 * ct) + 1.665 * exp(-4.494 * ct) + 1.08;
     const double dni_extra = sun[SUN_DNIX];
-    // F32 rows: the relative airmass only feeds Ineichen's exponent and the SAPM spectral
-    // polynomial (factors of GHI_cs and of the effective irradiance): fp32 power, ~2e-7
-    // relative; DISC's airmass (amd, below, ill-conditioned at low sun) stays fp64
+    // F32 rows: the relative airmass feeds Ineichen's exponent and the SAPM spectral polynomial: its
+    // power term (at most a seventh of the denominator) in fp32, the reciprocal refined (rcp_refined)
     double am_rel, am_abs;
-    if constexpr (F32) {   // fp32 quotient; the pressure ratio as a product
-        am_rel = azen <= 90.0 ? (double)__builtin_amdgcn_rcpf(
-                                    (float)(czs + 0.50572 * (double)__powf((float)(6.07995 + (90.0 - azen)), -1.6364f)))
+    if constexpr (F32) {   // the pressure ratio as a product
+        am_rel = azen <= 90.0 ? rcp_refined(czs + 0.50572 * (double)__powf((float)(6.07995 + (90.0 - azen)), -1.6364f))
                               : NAN;
         am_abs = am_rel * (k.pres * (1.0 / 101325.0));
     } else {
@@ -1043,26 +1050,27 @@ __device__ __forceinline__ bool site_geom_hc(const SiteK& k, const double* sun, 
     }
     const double cz = czs > 0.0 ? czs : 0.0;
     const double gx = -k.cg2 * am_abs * (k.fh1 + k.fh2 * (tl - 1.0));
-    const double gexp = F32 ? (double)__expf((float)gx) : exp(gx);   // F32: ~1e-7 relative on GHI_cs (kt guard band 4e-6)
+    // F32 rows: the PV table's exp (14 fp64 operations).  The fp32 exp left ~5e-7 relative on GHI_cs, inside the
+    // kt guard band, but kt's error is amplified ~30 times in the power of a low sun's beam on a steep panel
+    // (tests/test_gpu_pv_inputs.py, the world sites): the fp32 rows hold GHI_cs rounded once, like the plan's table
+    double gexp;
+    if constexpr (F32) gexp = exp_tab(gx, t);
+    else gexp = exp(gx);
     const double gmax = isnan(gexp) ? 0.0 : (gexp > 0.0 ? gexp : 0.0);
     // ineichen (pvmodel.py:60); F32 rows drop its tl / tl (an identity to one ulp)
     g[G_GHICS] = F32 ? k.cg1 * dni_extra * cz * gmax : k.cg1 * dni_extra * cz * tl / tl * gmax;
     const double I0 = sun[SUN_I0];
     g[G_I0] = I0;                                                              // disc (pvmodel.py:63)
     g[G_I0H] = I0 * (ct > 0.065 ? ct : 0.065);
-    // DISC's airmass from the fp64 zenith (its conditioning at low sun); F32 rows (which hold
-    // am and Kn_c as floats) take the reciprocal and Kn_c's polynomial in fp32 (~1e-7)
+    // DISC's airmass from the fp64 zenith (its conditioning at low sun); F32 rows take the refined
+    // reciprocal, and Kn_c's polynomial in fp64 like the others: am and Kn_c reach the row rounded once
     double amd;
-    if constexpr (F32) amd = zen <= 90.0 ? (double)__builtin_amdgcn_rcpf((float)(ct + 0.15 * pow_pos(93.885 - zen, -1.253, t)))
-                                         : NAN;
+    if constexpr (F32) amd = zen <= 90.0 ? rcp_refined(ct + 0.15 * pow_pos(93.885 - zen, -1.253, t)) : NAN;
     else amd = zen <= 90.0 ? 1.0 / (ct + 0.15 * pow_pos(93.885 - zen, -1.253, t)) : NAN;
     if constexpr (!F32) amd = amd * 101325.0 / 101325.0;   // (pvlib's pressure scaling: an identity to one ulp)
     amd = amd < 12.0 ? amd : (isnan(amd) ? amd : 12.0);
     g[G_AM] = amd;
-    if constexpr (F32) {
-        const float a = (float)amd;
-        g[G_KNC] = fmaf(fmaf(fmaf(fmaf(0.000014f, a, -0.000653f), a, 0.0121f), a, -0.122f), a, 0.866f);
-    } else {
+    {
         const double amd2 = amd * amd;
         g[G_KNC] = 0.866 - 0.122 * amd + 0.0121 * amd2 - 0.000653 * (amd2 * amd) + 0.000014 * (amd2 * amd2);
     }
@@ -1116,12 +1124,33 @@ __device__ __forceinline__ void site_row(const double* g, const double* sun, R* 
         row[G_KTC] = g[G_KTC];
         row[G_RDNIX] = g[G_RDNIX];
     } else {
-        row[G_I0H] = __builtin_amdgcn_rcpf((float)g[G_I0H]);
+        row[G_I0H] = (float)rcp_refined(g[G_I0H]);
         row[G_DNIEXTRA] = (float)sun[SUN_RDNIX];
         row[G_AM] = (float)(g[G_AM] * LOG2E);
         row[G_F1] = (float)(g[G_F1] * 1e-3);   // pv_power_f: Ee = F1 (...) without the / 1000
         row[G_RB] = (float)(g[G_RB] - g[G_TERM2]);   // pv_power_f: sky = dhi (term2 + AI (Rb - term2))
     }
+}
+
+// the single-site fp32 table's row (geom_kernel's tab32; ROW32 floats at o32) from the fp64 row g and
+// its flag bits: the clock fractions as (1 - f, f) pairs, then flags and G_COSZ..G_LAST at G_X + G32
+// with the reciprocals and folded factors pv_power_f reads.  geom_kernel and the PV probe
+// (probe_pv_kernel) both convert through it.
+__device__ __forceinline__ void table_row32(const double* g, uint32_t fl, float* o32)
+{
+    const int fr[3] = {G_MINF, G_HOURF, G_DAYF}, fc[3] = {G32_MINF_C, G32_HOURF_C, G32_DAYF_C};
+    for (int i = 0; i < 3; ++i) {   // (1 - f, f) pairs, 1 - f rounded in fp32 as the kernels computed it
+        const float f = (float)g[fr[i]];
+        o32[fc[i]] = 1.0f - f;
+        o32[fc[i] + 1] = f;
+    }
+    for (int i = G_COSZ; i <= G_LAST; ++i) o32[i + G32] = (float)g[i];
+    o32[G_FLAGS + G32] = __uint_as_float(fl);
+    o32[G_I0H + G32] = (float)(1.0 / g[G_I0H]);   // fp32 path multiplies by reciprocals
+    o32[G_DNIEXTRA + G32] = (float)(1.0 / g[G_DNIEXTRA]);
+    o32[G_AM + G32] = (float)(g[G_AM] * LOG2E);   // exp(c am) = exp2(c * am log2 e)
+    o32[G_F1 + G32] = (float)(g[G_F1] * 1e-3);    // Ee = F1 (...) / 1000 with the division folded in
+    o32[G_RB + G32] = (float)(g[G_RB] - g[G_TERM2]);   // sky = dhi (term2 + AI (Rb - term2))
 }
 
 // True when the sun at site k stays below the refraction band (cos z < -0.015, where
@@ -1232,7 +1261,12 @@ __device__ __forceinline__ double pv_power_d(PP p, const double* g, double csi, 
     const double am = g[G_AM];
     double a, b, cc;
     const double kt2 = kt * kt, kt3 = kt2 * kt;
-    if (kt <= 0.6) {
+    // DISC's split as pvmodel.py decides it, on the quotient ghi / I0h rounded to nearest: that quotient is <= 0.6
+    // (the double below 0.6; its mantissa is odd, so a tie rounds away from it) iff ghi - 0.6 I0h < 2^-54 I0h, the
+    // left side one fma.  The product form of kt above may round to the other side of the split within an ulp or
+    // two of it, where Kn jumps by up to 3 % of the power (tmh_probe_pv's planted rows).  A NaN csi stays low.
+    const bool lo = !(fma(-0.6, g[G_I0H], ghi) >= 0x1p-54 * g[G_I0H]);
+    if (lo) {
         a = 0.512 - 1.56 * kt + 2.286 * kt2 - 2.222 * kt3;
         b = 0.37 + 0.962 * kt;
         cc = -0.28 + 0.932 * kt - 2.048 * kt2;

@@ -992,6 +992,24 @@ class BatchedSim:
         plan = self.plan(step0, n_steps)
         return plan[: n_steps * _lib.TMH_GEOM_FIELDS * 8].view(torch.float64).view(n_steps, _lib.TMH_GEOM_FIELDS)
 
+    def probe_pv(self, rows, csi):
+        """The per-second PV chain on given geometry rows (tmh_probe_pv; parity tests): rows
+        [n, TMH_GEOM_FIELDS] fp64 in geometry()'s layout, csi [n] -> numpy [n, 3]: the fp64 chain's
+        power, the fp32 chain's on the row's fp32 form, and that second's guard-band flag (0 / 1)."""
+        torch = _torch()
+        rt = torch.as_tensor(np.asarray(rows, dtype=np.float64) if not torch.is_tensor(rows) else rows,
+                             dtype=torch.float64, device=self.device).contiguous()
+        ct = torch.as_tensor(np.asarray(csi, dtype=np.float64) if not torch.is_tensor(csi) else csi,
+                             dtype=torch.float64, device=self.device).contiguous()
+        if rt.dim() != 2 or rt.shape[1] != _lib.TMH_GEOM_FIELDS or tuple(ct.shape) != (rt.shape[0],):
+            raise ValueError(f"probe_pv wants rows [n, {_lib.TMH_GEOM_FIELDS}] and csi [n], got "
+                             f"{tuple(rt.shape)} and {tuple(ct.shape)}")
+        out = torch.empty(rt.shape[0], 3, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.tmh_probe_pv(self._eng, _ptr(rt), _ptr(ct), _ptr(out), rt.shape[0], self._stream()))
+            torch.cuda.synchronize()
+        return out.cpu().numpy()
+
     def stats_totals(self):
         """Node-local totals: histogram, energy sums (W*s, exact fixed-point limbs and the
         fp64 values of them) and peak residual (W) over every chain's accumulated
