@@ -40,7 +40,9 @@
  *    (tmh_battery_sweep: the battery kind's table and state of charge for each of up to
  *    TMH_BATTERY_SWEEP_MAX candidate batteries per chain, in one run), or battery dispatch
  *    (tmh_dispatch: the battery kind with a charge threshold, a discharge threshold and a
- *    feed-in limit per chain, the curtailed energy and the peaks behind the battery).
+ *    feed-in limit per chain, the curtailed energy and the peaks behind the battery), or the
+ *    dispatch sweep (tmh_dispatch_sweep: battery dispatch's table and state of charge for each
+ *    of up to TMH_DISPATCH_SWEEP_MAX rule sets per chain, in one run).
  *  - `stream` is a hipStream_t (NULL = default stream); all work is enqueued
  *    asynchronously on it.  One engine per device; not re-entrant per engine.
  */
@@ -436,6 +438,36 @@ typedef struct tmh_dispatch {
     const int64_t* params;    /* device [9][ld], ld = table.ld */
 } tmh_dispatch;
 
+/* The dispatch sweep: tmh_dispatch's rule, unchanged to the bit, applied to n_variants parameter sets per
+ * chain in one run -- the same household (the same chain: the same pv and meter second for second) under each
+ * of K rules and batteries: what a 70 % or a 60 % feed-in limit costs it, which charge threshold recovers the
+ * curtailed energy, which battery to buy under the limit.  It relates to tmh_dispatch as tmh_battery_sweep
+ * relates to tmh_battery.  Variant v has a table, a state of charge and parameters of its own, each exactly
+ * what tmh_set_dispatch would be given and would produce for it:
+ *   table.sum  device int64 [n_variants][n_intervals][TMH_DISPATCH_COLS][ld], zero-initialised by the caller;
+ *              variant v's table starts n_intervals * TMH_DISPATCH_COLS * ld elements after variant v - 1's
+ *              (n_intervals = ceil(table.n_steps / table.interval_s)) and equals tmh_dispatch's table for
+ *              params[v] and soc[v] bit for bit, so columns 0-3 are the same in every variant
+ *   soc        device int64 [n_variants][ld]: variant v's row at soc + v * ld, tmh_dispatch's soc
+ *   params     device int64 [n_variants][TMH_DISPATCH_PARAMS][ld]: variant v's nine rows at params + v * 9 * ld,
+ *              rows, ranges and clamping as tmh_dispatch's; read by every window, never written
+ * Indexing within a variant is per chain index (ids[slot] under tmh_set_chain_ids), so compacted windows fill
+ * the same tables; the strides are in units of ld, so a column slice of wider tensors ([K][n_iv][13][N],
+ * [K][9][N], [K][N] with ld = N) is a valid argument.  work: device scratch of the caller, the battery sweep's:
+ * >= tmh_battery_sweep_work_bytes(n_chains, n_steps, n_variants) bytes of the largest window.  The engine runs
+ * the variants in groups of a compile-time count per launch (the kind's three launches per group; a group of
+ * one variant is tmh_dispatch's own launches); the bits do not depend on the grouping, windows, batches or
+ * compaction.  fp64 engines and the engine's one site only. */
+#define TMH_DISPATCH_SWEEP_MAX 16
+typedef struct tmh_dispatch_sweep {
+    tmh_intervals table;      /* sum is [n_variants][n_intervals][TMH_DISPATCH_COLS][ld] */
+    int64_t* soc;             /* device [n_variants][ld] */
+    void* work;               /* device scratch */
+    size_t work_bytes;        /* >= tmh_battery_sweep_work_bytes(n_chains, n_steps, n_variants) of the largest window */
+    const int64_t* params;    /* device [n_variants][TMH_DISPATCH_PARAMS][ld], rows as tmh_dispatch's */
+    uint32_t n_variants;      /* 1 .. TMH_DISPATCH_SWEEP_MAX */
+} tmh_dispatch_sweep;
+
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
 /* TMH_SERIES_FRAC_BITS and TMH_SERIES_MAX_W as the library was built with them */
@@ -668,6 +700,19 @@ int tmh_set_battery_sweep(struct tmh_engine* eng, const tmh_battery_sweep* sw);
  * battery kind and the battery sweep included); a fleet series set too; tmh_set_battery_fleet set too.  The
  * parameters' values are not read on the host: the kernels clamp them. */
 int tmh_set_dispatch(struct tmh_engine* eng, const tmh_dispatch* dp);
+/* The dispatch sweep (tmh_dispatch_sweep above): every later expansion of this engine advances sw->soc and
+ * adds its window to sw->table.sum for each of the n_variants rule sets of every chain; NULL switches it off.
+ * The variants run in groups, each group in the kind's three launches; TMH_K_STORAGE_MAP, TMH_K_STORAGE_SCAN
+ * and TMH_K_STORAGE_REPLAY sum this kind's launches of a window and TMH_K_EXPAND spans all of them.  Statistics
+ * and the histogram, when tmh_stats gives them, are accumulated by exactly one replay launch per window.
+ * Refused here (TMH_E_INVAL, the messages name "dispatch sweep"): tmh_set_dispatch's bad-struct cases;
+ * n_variants 0 or above TMH_DISPATCH_SWEEP_MAX; a NULL or misaligned (8 bytes) params, soc or work; work_bytes
+ * below tmh_battery_sweep_work_bytes(1, 1, n_variants); an fp32 engine.  Refused at a step / expansion call or
+ * a walk of that window, before any launch: everything tmh_set_dispatch's step refuses (the work buffer against
+ * tmh_battery_sweep_work_bytes of the window); any other table kind set too, in either order, the battery
+ * sweep and battery dispatch included; tmh_set_series or tmh_set_battery_fleet set; per-chain sites
+ * (tmh_set_sites). */
+int tmh_set_dispatch_sweep(struct tmh_engine* eng, const tmh_dispatch_sweep* sw);
 /* Tests only: the fp32 guard-band records (chain, block) the last expansion on
  * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
  * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
@@ -763,7 +808,7 @@ int tmh_expand_part(struct tmh_engine* eng, void* state, uint64_t chain0, uint32
  * it.  kernel: TMH_K_EXPAND (P2 trace/stats expansion), TMH_K_SEGMENTS (P1
  * segment walk), TMH_K_CANDIDATES (P1's candidate table), TMH_K_STEP (the
  * whole tmh_step); with battery storage or the battery kind set, TMH_K_EXPAND spans the kind's three launches
- * and TMH_K_STORAGE_MAP, TMH_K_STORAGE_SCAN and TMH_K_STORAGE_REPLAY time each of them (the battery sweep:
+ * and TMH_K_STORAGE_MAP, TMH_K_STORAGE_SCAN and TMH_K_STORAGE_REPLAY time each of them (the battery sweep and the dispatch sweep:
  * each slot sums that launch over the window's groups of variants, several launches per read). */
 enum { TMH_K_EXPAND = 0, TMH_K_SEGMENTS = 1, TMH_K_CANDIDATES = 2, TMH_K_STEP = 3, TMH_K_STORAGE_MAP = 4,
        TMH_K_STORAGE_SCAN = 5, TMH_K_STORAGE_REPLAY = 6, TMH_K_COUNT = 7 };
@@ -781,7 +826,8 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * storage: the replay pass, the last of the kind's three launches, with or without statistics),
  * TMH_OUT_BATTERY (the battery kind, likewise), TMH_OUT_BATTERY_FLEET (the battery kind with its fleet
  * series: the replay pass that fills both), TMH_OUT_BATTERY_SWEEP (the battery sweep),
- * TMH_OUT_DISPATCH (battery dispatch: its replay pass, with or without statistics), plus
+ * TMH_OUT_DISPATCH (battery dispatch: its replay pass, with or without statistics),
+ * TMH_OUT_DISPATCH_SWEEP (the dispatch sweep), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
@@ -796,6 +842,7 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
 #define TMH_OUT_BATTERY_FLEET 9
 #define TMH_OUT_BATTERY_SWEEP 10
 #define TMH_OUT_DISPATCH 11
+#define TMH_OUT_DISPATCH_SWEEP 12
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

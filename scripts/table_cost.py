@@ -3,7 +3,7 @@
 kernel) of the statistics-only expansion and of the expansions with a table, same chains,
 same window, same process, the runs alternating.
 
-    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet|battery_sweep|dispatch
+    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet|battery_sweep|dispatch|dispatch_sweep
                                  [--variants 5] [--chains 65536] [--steps 86400]
                                  [--interval 900] [--rounds 5] [--precision fp32]
                                  [--start "2019-09-05 00:00:00"] [--out FILE.json]
@@ -43,6 +43,14 @@ The runs of a kind, each with the same statistics beside its table:
              than under the battery kind, energy is curtailed, the peak fed in is the limit) and the dispatch
              table's identities.  The kind's three launches are timed for both; dispatch / battery for the whole
              expansion and per launch, with medians and ranges, beside the spread of the battery kind's own rounds.
+  dispatch_sweep: OUT_DISPATCH and OUT_DISPATCH_SWEEP, dispatch's setting, no statistics -- the unchanged dispatch kind
+             (one rule per chain: --charge-above-w, --discharge-above-w, --feed-in-limit-w) and the dispatch sweep over
+             --variants K rule sets, the three quantities scaled by factors spread over [0.6, 1.4] around it,
+             alternating; variant (K - 1) / 2 has the kind's own rule and its table and soc are the kind's bit for bit,
+             columns 0-3 agree in every variant and every variant keeps the dispatch table's identities.  The kind's
+             three launches are timed for both (the sweep's slots sum its groups' launches); the yardstick is K x the
+             dispatch kind's median of the same run: ratio_sweep_k_dispatch = sweep / (K x dispatch) for the whole
+             expansion and per launch, beside the spread of each run's own rounds.
 The script checks each run's variant, these identities (on the warm-up round's tables), that
 the statistics of all runs agree bit for bit and that every table's ok seconds equal the
 histogram's count.  One warm-up round, then --rounds timed ones.  Prints one JSON line: the
@@ -70,6 +78,7 @@ RUNS = {
     "battery_fleet": (("battery", "battery"), ("battery_fleet", "battery")),
     "battery_sweep": (("battery", "battery"), ("battery_sweep", "battery_sweep")),   # (sweep_cost: a loop of its own)
     "dispatch": (("battery", "battery"), ("dispatch", "dispatch")),                  # (dispatch_cost: likewise)
+    "dispatch_sweep": (("dispatch", "dispatch"), ("dispatch_sweep", "dispatch_sweep")),   # (dsweep_cost: likewise)
 }
 
 
@@ -252,6 +261,83 @@ def dispatch_cost(a, mp, lossy):
                 build_stamp=_lib.loaded_stamp())
 
 
+def dsweep_cost(a, mp, lossy):
+    """--kind dispatch_sweep: the dispatch kind and the dispatch sweep over a.variants rule sets, alternating."""
+    import torch
+    from tmhpvsim_amd import _lib
+    from tmhpvsim_amd.engine import BatchedSim
+    K = a.variants
+    mid = (K - 1) // 2
+    fac = [0.6 + 0.8 * v / (K - 1) for v in range(K)] if K > 1 else [1.0]
+    fac[mid] = 1.0
+    rule = dict(charge_above_w=a.charge_above_w, discharge_above_w=a.discharge_above_w, feed_in_limit_w=a.feed_in_limit_w)
+    rules = {k: [w * f for f in fac] for k, w in rule.items()}
+    parts = (("map", _lib.K_STORAGE_MAP), ("scan", _lib.K_STORAGE_SCAN), ("replay", _lib.K_STORAGE_REPLAY))
+    labels = ("dispatch", "dispatch_sweep")
+    groups = None
+
+    def one(label):
+        nonlocal groups
+        sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=mp, precision="fp64", device="cuda:0", horizon=a.steps)
+        if label == "dispatch":
+            raw = sim.enable_dispatch(a.steps, a.interval, **lossy, **rule)
+        else:
+            raw = sim.enable_dispatch_sweep(a.steps, a.interval, n_variants=K, **lossy, **rules)
+        _lib.check(sim.L.tmh_profile_enable(sim._eng, 1))
+        sim.run(a.steps, trace=(), window=a.steps)
+        torch.cuda.synchronize()
+        ms, launches = _lib.profile_read(sim._eng, _lib.K_EXPAND)
+        want = (_lib.OUT_DISPATCH if label == "dispatch" else _lib.OUT_DISPATCH_SWEEP) | _lib.OUT_FP64
+        assert launches == 1 and sim.L.tmh_engine_last_expand(sim._eng) == want, (launches, want)
+        pm = {}
+        for name, kk in parts:
+            pm[name], pn = _lib.profile_read(sim._eng, kk)
+            if label == "dispatch":
+                assert pn == 1
+            else:
+                groups = pn
+        return ms, pm, raw, sim.soc.clone()
+
+    def check(dp, sw):   # the warm-up round's tables: the middle variant is the kind's, columns 0-3 every variant's
+        assert torch.equal(sw[2][mid], dp[2]) and torch.equal(sw[3][mid], dp[3])
+        for v in range(K):
+            t = sw[2][v]
+            assert torch.equal(t[:, :4], dp[2][:, :4]) and bool((t[:, 4:8] >= 0).all()) and bool((t[:, 9:11] >= 0).all())
+            assert torch.equal(t[:, 4] - t[:, 5], t[:, 1] - t[:, 0] + t[:, 6] - t[:, 7] + t[:, 10])
+            assert torch.equal(t[:, 11] != 0, t[:, 2] > 0) and torch.equal(t[:, 12] != 0, t[:, 2] > 0)
+            assert int((t[:, 12] >> 32).max()) == int(round(rules["feed_in_limit_w"][v] * 4096)) and int(t[:, 10].sum()) > 0
+            assert v == mid or not torch.equal(t[:, 4:], dp[2][:, 4:])
+        d = dp[2]
+        assert int(d[:, 6].sum()) > 0 and int(d[:, 7].sum()) > 0 and int(d[:, 9].sum()) > 0
+        return [int(sw[2][v][:, 10].sum()) / int(d[:, 0].sum()) for v in range(K)]
+
+    shares = check(one("dispatch"), one("dispatch_sweep"))   # warm-up: code objects, allocator
+    t = {k: [] for k in labels}
+    pt = {k: {name: [] for name, _ in parts} for k in labels}
+    for _ in range(a.rounds):
+        for label in labels:
+            ms, pm, _raw, _soc = one(label)
+            t[label].append(ms)
+            for name in pm:
+                pt[label][name].append(pm[name])
+            del _raw, _soc
+    med = {k: statistics.median(t[k]) for k in labels}
+    pmed = {k: {name: statistics.median(v) for name, v in pt[k].items()} for k in labels}
+    return dict(device=torch.cuda.get_device_name(0), chains=a.chains, steps=a.steps, interval_s=a.interval, precision="fp64",
+                start=a.start, rounds=a.rounds, modules=a.modules, battery=lossy, variants=K, rules=rules,
+                curtailed_shares=shares, launch_groups=groups,
+                **{f"{k}_ms": t[k] for k in labels}, **{f"{k}_median_ms": med[k] for k in labels},
+                **{f"{k}_range_ms": [min(t[k]), max(t[k])] for k in labels},
+                **{f"{k}_{name}_ms": v for k in labels for name, v in pt[k].items()},
+                **{f"{k}_{name}_median_ms": v for k in labels for name, v in pmed[k].items()},
+                **{f"{k}_spread": max(t[k]) / min(t[k]) for k in labels},
+                **{f"{k}_replay_spread": max(pt[k]["replay"]) / min(pt[k]["replay"]) for k in labels},
+                yardstick_ms=K * med["dispatch"], sweep_ms_per_variant=med["dispatch_sweep"] / K,
+                ratio_sweep_k_dispatch=med["dispatch_sweep"] / (K * med["dispatch"]),
+                **{f"ratio_{name}_sweep_k_dispatch": pmed["dispatch_sweep"][name] / (K * pmed["dispatch"][name]) for name, _ in parts},
+                build_stamp=_lib.loaded_stamp())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", choices=tuple(RUNS), required=True)
@@ -269,12 +355,12 @@ def main():
     ap.add_argument("--charge-eff", type=float, default=0.95)
     ap.add_argument("--discharge-eff", type=float, default=0.95)
     ap.add_argument("--standby-w", type=float, default=2.0)
-    ap.add_argument("--variants", type=int, default=5, help="--kind battery_sweep: the batteries per chain")
+    ap.add_argument("--variants", type=int, default=5, help="--kind battery_sweep, dispatch_sweep: the variants per chain")
     ap.add_argument("--charge-above-w", type=float, default=500.0, help="--kind dispatch: the charge threshold")
     ap.add_argument("--discharge-above-w", type=float, default=200.0, help="--kind dispatch: the discharge threshold")
     ap.add_argument("--feed-in-limit-w", type=float, default=1000.0, help="--kind dispatch: the feed-in limit")
     a = ap.parse_args()
-    if a.kind in ("storage", "battery", "battery_fleet", "battery_sweep", "dispatch"):
+    if a.kind in ("storage", "battery", "battery_fleet", "battery_sweep", "dispatch", "dispatch_sweep"):
         a.precision = "fp64"   # (the kind's engines)
     import torch
     from tmhpvsim_amd import _lib
@@ -299,8 +385,9 @@ def main():
     battery = dict(capacity_wh=a.capacity_wh, charge_w=a.charge_w, discharge_w=a.discharge_w, soc0_wh=a.capacity_wh / 2)
     lossy = dict(battery, charge_eff=a.charge_eff, discharge_eff=a.discharge_eff, standby_w=a.standby_w)
     enable_kw = {"storage": battery, "battery": lossy}
-    if a.kind in ("battery_sweep", "dispatch"):
-        line = json.dumps(sweep_cost(a, mp, lossy) if a.kind == "battery_sweep" else dispatch_cost(a, mp, lossy))
+    if a.kind in ("battery_sweep", "dispatch", "dispatch_sweep"):
+        cost = {"battery_sweep": sweep_cost, "dispatch": dispatch_cost, "dispatch_sweep": dsweep_cost}[a.kind]
+        line = json.dumps(cost(a, mp, lossy))
         print(line)
         if a.out:
             with open(a.out, "w") as fh:

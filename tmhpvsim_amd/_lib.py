@@ -106,6 +106,14 @@ class Dispatch(C.Structure):
                 ("params", C.c_void_p)]
 
 
+class DispatchSweep(C.Structure):
+    """tmh_dispatch_sweep: the dispatch sweep's tables [n_variants][n_intervals][13][ld] (tmh_intervals of variant
+    0), the variants' state of charge [n_variants][ld], the work buffer and parameters [n_variants][9][ld]
+    (tmh_set_dispatch_sweep)."""
+    _fields_ = [("table", Intervals), ("soc", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t),
+                ("params", C.c_void_p), ("n_variants", C.c_uint32)]
+
+
 EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_bytes", "tmh_state_offsets", "tmh_plan_bytes",
            "tmh_scratch_bytes", "tmh_engine_scratch_bytes", "tmh_workspace_bytes", "tmh_engine_create", "tmh_engine_destroy", "tmh_engine_path",
            "tmh_init", "tmh_run", "tmh_plan", "tmh_step", "tmh_probe", "tmh_profile_enable", "tmh_profile_read",
@@ -115,7 +123,8 @@ EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_by
            "tmh_stream_create_cus", "tmh_stream_destroy", "tmh_set_walk_order", "tmh_engine_last_expand",
            "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals",
            "tmh_set_registers", "tmh_set_demand", "tmh_set_storage", "tmh_storage_work_bytes", "tmh_set_battery", "tmh_set_battery_fleet",
-           "tmh_set_battery_sweep", "tmh_battery_sweep_work_bytes", "tmh_set_dispatch", "tmh_probe_pv"]
+           "tmh_set_battery_sweep", "tmh_battery_sweep_work_bytes", "tmh_set_dispatch", "tmh_probe_pv",
+           "tmh_set_dispatch_sweep"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
 K_STORAGE_MAP, K_STORAGE_SCAN, K_STORAGE_REPLAY = 4, 5, 6   # battery storage's three launches (inside K_EXPAND)
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
@@ -130,7 +139,9 @@ OUT_BATTERY = 8
 OUT_BATTERY_FLEET = 9   # the battery kind with its fleet series (tmh_set_battery_fleet)
 OUT_BATTERY_SWEEP = 10  # the battery sweep (tmh_set_battery_sweep)
 OUT_DISPATCH = 11       # battery dispatch (tmh_set_dispatch)
+OUT_DISPATCH_SWEEP = 12  # the dispatch sweep (tmh_set_dispatch_sweep)
 BATTERY_SWEEP_MAX = 16  # TMH_BATTERY_SWEEP_MAX
+DISPATCH_SWEEP_MAX = 16  # TMH_DISPATCH_SWEEP_MAX
 
 _lib = None
 
@@ -238,6 +249,8 @@ def load():
     L.tmh_set_battery_fleet.restype = C.c_int
     L.tmh_set_battery_sweep.argtypes = [p, C.POINTER(BatterySweep)]
     L.tmh_set_battery_sweep.restype = C.c_int
+    L.tmh_set_dispatch_sweep.argtypes = [p, C.POINTER(DispatchSweep)]
+    L.tmh_set_dispatch_sweep.restype = C.c_int
     L.tmh_battery_sweep_work_bytes.argtypes = [u32, u32, u32]
     L.tmh_battery_sweep_work_bytes.restype = sz
     L.tmh_storage_work_bytes.argtypes = [u32, u32]

@@ -465,15 +465,24 @@ SWEEP_TOTALS = (("import_wh", "energy_wh_import"), ("export_wh", "energy_wh_expo
 SWEEP_RATIOS = ("self_consumption", "self_sufficiency", "full_cycles")
 
 
-def sweep_lists(**lists):
-    """The battery-sweep options (lists of floats) as one value per variant: every list has the one length K or
-    length 1 (repeated); click.ClickException otherwise.  Returns (K, {option: [K floats]})."""
+def _variant_lists(command, lists):
     k = max(len(v) for v in lists.values())
     bad = [name for name, v in lists.items() if len(v) not in (1, k)]
     if bad:
-        raise click.ClickException(f"battery-sweep: --{bad[0].replace('_', '-')} has {len(lists[bad[0]])} values; every list "
+        raise click.ClickException(f"{command}: --{bad[0].replace('_', '-')} has {len(lists[bad[0]])} values; every list "
                                    f"needs one length ({k} here) or length 1: a list is one value per variant")
     return k, {name: list(v) * (k if len(v) == 1 else 1) for name, v in lists.items()}
+
+
+def sweep_lists(**lists):
+    """The battery-sweep options (lists of floats) as one value per variant: every list has the one length K or
+    length 1 (repeated); click.ClickException otherwise.  Returns (K, {option: [K floats]})."""
+    return _variant_lists("battery-sweep", lists)
+
+
+def dispatch_sweep_lists(**lists):
+    """The dispatch-sweep options likewise (lists of floats; --feed-in-limit-w's entries may be None: no limit)."""
+    return _variant_lists("dispatch-sweep", lists)
 
 
 def sweep_fleet_rows(raw, interval_s, params):
@@ -527,6 +536,81 @@ def battery_sweep(file, amqp_url, exchange, verbose, realtime, batch, start, sec
         for v, row in enumerate(rows):
             f.write(",".join([str(v)] + [repr(float(opts[o][v])) for o in SWEEP_OPTIONS] + [repr(row[key]) for _, key in SWEEP_TOTALS]
                              + [repr(row[key]) for key in SWEEP_RATIOS]) + "\n")
+    if all_chains:
+        import numpy as np
+        np.savez(all_chains, raw=raw, params=params, soc=sim.soc.cpu().numpy(), interval_s=interval_s)
+    click.echo(f"wrote {k} rows to {file}" + (f" and {k} x {batch} chains to {all_chains}" if all_chains else ""))
+
+
+DISPATCH_SWEEP_OPTIONS = SWEEP_OPTIONS + ("charge_above_w", "discharge_above_w", "feed_in_limit_w")
+# the dispatch-sweep CSV: a row per variant -- its parameters (feed_in_limit_w `none` without a limit), then (header,
+# key of dispatch.sweep_summary) fleet totals, the largest peaks of any chain (W) and ratios
+DISPATCH_SWEEP_TOTALS = SWEEP_TOTALS + (("curtailed_wh", "energy_wh_curtailed"), ("peak_import_w", "peak_w_import"),
+                                        ("peak_export_w", "peak_w_export"))
+DISPATCH_SWEEP_RATIOS = SWEEP_RATIOS + ("curtailed_share",)
+
+
+def dispatch_sweep_fleet_rows(raw, interval_s, params):
+    """A dict per variant of the fleet's totals and ratios (DISPATCH_SWEEP_TOTALS, DISPATCH_SWEEP_RATIOS) from a raw
+    dispatch sweep table [K, n_iv, 13, n]: dispatch.sweep_summary(fleet=True)."""
+    from . import dispatch as D
+    fleet = D.sweep_summary(raw, interval_s, params, fleet=True)
+    return [{k: float(v[i]) for k, v in fleet.items()} for i in range(len(raw))]
+
+
+@main.command("dispatch-sweep")
+@click.argument("file")
+@common
+@click.option("--all-chains", default=None, help="also write every variant's raw table of every chain to this .npz")
+@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
+              help="seconds per metering interval (a last partial interval is kept)")
+@click.option("--capacity-wh", callback=_dealt, required=True, help="battery capacity (Wh); a list is one value per variant")
+@click.option("--charge-w", callback=_dealt, required=True, help="charge power limit at the meter side (W)")
+@click.option("--discharge-w", callback=_dealt, required=True, help="discharge power limit at the meter side (W)")
+@click.option("--charge-eff", callback=_dealt, default="1.0", help="charge efficiency in [0.5, 1]")
+@click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]")
+@click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)")
+@click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)")
+@click.option("--charge-above-w", callback=_dealt, default="0.0", help="charge only from the surplus above this (W)")
+@click.option("--discharge-above-w", callback=_dealt, default="0.0", help="discharge only into the deficit above this (W)")
+@click.option("--feed-in-limit-w", callback=_dealt_limit, default=None, help="feed-in limit (W); `none`: no limit (the default)")
+def dispatch_sweep(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
+                   charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh, charge_above_w, discharge_above_w,
+                   feed_in_limit_w):
+    """Every chain under each of K dispatch rules (battery, thresholds, feed-in limit) in one fp64 engine run: a CSV
+    row per variant to FILE."""
+    logging.basicConfig(level=logging.WARN - 10 * verbose)
+    _need_batch(realtime, batch, "dispatch-sweep")
+    k, opts = dispatch_sweep_lists(capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
+                                   discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh,
+                                   charge_above_w=charge_above_w, discharge_above_w=discharge_above_w,
+                                   feed_in_limit_w=feed_in_limit_w)
+    from .engine import BatchedSim
+    from .params import ModelParams
+    import torch
+    if not torch.cuda.is_available():
+        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
+    mp = ModelParams(seed=int(seed))
+    sim = BatchedSim(int(batch), start, tz=mp.site.tz, params=mp, precision="fp64", device="cuda:0", horizon=int(seconds))
+    try:
+        raw = sim.enable_dispatch_sweep(int(seconds), int(interval_s), n_variants=k, **opts)
+    except ValueError as e:   # (a quantity outside its range, too many variants: dispatch.quantize_sweep_params)
+        raise click.ClickException(str(e))
+    sim.run(int(seconds), trace=())
+    torch.cuda.synchronize()
+    raw, params = raw.cpu().numpy(), sim.dispatch_params.cpu().numpy()
+    bad = int((sim.status() != 0).sum())
+    if bad:
+        logger.warning(f"{bad} of {batch} chains faulted (reference exceptions); their tables hold the seconds before the fault")
+    rows = dispatch_sweep_fleet_rows(raw, interval_s, params)
+    cell = lambda x: "none" if x is None else repr(float(x))
+    with open(file, "w") as f:
+        f.write(",".join(("variant",) + DISPATCH_SWEEP_OPTIONS + tuple(h for h, _ in DISPATCH_SWEEP_TOTALS)
+                         + DISPATCH_SWEEP_RATIOS) + "\n")
+        for v, row in enumerate(rows):
+            f.write(",".join([str(v)] + [cell(opts[o][v]) for o in DISPATCH_SWEEP_OPTIONS]
+                             + [repr(row[key]) for _, key in DISPATCH_SWEEP_TOTALS]
+                             + [repr(row[key]) for key in DISPATCH_SWEEP_RATIOS]) + "\n")
     if all_chains:
         import numpy as np
         np.savez(all_chains, raw=raw, params=params, soc=sim.soc.cpu().numpy(), interval_s=interval_s)

@@ -89,7 +89,15 @@ constexpr int EXP_WAVES_LOSSY = 3;
 //    at most 256 VGPRs; the map pass takes 209 and the replay 240, neither spills.  At 3 waves (168 VGPRs) the map
 //    pass spilled 98 VGPRs, the cliff the battery kind's replay met at 4 (Battery sweep)
 constexpr int EXP_WAVES_SWEEP_MAP = 2, EXP_WAVES_SWEEP_REPLAY = 2;
+//  the dispatch sweep's two passes (fp64 single-site, DSWEEP_KV = 4 variants per lane), in 256-chain workgroups: 2 =
+//    at most 256 VGPRs; the map pass takes 216 and does not spill, the replay takes all 256 and spills 23 (80 B of
+//    scratch): dispatch's three parameters, curtailed sum and four peak registers per variant on top of the battery
+//    sweep's 240.  Three variants per lane fit (245 VGPRs, no spill) and ran slower, 276.8 ms against 255.0 ms at
+//    K = 5 and 422.9 ms against 337.3 ms at K = 8: a pass over the seconds more costs more than the spills.  Two
+//    variants take 215 VGPRs at 2 waves and spill 87 at 3 (168 VGPRs); neither was timed (Dispatch sweep)
+constexpr int EXP_WAVES_DSWEEP_MAP = 2, EXP_WAVES_DSWEEP_REPLAY = 2;
 constexpr bool out_sweep(int out) { return (out & OUT_SWEEP) != 0; }
+constexpr bool out_dsweep(int out) { return (out & OUT_SWEEP) != 0 && (out & OUT_DISPATCH) != 0; }
 constexpr bool out_lossy_replay(int out) { return out_base(out) == OUT_STORAGE && (out & OUT_LOSSY) && !(out & OUT_MAP); }
 //  battery dispatch's replay pass (fp64 single-site) runs at the battery kind's shape, EXP_WAVES_LOSSY: one more
 //    64-bit sum, the two running peaks with their seconds and three more parameters live across the per-second
@@ -2038,6 +2046,7 @@ template <typename R, int OUT, bool SITES>
 constexpr int exp_waves()
 {
     return SITES                             ? EXP_WAVES_SITES
+           : out_dsweep(OUT)                  ? ((OUT & OUT_MAP) ? EXP_WAVES_DSWEEP_MAP : EXP_WAVES_DSWEEP_REPLAY)
            : out_sweep(OUT)                   ? ((OUT & OUT_MAP) ? EXP_WAVES_SWEEP_MAP : EXP_WAVES_SWEEP_REPLAY)
            : out_lossy_replay(OUT)            ? EXP_WAVES_LOSSY
            : sizeof(R) == 8                   ? EXP_WAVES_F64
@@ -2236,13 +2245,19 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // and piece sums (REP) per lane, one iv_pv and one iv_m; variants swv.nv .. KV - 1 of a short group are empty
     // batteries in registers that are never loaded, stored or flushed and whose seconds are skipped
     constexpr bool SWP = (OUT & OUT_SWEEP) != 0;
-    constexpr int KV = SWP ? SWEEP_KV : 1;
     static_assert(!SWP || (BAT && !FLT && !SITES), "the battery sweep: a flag of the battery kind's passes, single site");
     // DSP: battery dispatch on the battery kind's two passes -- the lane's three more parameters (dispatch_load),
     // dispatch_ask in place of soc_ask, and in the replay the feed-in limit: one more 64-bit sum (the curtailed
     // energy), the demand kind's running peaks fed with import_b and export_b, and IVC = 13
     constexpr bool DSP = (OUT & OUT_DISPATCH) != 0;
-    static_assert(!DSP || (BAT && !FLT && !SWP), "battery dispatch: a flag of the battery kind's passes, no fleet series, no sweep");
+    static_assert(!DSP || (BAT && !FLT), "battery dispatch: a flag of the battery kind's passes, no fleet series");
+    // DSW: the dispatch sweep, both flags -- the sweep's shared second, then dispatch's second of each of KV variants:
+    // per variant three more parameters (sw_dsp), and in the replay the curtailed sum (sw_cu) and the four peak
+    // registers (sw_im, sw_imj, sw_xm, sw_xmj) beside the sweep's; a variant's parameters are 9 rows, its cells 13 columns
+    constexpr bool DSW = SWP && DSP;
+    constexpr int KV = DSW ? DSWEEP_KV : SWP ? SWEEP_KV : 1;
+    constexpr int KD = DSW ? KV : 1;          // the per-variant dispatch state: one unused set elsewhere
+    constexpr int PROWS = DSP ? TMH_DISPATCH_PARAMS : 6;   // a variant's parameter rows
     static_assert(!STO || sizeof(R) == 8, "battery storage: fp64 engines only (no guard-band seconds)");
     // REG: the import / export registers -- the intervals' pieces, accumulators and flush, with
     // one more accumulator and IVC = 6 columns per cell instead of 4
@@ -2451,7 +2466,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // st_dis) - (iv_pv - iv_m); the peaks are the demand kind's dm_im / dm_ex with their seconds.
     DispatchParams dsp = dispatch_none();
     long long ds_cu = 0;
-    if constexpr (DSP) {
+    if constexpr (DSP && !SWP) {
         if (live) dsp = dispatch_load(batp, ivv.ld, gid(kp.ids, c));
     }
     if constexpr (REP && !SWP) {
@@ -2462,13 +2477,28 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     SocMap sw_map[KV];
     BatteryParams sw_bp[KV];
     long long sw_hi[KV], sw_x[KV], sw_x0[KV], sw_ex[KV], sw_ch[KV], sw_dis[KV];
+    // the dispatch sweep's, as battery dispatch's dsp, ds_cu and dm_* above
+    DispatchParams sw_dsp[KD];
+    long long sw_cu[KD];
+    int sw_im[KD], sw_xm[KD];
+    uint32_t sw_imj[KD], sw_xmj[KD];
+    if constexpr (DSW) {
+#pragma unroll
+        for (int v = 0; v < KV; ++v) {
+            sw_dsp[v] = dispatch_none();
+            if (live && (uint32_t)v < swv.nv) sw_dsp[v] = dispatch_load(batp + (size_t)v * PROWS * ivv.ld, ivv.ld, gid(kp.ids, c));
+            sw_cu[v] = 0;
+            sw_im[v] = sw_xm[v] = 0;
+            sw_imj[v] = sw_xmj[v] = 0;
+        }
+    }
     if constexpr (SWP) {
 #pragma unroll
         for (int v = 0; v < KV; ++v) {
             const bool on = live && (uint32_t)v < swv.nv;
             sw_map[v] = soc_identity();
             sw_bp[v] = battery_none();
-            if (on) sw_bp[v] = battery_load(batp + (size_t)v * 6 * ivv.ld, ivv.ld, gid(kp.ids, c));
+            if (on) sw_bp[v] = battery_load(batp + (size_t)v * PROWS * ivv.ld, ivv.ld, gid(kp.ids, c));
             sw_hi[v] = max(sw_bp[v].cap - (long long)sw_bp[v].sigma, 0ll);
             sw_x[v] = 0;
             if constexpr (REP)
@@ -2516,7 +2546,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 for (int v = 0; v < KV; ++v) {
                     if ((uint32_t)v < swv.nv) {
                         unsigned long long* cell = ivv.sum + (size_t)v * swv.tstride + (size_t)iv_k * IVC * ivv.ld + gid(kp.ids, c);
-                        const long long net = sw_ch[v] - sw_dis[v], im = sw_ex[v] + net - (iv_pv - iv_m),
+                        // (the dispatch sweep: the import from dispatch's identity, the curtailed sum beside the export)
+                        long long exc = sw_ex[v];
+                        if constexpr (DSW) exc += sw_cu[v];
+                        const long long net = sw_ch[v] - sw_dis[v], im = exc + net - (iv_pv - iv_m),
                                         loss = net - (sw_x[v] - sw_x0[v]);
                         if (iv_pv) atomicAdd(cell, (unsigned long long)iv_pv);
                         if (iv_m) atomicAdd(cell + ivv.ld, (unsigned long long)iv_m);
@@ -2525,10 +2558,20 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                         if (sw_ch[v]) atomicAdd(cell + 6 * ivv.ld, (unsigned long long)sw_ch[v]);
                         if (sw_dis[v]) atomicAdd(cell + 7 * ivv.ld, (unsigned long long)sw_dis[v]);
                         if (loss) atomicAdd(cell + 9 * ivv.ld, (unsigned long long)loss);
+                        if constexpr (DSW)
+                            if (sw_cu[v]) atomicAdd(cell + 10 * ivv.ld, (unsigned long long)sw_cu[v]);
                         if (hi > lo) {
                             atomicAdd(cell + 2 * ivv.ld, (unsigned long long)(hi - lo));
                             __hip_atomic_fetch_max(cell + 8 * ivv.ld, soc_key(ob + (uint32_t)(hi - 1), sw_x[v]),
                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if constexpr (DSW) {   // the variant's peaks behind its battery: battery dispatch's keys, columns 11, 12
+                                const unsigned long long kim =
+                                    demand_key((uint32_t)sw_im[v], ob + (sw_im[v] > 0 ? sw_imj[v] : (uint32_t)lo));
+                                const unsigned long long kex =
+                                    demand_key((uint32_t)sw_xm[v], ob + (sw_xm[v] > 0 ? sw_xmj[v] : (uint32_t)lo));
+                                __hip_atomic_fetch_max(cell + 11 * ivv.ld, kim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                __hip_atomic_fetch_max(cell + 12 * ivv.ld, kex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            }
                             if (nc) atomicAdd(cell + 3 * ivv.ld, (unsigned long long)nc);
                         }
                     }
@@ -2540,6 +2583,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             for (int v = 0; v < KV; ++v) {
                 sw_ex[v] = sw_ch[v] = sw_dis[v] = 0;
                 sw_x0[v] = sw_x[v];
+                if constexpr (DSW) {
+                    sw_cu[v] = 0;
+                    sw_im[v] = sw_xm[v] = 0;
+                }
             }
             ++iv_k;
             return;
@@ -2668,7 +2715,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 for (int v = 0; v < KV; ++v) {
                     if (v > 0 && (uint32_t)v >= swv.nv) continue;   // a short group's missing variants: a scalar branch
                     const BatteryParams& p = sw_bp[v];
-                    const int ab = soc_ask(d, p.pc, p.pd), s = bat_stored(ab, p);
+                    int ab;
+                    if constexpr (DSW) ab = dispatch_ask(d, sw_dsp[v].tc, sw_dsp[v].td, p.pc, p.pd);
+                    else ab = soc_ask(d, p.pc, p.pd);
+                    const int s = bat_stored(ab, p);
                     if constexpr (MAP) {
                         const SocMap f = soc_compose(sw_map[v], SocMap{(long long)(s - p.sigma), 0, sw_hi[v]});
                         sw_map[v].a = ok ? f.a : sw_map[v].a;
@@ -2678,7 +2728,23 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                         const long long x1 = soc_clamp(sw_x[v] + s, 0, p.cap);
                         const int bm = bat_meter_side(ab, s, (int)(x1 - sw_x[v]), p);
                         sw_x[v] = ok ? max(x1 - (long long)p.sigma, 0ll) : sw_x[v];
-                        sw_ex[v] += (long long)(ok ? max(d - bm, 0) : 0);
+                        if constexpr (DSW) {
+                            // battery dispatch's second (below) of the variant: the deficit left at the meter is the
+                            // import, the surplus fed in up to the variant's limit and curtailed above it; a night
+                            // second's literal pv = 0 has no surplus, so that code stays out of it
+                            const int r = d - bm, vi = ok ? max(-r, 0) : 0;
+                            sw_imj[v] = vi > sw_im[v] ? jb : sw_imj[v];
+                            sw_im[v] = max(vi, sw_im[v]);
+                            if (!(__builtin_constant_p(pv) && pv == R(0))) {
+                                const int su = ok ? max(r, 0) : 0, ve = min(su, sw_dsp[v].lim);
+                                sw_ex[v] += (long long)ve;
+                                sw_cu[v] += (long long)(su - ve);
+                                sw_xmj[v] = ve > sw_xm[v] ? jb : sw_xmj[v];
+                                sw_xm[v] = max(ve, sw_xm[v]);
+                            }
+                        } else {
+                            sw_ex[v] += (long long)(ok ? max(d - bm, 0) : 0);
+                        }
                         sw_ch[v] += (long long)(ok ? max(bm, 0) : 0);
                         sw_dis[v] += (long long)(ok ? max(-bm, 0) : 0);
                     }
@@ -3271,6 +3337,16 @@ __global__ __launch_bounds__(256) void battery_sweep_scan_kernel(long long* __re
     const size_t v = blockIdx.y;
     storage_scan<true>(work + v * wstride, soc + v * ld, params + v * 6 * ld, ids, n, nblk);
 }
+// the dispatch sweep: the same walk, a variant's nine parameter rows apart (row 0 of a variant's params sits where the
+// battery kind's sits); a kernel of its own, so that the battery sweep's stays as it is
+__global__ __launch_bounds__(256) void dispatch_sweep_scan_kernel(long long* __restrict__ work, long long* __restrict__ soc,
+                                                                  const long long* __restrict__ params,
+                                                                  const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk,
+                                                                  uint64_t wstride, uint64_t ld)
+{
+    const size_t v = blockIdx.y;
+    storage_scan<true>(work + v * wstride, soc + v * ld, params + v * TMH_DISPATCH_PARAMS * ld, ids, n, nblk);
+}
 
 // ------------------------------------------------------------ compaction
 // Batches whose chains fault (the reference's AssertionError in markov mode ends
@@ -3806,7 +3882,7 @@ void with_real(bool f64, F&& f)
 // one kind per engine at a step.  A kind is its column count, the expansion's and the fixup's
 // output, and the words the refusals name it by; a new kind is a row here, its columns in
 // expand_tile and the fixup, and its exported setter.
-enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_KINDS };
+enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_DISPATCH_SWEEP, TBL_KINDS };
 struct TableKindInfo {
     int cols, out;      // out: TMH_OUT_* as tmh_engine_last_expand reports it (the expansion's OutKind but for TBL_BATTERY)
     const char* what;   // in the setter's and the checks' messages
@@ -3828,18 +3904,24 @@ constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
     // battery dispatch (tmh_dispatch: thresholds and a feed-in limit per chain; tmh_engine::dispatch): the battery
     // kind's three launches on the OUT_DISPATCH instantiations, TMH_OUT_DISPATCH
     {TMH_DISPATCH_COLS, TMH_OUT_DISPATCH, "battery dispatch tables", "battery dispatch"},
+    // the dispatch sweep (tmh_dispatch_sweep: n_variants rule sets per chain; tmh_engine::dsweep): battery dispatch's
+    // three launches per group of DSWEEP_KV variants on the OUT_SWEEP | OUT_DISPATCH instantiations, TMH_OUT_DISPATCH_SWEEP
+    {TMH_DISPATCH_COLS, TMH_OUT_DISPATCH_SWEEP, "dispatch sweep tables", "the dispatch sweep"},
 };
 static_assert(TMH_OUT_BATTERY > out_base(~0) && TMH_OUT_BATTERY < TMH_OUT_SITES, "TMH_OUT_BATTERY: a code of its own below the flags");
 static_assert(TMH_OUT_BATTERY_FLEET > TMH_OUT_BATTERY && TMH_OUT_BATTERY_FLEET < TMH_OUT_SITES, "TMH_OUT_BATTERY_FLEET: likewise");
 static_assert(TMH_OUT_BATTERY_SWEEP > TMH_OUT_BATTERY_FLEET && TMH_OUT_BATTERY_SWEEP < TMH_OUT_SITES, "TMH_OUT_BATTERY_SWEEP: likewise");
 static_assert(TMH_OUT_DISPATCH > TMH_OUT_BATTERY_SWEEP && TMH_OUT_DISPATCH < TMH_OUT_SITES, "TMH_OUT_DISPATCH: likewise");
+static_assert(TMH_OUT_DISPATCH_SWEEP > TMH_OUT_DISPATCH && TMH_OUT_DISPATCH_SWEEP < TMH_OUT_SITES, "TMH_OUT_DISPATCH_SWEEP: likewise");
+static_assert(DSWEEP_KV >= 2 && DSWEEP_KV <= TMH_DISPATCH_SWEEP_MAX, "a group of one variant runs battery dispatch's own kernels");
 static_assert(interval_cols(OUT_INTERVALS) == TABLE_KINDS[TBL_INTERVALS].cols &&
                   interval_cols(OUT_REGISTERS) == TABLE_KINDS[TBL_REGISTERS].cols &&
                   interval_cols(OUT_DEMAND) == TABLE_KINDS[TBL_DEMAND].cols &&
                   interval_cols(OUT_STORAGE) == TABLE_KINDS[TBL_STORAGE].cols &&
                   interval_cols(OUT_STORAGE | OUT_LOSSY) == TABLE_KINDS[TBL_BATTERY].cols &&
                   interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_SWEEP) == TABLE_KINDS[TBL_SWEEP].cols &&
-                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH) == TABLE_KINDS[TBL_DISPATCH].cols,
+                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH) == TABLE_KINDS[TBL_DISPATCH].cols &&
+                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SWEEP) == TABLE_KINDS[TBL_DISPATCH_SWEEP].cols,
               "the kernels' cells");
 
 }  // namespace
@@ -3867,6 +3949,7 @@ struct tmh_engine {
     tmh_battery battery{};   // tmh_set_battery: soc, the work buffer and the parameters beside tables[TBL_BATTERY]
     tmh_battery_sweep sweep{};   // tmh_set_battery_sweep: the variants' soc, work buffer and parameters beside tables[TBL_SWEEP]
     tmh_dispatch dispatch{};   // tmh_set_dispatch: soc, the work buffer and the parameters beside tables[TBL_DISPATCH]
+    tmh_dispatch_sweep dsweep{};   // tmh_set_dispatch_sweep: the variants' soc, work buffer and parameters beside tables[TBL_DISPATCH_SWEEP]
     bool has_fleet = false;  // tmh_set_battery_fleet: the battery kind's replay pass adds its window to `fleet` too
     tmh_series fleet{};
     // the first set kind (TBL_KINDS: none); a step is refused unless it is the only one (check_interval_tables)
@@ -4467,6 +4550,39 @@ int tmh_set_dispatch(struct tmh_engine* eng, const tmh_dispatch* dp)
     return TMH_OK;
 }
 
+// the dispatch sweep: tmh_set_battery_sweep's checks in its own words, nine parameter rows per variant
+int tmh_set_dispatch_sweep(struct tmh_engine* eng, const tmh_dispatch_sweep* sw)
+{
+    if (!sw) {
+        if (int rc = set_interval_table(eng, TBL_DISPATCH_SWEEP, nullptr)) return rc;
+        eng->dsweep = tmh_dispatch_sweep{};
+        return TMH_OK;
+    }
+    const char* what = TABLE_KINDS[TBL_DISPATCH_SWEEP].what;
+    if (!sw->table.sum || sw->table.n_steps == 0 || sw->table.ld == 0 || ((uintptr_t)sw->table.sum & 7) ||
+        sw->table.interval_s == 0)   // (the struct's cases, in the setter's words)
+        return set_interval_table(nullptr, TBL_DISPATCH_SWEEP, &sw->table);
+    if (sw->table.interval_s > (1u << 23) - 1)
+        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
+                    sw->table.interval_s);
+    if (sw->n_variants == 0 || sw->n_variants > TMH_DISPATCH_SWEEP_MAX)
+        return fail(TMH_E_INVAL, "%s: n_variants %u outside [1, %d]", what, sw->n_variants, TMH_DISPATCH_SWEEP_MAX);
+    if (!sw->soc || ((uintptr_t)sw->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer [n_variants][ld]", what);
+    if (!sw->work || ((uintptr_t)sw->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
+    if (!sw->params || ((uintptr_t)sw->params & 7))
+        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor [n_variants][%d][ld]", what, TMH_DISPATCH_PARAMS);
+    if (sw->work_bytes < tmh_battery_sweep_work_bytes(1, 1, sw->n_variants))
+        return fail(TMH_E_INVAL, "%s work buffer too small: %zu < %zu", what, sw->work_bytes,
+                    tmh_battery_sweep_work_bytes(1, 1, sw->n_variants));
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (eng->kp.precision != TMH_FP64)   // (as tmh_set_battery)
+        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
+                                 "expansion, and the state of charge depends on every earlier second)", what);
+    if (int rc = set_interval_table(eng, TBL_DISPATCH_SWEEP, &sw->table)) return rc;
+    eng->dsweep = *sw;
+    return TMH_OK;
+}
+
 // the battery fleet series: tmh_set_series' struct cases in its own words (the struct first, as the tables'
 // setters: a bad one is named whatever the engine), and the battery kind's engines only
 int tmh_set_battery_fleet(struct tmh_engine* eng, const tmh_series* fleet)
@@ -4523,6 +4639,19 @@ static int check_interval_tables(const tmh_engine* eng, uint32_t n_chains, int64
                has_demand = eng->tables[TBL_DEMAND].set;
     if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
         return fail(TMH_E_INVAL, "%s are set: no traces in the same call (a caller with traces can sum them)", what);
+    if (eng->tables[TBL_DISPATCH_SWEEP].set) {   // the dispatch sweep runs alone (the last kind: `kind` is another table when there is one)
+        if (kind != TBL_DISPATCH_SWEEP)
+            return fail(TMH_E_INVAL, "the dispatch sweep and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
+        if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
+        if (eng->has_fleet)
+            return fail(TMH_E_INVAL, "the dispatch sweep and a battery fleet series are both set: the fleet series is the battery "
+                                     "kind's (one battery per chain)");
+        if (eng->kp.sites)
+            return fail(TMH_E_INVAL, "the dispatch sweep cannot run with per-chain sites (tmh_set_sites)");
+        if (eng->dsweep.work_bytes < tmh_battery_sweep_work_bytes(n_chains, n_steps, eng->dsweep.n_variants))
+            return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->dsweep.work_bytes,
+                        tmh_battery_sweep_work_bytes(n_chains, n_steps, eng->dsweep.n_variants));
+    }
     if (eng->tables[TBL_DISPATCH].set) {   // battery dispatch runs alone (kind: the first set one, so another table when there is one)
         const char* dsp = TABLE_KINDS[TBL_DISPATCH].name;
         if (kind != TBL_DISPATCH)
@@ -5004,6 +5133,42 @@ static int phase_expand(const StepCtx& c)
                         t = eng->mark(c.s);
                         if (nv == 1) launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY>{}, st, btv, gsv);
                         else launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_SWEEP>{}, st, swv, gsv);
+                        eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
+                    }
+                }
+            } else if (table == TBL_DISPATCH_SWEEP) {
+                // the dispatch sweep (fp64, one site: tmh_set_dispatch_sweep): the battery sweep's groups with battery
+                // dispatch's second -- three launches per group of up to DSWEEP_KV variants, group after group in
+                // stream order, each variant with its own table (13 columns), work buffer, soc row and nine
+                // parameter rows; the statistics go to the first group's replay launch alone
+                if constexpr (!F32 && !S) {
+                    const tmh_dispatch_sweep& sw = eng->dsweep;
+                    const uint64_t ld = c.ivv.ld;
+                    const uint64_t n_iv = ((uint64_t)eng->tables[TBL_DISPATCH_SWEEP].t.n_steps + c.ivv.interval_s - 1) / c.ivv.interval_s;
+                    const uint64_t tstride = n_iv * TMH_DISPATCH_COLS * ld;
+                    const uint64_t wstride = tmh_storage_work_bytes(c.n_chains, c.n_steps) / sizeof(long long);
+                    for (uint32_t v0 = 0; v0 < sw.n_variants; v0 += DSWEEP_KV) {
+                        const uint32_t nv = std::min<uint32_t>(DSWEEP_KV, sw.n_variants - v0);
+                        IntervalsView iv = c.ivv;
+                        iv.sum += (size_t)v0 * tstride;
+                        long long* const work = reinterpret_cast<long long*>(sw.work) + (size_t)v0 * wstride;
+                        long long* const soc = reinterpret_cast<long long*>(sw.soc) + (size_t)v0 * ld;
+                        const long long* const params = reinterpret_cast<const long long*>(sw.params) + (size_t)v0 * TMH_DISPATCH_PARAMS * ld;
+                        const BatteryView btv{StorageView{iv, work, 0, 0, 0}, params};
+                        const SweepView swv{btv, tstride, wstride, nv, 0u};
+                        const StatsView& gsv = v0 == 0 ? sv : StatsView{};
+                        // a group of one variant is battery dispatch itself: its own instantiations, at their occupancy
+                        hipEvent_t t = eng->mark(c.s);
+                        if (nv == 1) launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_MAP>{}, st, btv, StatsView{});
+                        else launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_MAP | OUT_SWEEP>{}, st, swv, StatsView{});
+                        eng->close(TMH_K_STORAGE_MAP, t, c.s);
+                        t = eng->mark(c.s);
+                        hipLaunchKernelGGL(dispatch_sweep_scan_kernel, dim3(c.cb(), nv), dim3(256), 0, c.s, work, soc, params,
+                                           eng->kp.ids, c.n_chains, c.sg.nblk, wstride, ld);
+                        eng->close(TMH_K_STORAGE_SCAN, t, c.s);
+                        t = eng->mark(c.s);
+                        if (nv == 1) launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH>{}, st, btv, gsv);
+                        else launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SWEEP>{}, st, swv, gsv);
                         eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
                     }
                 }

@@ -1760,6 +1760,12 @@ struct BatteryFleetView {
 // group are empty lossless batteries in registers: never loaded, stored or flushed, their seconds skipped (nv is
 // wave-uniform: scalar branches).  A group of one variant runs the battery kind's own instantiations instead.
 constexpr int SWEEP_KV = 4;
+// The dispatch sweep (OUT_SWEEP | OUT_DISPATCH, tmh_dispatch_sweep): the same view, a variant's parameters 9 * ld
+// elements after the one before, its table n_intervals * TMH_DISPATCH_COLS * ld; DSWEEP_KV variants per lane and
+// launch, a count of this kind's own (dispatch carries three more parameters, one more 64-bit sum and the four
+// peak registers per variant: DESIGN.md, Dispatch sweep).  A group of one variant runs battery dispatch's own
+// instantiations.
+constexpr int DSWEEP_KV = 4;
 struct SweepView {
     BatteryView bt;
     uint64_t tstride, wstride;

@@ -35,6 +35,12 @@ SoC are `battery`'s bit for bit and column 10 is 0; with C = 0 and L = NO_LIMIT 
 6 and 7; with C = 0 and any L, [5] + [10] is the registers' export.  The ask depends on d and the chain's
 constants only, so the second is still a clamped addition followed by the drain's: `second_maps` gives the
 triples that storage.compose / storage.apply fold.  `from_traces` is the contract as a plain loop.
+
+The dispatch sweep (BatchedSim.enable_dispatch_sweep, tmh_set_dispatch_sweep) runs the same rule for K <= SWEEP_MAX
+parameter sets per chain in one run -- one household under K rules and batteries: params [K, 9, n]
+(`quantize_sweep_params`), the state of charge [K, n], the tables [K, n_intervals, 13, n], variant v's slice of each
+what the single kind is given and gives.  `sweep_from_traces` is that contract as one loop with the state [K, n],
+`sweep_summary` the run's totals, shares and peaks per variant and chain.
 """
 from __future__ import annotations
 
@@ -187,4 +193,142 @@ def to_watts(raw, interval_s, n_steps=None):
         v, o = demand.unpack(raw[:, col])
         out["peak_w_" + name] = v / scale
         out["t_peak_" + name] = np.where(o >= 0, o, np.nan).astype(np.float64)
+    return out
+
+
+SWEEP_MAX = 16   # TMH_DISPATCH_SWEEP_MAX: the variants of one dispatch sweep
+
+
+def check_sweep_params(params):
+    """Sweep parameters as an int64 [K, 9, n] array, 1 <= K <= SWEEP_MAX, every variant inside tmh_dispatch's
+    ranges (check_params per variant; ValueError otherwise)."""
+    params = np.asarray(params.cpu() if hasattr(params, "cpu") else params)
+    if params.ndim != 3 or params.shape[1] != len(PARAMS) or params.dtype != np.int64:
+        raise ValueError("dispatch sweep params must be an int64 [K, 9, n] array")
+    if not 1 <= params.shape[0] <= SWEEP_MAX:
+        raise ValueError(f"dispatch sweep: {params.shape[0]} variants outside [1, {SWEEP_MAX}]")
+    for p in params:
+        check_params(p)
+    return params
+
+
+def quantize_sweep_params(capacity_wh, charge_w, discharge_w, charge_eff=1.0, discharge_eff=1.0, standby_w=0.0,
+                          charge_above_w=0.0, discharge_above_w=0.0, feed_in_limit_w=None, *, n, n_variants=None):
+    """The int64 [K, 9, n] parameters of a dispatch sweep: each quantity a scalar (every variant and chain), a
+    sequence of K values (one per variant, uniform over the chains) or a [K, n] array; quantised per variant by
+    quantize_params.  feed_in_limit_w=None, or an entry that is None, means no limit.  K is n_variants when
+    given, else the longest argument's length; ValueError when an argument's length is neither 1 nor K or K is
+    outside [1, SWEEP_MAX]."""
+    none_w = NO_LIMIT / float(1 << FRAC_BITS)
+    if feed_in_limit_w is None:
+        feed_in_limit_w = none_w
+    elif not np.isscalar(feed_in_limit_w):
+        lim = np.asarray(feed_in_limit_w, dtype=object)
+        feed_in_limit_w = np.where(lim == None, none_w, lim).astype(np.float64)   # noqa: E711 (elementwise)
+    args = [np.asarray(v, dtype=np.float64) for v in (capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff,
+                                                      standby_w, charge_above_w, discharge_above_w, feed_in_limit_w)]
+    if any(a.ndim > 2 for a in args):
+        raise ValueError("dispatch sweep quantities are scalars, [K] sequences or [K, n] arrays")
+    k = int(n_variants) if n_variants is not None else max([a.shape[0] for a in args if a.ndim] or [1])
+    if not 1 <= k <= SWEEP_MAX:
+        raise ValueError(f"dispatch sweep: {k} variants outside [1, {SWEEP_MAX}]")
+    for name, a in zip(PARAMS, args):
+        if a.ndim and a.shape[0] not in (1, k):
+            raise ValueError(f"dispatch sweep {name}: {a.shape[0]} values for {k} variants")
+        if a.ndim == 2 and a.shape[1] not in (1, int(n)):
+            raise ValueError(f"dispatch sweep {name}: {a.shape[1]} values for {n} chains")
+    rows = [np.broadcast_to(a if a.ndim == 2 else a.reshape(-1, 1), (k, a.shape[1] if a.ndim == 2 else 1)) for a in args]
+    return np.stack([quantize_params(*(r[v] for r in rows), n=int(n)) for v in range(k)])
+
+
+def quantize_sweep_soc(soc0_wh, params):
+    """The starting SoC [K, n] of a sweep's batteries from watt-hours (a scalar, [K] or [K, n]); ValueError
+    outside [0, C]."""
+    k, _, n = params.shape
+    a = np.asarray(soc0_wh, dtype=np.float64)
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)
+    a = np.broadcast_to(a, (k, n))
+    return np.stack([quantize_soc(a[v], params[v]) for v in range(k)])
+
+
+def sweep_from_traces(pv, meter, covered, interval_s, *, params, soc0, origin=0):
+    """The dispatch sweep of time-major traces [n_steps, n_chains]: every chain under each of K rule sets --
+    (int64 [K, n_intervals, 13, n_chains], int64 [K, n_chains]), variant v what from_traces gives for params[v]
+    and soc0[v].  One loop over the seconds with the state [K, n]: the second's rule is written out here on
+    [K, n] arrays, apart from from_traces, _ask and _second, so that comparing the two compares two derivations.
+    params: int64 [K, 9, n_chains]; soc0: a scalar, [K, 1] or [K, n_chains], clamped into [0, C]."""
+    pv, meter, covered = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (pv, meter, covered))
+    base = intervals.from_traces(pv, meter, covered, interval_s, origin=origin)      # (checks the arguments)
+    interval_s, origin = int(interval_s), int(origin)
+    if interval_s > MAX_INTERVAL_S:
+        raise ValueError("interval_s <= 2^23 - 1")
+    n_steps, n = pv.shape
+    params = check_sweep_params(params)
+    if params.shape[2] != n:
+        raise ValueError(f"dispatch sweep params for {params.shape[2]} chains, traces of {n}")
+    K = params.shape[0]
+    cap, pc, pd, ec, ed, sb, tc, td, lim = (params[:, r] for r in range(9))              # [K, n] each
+    kc, kd = ((1 << 32) - 1) // ec + 1, ((1 << 32) - 1) // ed + 1
+    out = np.zeros((K, base.shape[0], len(COLUMNS), n), dtype=np.int64)
+    out[:, :, :4] = base[None]
+    x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (K, n)), 0, cap)
+    nan = np.isnan(pv) | np.isnan(meter) | (covered == 255)
+    qd = np.where(nan, 0, quantize(pv) - quantize(meter)).astype(np.int64)
+    for t in range(n_steps):
+        k, o = divmod(origin + t, interval_s)
+        oks, d = ~nan[t][None], qd[t][None]                                 # [1, n] against the variants' [K, n]
+        charge = np.minimum(np.clip(d - tc, 0, None), pc)                   # from the surplus above Tc
+        drain = np.minimum(np.clip(-d - td, 0, None), pd)                   # into the deficit above Td
+        ask = np.where(d >= 0, charge, -drain)
+        up = ask >= 0
+        mag = np.abs(ask)
+        stored = np.where(up, (mag * ec) >> 16, -((mag * kd + 65535) >> 16))
+        x1 = np.minimum(np.maximum(x + stored, 0), cap)
+        moved = x1 - x
+        cost = np.where(moved > 0, (moved * kc + 65535) >> 16, (-moved * ed) >> 16)   # at the meter side, unsigned
+        clipped = np.sign(moved) * np.minimum(mag, cost)
+        b = np.where(moved == stored, ask, clipped)
+        xn = np.maximum(x1 - sb, 0)
+        rest = d - b                                                        # left at the meter
+        imp = np.where(rest < 0, -rest, 0)
+        sur = np.where(rest > 0, rest, 0)
+        fed = np.where(sur > lim, lim, sur)
+        cell = out[:, k]
+        cell[:, 4] += np.where(oks, imp, 0)
+        cell[:, 5] += np.where(oks, fed, 0)
+        cell[:, 6] += np.where(oks, np.maximum(b, 0), 0)
+        cell[:, 7] += np.where(oks, np.maximum(-b, 0), 0)
+        cell[:, 8] = np.where(oks, ((o + 1) << KEY_SHIFT) | xn, cell[:, 8])
+        cell[:, 9] += np.where(oks, b - (xn - x), 0)
+        cell[:, 10] += np.where(oks, sur - fed, 0)
+        cell[:, 11] = np.maximum(cell[:, 11], np.where(oks, demand.pack(imp, o), 0))
+        cell[:, 12] = np.maximum(cell[:, 12], np.where(oks, demand.pack(fed, o), 0))
+        x = np.where(oks, xn, x)
+    return out, x
+
+
+def sweep_summary(raw, interval_s, params, fleet=False):
+    """Per variant and chain, over all the intervals of a raw dispatch sweep table [K, n_intervals, 13, n] with
+    the parameters [K, 9, n]: battery.sweep_summary's keys (self_consumption with the curtailed energy taken out,
+    as to_watts: (pv - export - curtailed) / pv) plus energy_wh_curtailed, curtailed_share = curtailed /
+    available PV (NaN without PV) and peak_w_import and peak_w_export, the run's largest import and feed-in
+    behind the battery in W -- float64 [K, n] each.  fleet=True: [K], of the integer totals over the chains; the
+    peaks are then the largest of any chain (the chains' peaks need not coincide: not the fleet's peak)."""
+    raw = np.asarray(raw.cpu() if hasattr(raw, "cpu") else raw).astype(np.int64, copy=False)
+    params = check_sweep_params(params)
+    if raw.ndim != 4 or raw.shape[2] != len(COLUMNS) or raw.shape[0] != params.shape[0] or raw.shape[3] != params.shape[2]:
+        raise ValueError("raw dispatch sweep table must be [K, n_intervals, 13, n] with params [K, 9, n]")
+    out = battery.sweep_summary(raw[:, :, :10], interval_s, params[:, :6], fleet=fleet)
+    tot = raw.sum(axis=1)                                                   # [K, 13, n] (columns 8, 11, 12 are keys: unused)
+    pk_im = demand.unpack(raw[:, :, 11])[0].max(axis=1) if raw.shape[1] else np.zeros(tot[:, 0].shape, dtype=np.int64)
+    pk_ex = demand.unpack(raw[:, :, 12])[0].max(axis=1) if raw.shape[1] else np.zeros(tot[:, 0].shape, dtype=np.int64)
+    if fleet:
+        tot = tot.sum(axis=2)
+        pk_im, pk_ex = (p.max(axis=1) if p.shape[1] else np.zeros(p.shape[0], dtype=np.int64) for p in (pk_im, pk_ex))
+    e, scale = float(1 << FRAC_BITS) * 3600.0, float(1 << FRAC_BITS)
+    pv, exp, cur = tot[:, 0], tot[:, 5], tot[:, 10]
+    qpv = np.where(pv != 0, pv, np.nan).astype(np.float64)
+    out.update({"energy_wh_curtailed": cur / e, "curtailed_share": cur / qpv, "self_consumption": (pv - exp - cur) / qpv,
+                "peak_w_import": pk_im / scale, "peak_w_export": pk_ex / scale})
     return out

@@ -108,6 +108,9 @@ for _kind, _t in _TABLES.items():   # no table beside battery storage, whichever
     # (enable_battery_sweep: the battery sweep, a kind with descriptor and attributes of its own)
     _t["enable_excludes"] += (("_battery_sweep", "the battery sweep is enabled: one table output per sim "
                                                  "(the battery sweep runs alone)"),)
+    # (enable_dispatch_sweep: the dispatch sweep, likewise)
+    _t["enable_excludes"] += (("_dispatch_sweep", "the dispatch sweep is enabled: one table output per sim "
+                                                  "(the dispatch sweep runs alone)"),)
 
 
 class BatchedSim:
@@ -217,6 +220,8 @@ class BatchedSim:
         self._battery_fleet = None
         self.battery_sweep_raw = None   # int64 [K, n_intervals, 10, n]: the battery sweep's tables (enable_battery_sweep)
         self._battery_sweep = self._sweep_args = self._sweep_work = self._sweep_desc = None
+        self.dispatch_sweep_raw = None   # int64 [K, n_intervals, 13, n]: the dispatch sweep's tables (enable_dispatch_sweep)
+        self._dispatch_sweep = self._dsweep_args = self._dsweep_work = self._dsweep_desc = None
         self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
@@ -675,6 +680,8 @@ class BatchedSim:
         for kind, t in _TABLES.items():
             if getattr(self, "_" + kind) is not None:
                 raise ValueError(f"{t['name']} is enabled: one table output per sim (the battery sweep runs alone)")
+        if self._dispatch_sweep is not None:
+            raise ValueError("the dispatch sweep is enabled: one table output per sim (the battery sweep runs alone)")
         if self.sites is not None:
             raise ValueError("the battery sweep cannot run with per-chain sites")
         from . import battery
@@ -743,6 +750,111 @@ class BatchedSim:
         _torch().cuda.synchronize(self.device)
         t = self._battery_sweep
         return [to_watts(raw, t.interval_s, n_steps=t.n_steps) for raw in self.battery_sweep_raw]
+
+    # ------------------------------------------------------------------ the dispatch sweep
+    def enable_dispatch_sweep(self, n_steps, interval_s=900, *, n_variants=None, capacity_wh=None, charge_w=None,
+                              discharge_w=None, charge_eff=1.0, discharge_eff=1.0, standby_w=0.0, charge_above_w=0.0,
+                              discharge_above_w=0.0, feed_in_limit_w=None, soc0_wh=0.0, step0=None, buffer=None, soc=None,
+                              params=None):
+        """enable_dispatch for K rule sets per chain in one run (tmhpvsim_amd.dispatch, tmh_dispatch_sweep): every
+        chain -- the same pv and meter second for second -- under each of K sets of battery, thresholds and
+        feed-in limit, variant v's table and state of charge bit for bit what enable_dispatch gives for its
+        parameters.  Each quantity is a scalar, a sequence of K values (one per variant, uniform over the chains)
+        or a [K, n] array; feed_in_limit_w entries may be None (dispatch.quantize_sweep_params); or pass params, a
+        ready int64 device tensor [K, 9, n] (checked with dispatch.check_params per variant).  Returns the raw
+        int64 tensor [K, n_intervals, 13, n]; `sim.soc` is the int64 [K, n] state of charge, `sim.dispatch_params`
+        the parameters [K, 9, n].  buffer, soc, params: tensors of those shapes to use, possibly column slices of
+        wider [.., N] tensors of one width.  fp64 only, no traces, no fleet series, no battery fleet series, no
+        other table, no per-chain sites; compaction is allowed.  n_steps=None switches the output off."""
+        torch = _torch()
+        L = self.L
+        if n_steps is None:
+            _lib.check(L.tmh_set_dispatch_sweep(self._eng, None))
+            if self._dispatch_sweep is not None:
+                self.soc = self.dispatch_params = None
+            self.dispatch_sweep_raw = self._dispatch_sweep = self._dsweep_args = self._dsweep_work = self._dsweep_desc = None
+            return None
+        if self.precision != _lib.TMH_FP64:
+            raise ValueError("the dispatch sweep needs precision='fp64': an fp32 engine replaces its guard-band seconds "
+                             "after the expansion, and the state of charge depends on every earlier second")
+        if self._series is not None:
+            raise ValueError("a fleet series is enabled: one table output per sim (the dispatch sweep runs alone)")
+        if self._battery_fleet is not None:
+            raise ValueError("a battery fleet series is enabled: it is the battery kind's (the dispatch sweep runs alone)")
+        for kind, t in _TABLES.items():
+            if getattr(self, "_" + kind) is not None:
+                raise ValueError(f"{t['name']} is enabled: one table output per sim (the dispatch sweep runs alone)")
+        if self._battery_sweep is not None:
+            raise ValueError("the battery sweep is enabled: one table output per sim (the dispatch sweep runs alone)")
+        if self.sites is not None:
+            raise ValueError("the dispatch sweep cannot run with per-chain sites")
+        from . import dispatch
+        n_steps, interval_s = int(n_steps), int(interval_s)
+        if n_steps < 1 or interval_s < 1 or interval_s > dispatch.MAX_INTERVAL_S:
+            raise ValueError(f"enable_dispatch_sweep: n_steps >= 1 and 1 <= interval_s <= {dispatch.MAX_INTERVAL_S}")
+        npar = len(dispatch.PARAMS)
+        if params is None:
+            if capacity_wh is None or charge_w is None or discharge_w is None:
+                raise ValueError("enable_dispatch_sweep: capacity_wh, charge_w and discharge_w (or params) are required")
+            host = dispatch.quantize_sweep_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
+                                                  charge_above_w, discharge_above_w, feed_in_limit_w, n=self.n,
+                                                  n_variants=n_variants)
+            params = torch.from_numpy(host).to(self.device)
+        else:
+            if (params.dtype != torch.int64 or params.device != self.device or params.dim() != 3
+                    or tuple(params.shape[1:]) != (npar, self.n) or (self.n > 1 and params.stride(2) != 1)):
+                raise ValueError(f"dispatch sweep params must be an int64 [K, {npar}, {self.n}] tensor on {self.device}, chains contiguous")
+            host = dispatch.check_sweep_params(params)
+        K = int(host.shape[0])
+        if n_variants is not None and int(n_variants) != K:
+            raise ValueError(f"enable_dispatch_sweep: n_variants {n_variants} but parameters of {K} variants")
+        if soc is None:
+            soc = torch.from_numpy(dispatch.quantize_sweep_soc(soc0_wh, host)).to(self.device)
+        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (K, self.n)
+              or (self.n > 1 and soc.stride(1) != 1)):
+            raise ValueError(f"dispatch sweep soc must be an int64 [{K}, {self.n}] tensor on {self.device}, chains contiguous")
+        nk, nc = dispatch.n_intervals(n_steps, interval_s), len(dispatch.COLUMNS)
+        if buffer is None:
+            buffer = torch.zeros(K, nk, nc, self.n, dtype=torch.int64, device=self.device)
+        elif buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (K, nk, nc, self.n):
+            raise ValueError(f"dispatch sweep buffer must be an int64 [{K}, {nk}, {nc}, {self.n}] tensor on {self.device}")
+        ld = int(buffer.stride(2))
+        if (ld < self.n or (self.n > 1 and buffer.stride(3) != 1) or (nk > 1 and buffer.stride(1) != nc * ld)
+                or (K > 1 and buffer.stride(0) != nk * nc * ld)):
+            raise ValueError(f"dispatch sweep buffer strides {tuple(buffer.stride())}: need ({nk * nc} ld, {nc} ld, ld, 1) "
+                             f"with ld >= {self.n}")
+        if int(params.stride(1)) != ld or (K > 1 and (int(params.stride(0)) != npar * ld or int(soc.stride(0)) != ld)):
+            raise ValueError(f"dispatch sweep params strides {tuple(params.stride())}, soc strides {tuple(soc.stride())}: need "
+                             f"({npar} ld, ld, 1) and (ld, 1) with the table's ld {ld}: slice them from tensors of the same width")
+        table = _lib.Intervals(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
+        nb = L.tmh_battery_sweep_work_bytes(self.n, min(n_steps, 86400), K)
+        work = self._dsweep_work
+        if work is None or work.numel() < nb:
+            work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
+        sw = _lib.DispatchSweep(table, soc.data_ptr(), work.data_ptr(), work.numel(), params.data_ptr(), K)
+        _lib.check(L.tmh_set_dispatch_sweep(self._eng, C.byref(sw)))
+        self._dispatch_sweep, self._dsweep_desc, self._dsweep_args, self._dsweep_work = table, sw, (soc, params), work
+        self.dispatch_sweep_raw, self.soc, self.dispatch_params = buffer, soc, params
+        return buffer
+
+    def _dsweep_window(self, win):
+        """run(): the dispatch sweep's work buffer holds a window of `win` steps (as _sweep_window)."""
+        sw = self._dsweep_desc
+        need = self.L.tmh_battery_sweep_work_bytes(self.n, int(win), int(sw.n_variants))
+        if self._dsweep_work.numel() < need:
+            _torch().cuda.synchronize(self.device)
+            self._dsweep_work = _torch().empty(need, dtype=torch_uint8(), device=self.device)
+            sw.work, sw.work_bytes = self._dsweep_work.data_ptr(), self._dsweep_work.numel()
+            _lib.check(self.L.tmh_set_dispatch_sweep(self._eng, C.byref(sw)))
+
+    def dispatch_sweep(self):
+        """The sweep's tables in watts and watt-hours: a list of dispatch.to_watts dicts, one per variant."""
+        from .dispatch import to_watts
+        if self.dispatch_sweep_raw is None:
+            raise ValueError("no dispatch sweep tables: call enable_dispatch_sweep first")
+        _torch().cuda.synchronize(self.device)
+        t = self._dispatch_sweep
+        return [to_watts(raw, t.interval_s, n_steps=t.n_steps) for raw in self.dispatch_sweep_raw]
 
     # ------------------------------------------------------------------ the battery fleet series
     def enable_battery_fleet(self, n_steps, step0=None, group_chains=0, buffer=None):
@@ -853,6 +965,15 @@ class BatchedSim:
                                  "(battery.sweep_from_traces)")
             if self.step < tb.step0 or self.step + n_steps > tb.step0 + tb.n_steps:
                 raise ValueError(f"steps [{self.step}, +{n_steps}) outside the battery sweep tables [{tb.step0}, +{tb.n_steps})")
+        if self._dispatch_sweep is not None:   # (likewise; compact=True is allowed)
+            tb = self._dispatch_sweep
+            if self._series is not None:
+                raise ValueError("the dispatch sweep and a fleet series are both enabled: one of the two per sim")
+            if trace:
+                raise ValueError("a dispatch sweep run takes no traces (trace=()): run the rules over the traces instead "
+                                 "(dispatch.sweep_from_traces)")
+            if self.step < tb.step0 or self.step + n_steps > tb.step0 + tb.n_steps:
+                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the dispatch sweep tables [{tb.step0}, +{tb.n_steps})")
         if self._battery_fleet is not None:   # (the library refuses each too, window by window)
             if compact:
                 raise ValueError("a battery fleet series cannot run compacted (a compacted tile would mix groups)")
@@ -879,6 +1000,8 @@ class BatchedSim:
             self._storage_window(win)
         if self._battery_sweep is not None:
             self._sweep_window(win)
+        if self._dispatch_sweep is not None:
+            self._dsweep_window(win)
         if compact and n_steps > win:
             with torch.cuda.device(self.device):
                 self._run_compacted(n_steps, win, st)
