@@ -42,7 +42,9 @@
  *    (tmh_dispatch: the battery kind with a charge threshold, a discharge threshold and a
  *    feed-in limit per chain, the curtailed energy and the peaks behind the battery), or the
  *    dispatch sweep (tmh_dispatch_sweep: battery dispatch's table and state of charge for each
- *    of up to TMH_DISPATCH_SWEEP_MAX rule sets per chain, in one run).
+ *    of up to TMH_DISPATCH_SWEEP_MAX rule sets per chain, in one run), or scheduled dispatch
+ *    (tmh_schedule: battery dispatch with up to TMH_SCHEDULE_RULES_MAX rule sets per chain, one
+ *    of them in force per metering interval, and charging from the grid).
  *  - `stream` is a hipStream_t (NULL = default stream); all work is enqueued
  *    asynchronously on it.  One engine per device; not re-entrant per engine.
  */
@@ -468,6 +470,50 @@ typedef struct tmh_dispatch_sweep {
     uint32_t n_variants;      /* 1 .. TMH_DISPATCH_SWEEP_MAX */
 } tmh_dispatch_sweep;
 
+/* Scheduled dispatch: battery dispatch (tmh_dispatch above) whose rule changes at known times -- a time-of-use
+ * tariff (discharge only in the expensive hours), charging from the grid in the cheap hours, delayed charging
+ * under a feed-in limit, a controller that picks the thresholds per quarter hour.  A chain has one battery and
+ * n_rules rule sets; one array shared by all chains of the engine says which rule is in force in each metering
+ * interval of the table.  tmh_dispatch stays as it is; this kind reproduces it bit for bit (all thirteen columns
+ * and soc) when no rule charges from the grid and the chain's rules are equal, when n_rules = 1, and when the
+ * array names one rule throughout.  Integers in the series' units as above.
+ * params: device int64 [6 + 4 * n_rules][ld] of the caller, laid out and read as tmh_dispatch's (row stride ld,
+ * indexed per chain: ids[slot] under tmh_set_chain_ids; a column slice of a wider tensor is valid).  Rows 0-5 are
+ * tmh_battery's exactly (C, Pc, Pd, ec, ed, sigma), constant over the run; rows 6 + 4r .. 9 + 4r are rule r's
+ *   Tc  charge threshold       0 .. 2^27      Td  discharge threshold                      0 .. 2^27
+ *   L   feed-in limit, 2^27 = none            G   grid-charge power, 0 = none              0 .. 2^27
+ * each clamped into its range as a lane loads it.  A "hold" rule is Tc = Td = 2^27.
+ * rule_of_interval: device uint8 [n_intervals], n_intervals = ceil(table.n_steps / table.interval_s): entry k is
+ * the rule of the table's interval k, on the table's own grid and origin -- the index a window's step j has as
+ * (step0 + j - table.step0) / interval_s.  Read by every window, never written; the kernels use min(entry,
+ * n_rules - 1), so no address depends on an unchecked value.  Per-chain behaviour lives in the rule parameters (a
+ * chain without a tariff gives all its rules the same values), not in the array.
+ * An ok second in interval k, with (Tc, Td, L, G) the chain's rule rule_of_interval[k], d = q(pv) - q(meter) and
+ * the SoC x before it:
+ *   a0 = tmh_dispatch's ask: d >= 0 ? min(max(d - Tc, 0), Pc) : -min(max(-d - Td, 0), Pd)
+ *   a  = G == 0 ? a0 : min(max(a0, 0) + G, Pc)            a grid-charging rule never discharges
+ *   s, x1, g, b, x', r = d - b, import_b, export_b = min(max(r, 0), L), curtailed, loss: tmh_dispatch's on this a
+ * With G > 0, b may exceed max(d, 0): the difference is bought from the grid and is part of import_b (< 2^26 +
+ * 2^27).  |a| <= max(Pc, Pd) as before and the ask depends on d, the chain's constants and the time only, never
+ * on x: the second is still tmh_battery's pair of clamped additions and the three launches carry over.
+ * table.sum: device int64 [n_intervals][TMH_DISPATCH_COLS][ld], zero-initialised by the caller: tmh_dispatch's
+ * thirteen columns with the same meanings.  For every cell [4] - [5] == [1] - [0] + [6] - [7] + [10], columns 4-7,
+ * 9 and 10 are >= 0, [6] - [7] - [9] is the interval's SoC change and the peak in [12] is <= the L of the
+ * interval's rule.  The bits do not depend on windows, pipelining, batches, column slices or compaction and equal
+ * a sequential loop over the traces.  fp64 engines and the engine's one site only.  soc, work and work_bytes:
+ * tmh_dispatch's (tmh_storage_work_bytes). */
+#define TMH_SCHEDULE_RULES_MAX 8
+#define TMH_SCHEDULE_RULE_PARAMS 4
+typedef struct tmh_schedule {
+    tmh_intervals table;      /* sum is [n_intervals][13][ld] */
+    int64_t* soc;             /* device [ld]: as tmh_battery's */
+    void* work;               /* device scratch */
+    size_t work_bytes;        /* >= tmh_storage_work_bytes(n_chains, n_steps) of the largest window */
+    const int64_t* params;    /* device [6 + 4 * n_rules][ld], ld = table.ld */
+    const uint8_t* rule_of_interval;   /* device [n_intervals] */
+    uint32_t n_rules;         /* 1 .. TMH_SCHEDULE_RULES_MAX */
+} tmh_schedule;
+
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
 /* TMH_SERIES_FRAC_BITS and TMH_SERIES_MAX_W as the library was built with them */
@@ -713,6 +759,16 @@ int tmh_set_dispatch(struct tmh_engine* eng, const tmh_dispatch* dp);
  * sweep and battery dispatch included; tmh_set_series or tmh_set_battery_fleet set; per-chain sites
  * (tmh_set_sites). */
 int tmh_set_dispatch_sweep(struct tmh_engine* eng, const tmh_dispatch_sweep* sw);
+/* Scheduled dispatch (tmh_schedule above): as tmh_set_dispatch, with 6 + 4 * n_rules parameter rows and the rule
+ * array.  Every later expansion clamps sc->soc into [0, C], advances it over its window and adds the window to
+ * sc->table.sum in the battery kind's three launches (the same TMH_K_STORAGE_* slots time them); NULL switches
+ * it off.  Refused here (TMH_E_INVAL, the messages name "schedule"): everything tmh_set_dispatch refuses;
+ * n_rules 0 or above TMH_SCHEDULE_RULES_MAX; a NULL rule_of_interval; work_bytes below
+ * tmh_storage_work_bytes(1, 1).  Refused at a step / expansion call or a walk of that window, before any launch:
+ * everything tmh_set_dispatch's step refuses (traces, the work buffer against the window, ...); any other table
+ * kind set too, in either order; tmh_set_series or tmh_set_battery_fleet set; per-chain sites (tmh_set_sites).
+ * The parameters' and the array's values are not read on the host: the kernels clamp them. */
+int tmh_set_schedule(struct tmh_engine* eng, const tmh_schedule* sc);
 /* Tests only: the fp32 guard-band records (chain, block) the last expansion on
  * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
  * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
@@ -827,7 +883,7 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * TMH_OUT_BATTERY (the battery kind, likewise), TMH_OUT_BATTERY_FLEET (the battery kind with its fleet
  * series: the replay pass that fills both), TMH_OUT_BATTERY_SWEEP (the battery sweep),
  * TMH_OUT_DISPATCH (battery dispatch: its replay pass, with or without statistics),
- * TMH_OUT_DISPATCH_SWEEP (the dispatch sweep), plus
+ * TMH_OUT_DISPATCH_SWEEP (the dispatch sweep), TMH_OUT_SCHEDULE (scheduled dispatch: its replay pass), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
@@ -843,6 +899,7 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
 #define TMH_OUT_BATTERY_SWEEP 10
 #define TMH_OUT_DISPATCH 11
 #define TMH_OUT_DISPATCH_SWEEP 12
+#define TMH_OUT_SCHEDULE 13
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

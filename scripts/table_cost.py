@@ -3,8 +3,8 @@
 kernel) of the statistics-only expansion and of the expansions with a table, same chains,
 same window, same process, the runs alternating.
 
-    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet|battery_sweep|dispatch|dispatch_sweep
-                                 [--variants 5] [--chains 65536] [--steps 86400]
+    python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet|battery_sweep|dispatch|dispatch_sweep|schedule
+                                 [--variants 5] [--rules 1] [--chains 65536] [--steps 86400]
                                  [--interval 900] [--rounds 5] [--precision fp32]
                                  [--start "2019-09-05 00:00:00"] [--out FILE.json]
                                  [--modules 1 --capacity-wh 5000 --charge-w 2500 --discharge-w 2500]
@@ -51,6 +51,15 @@ The runs of a kind, each with the same statistics beside its table:
              three launches are timed for both (the sweep's slots sum its groups' launches); the yardstick is K x the
              dispatch kind's median of the same run: ratio_sweep_k_dispatch = sweep / (K x dispatch) for the whole
              expansion and per launch, beside the spread of each run's own rounds.
+  schedule:  OUT_DISPATCH and OUT_SCHEDULE, dispatch's setting with statistics beside both -- the unchanged dispatch kind
+             (one rule per chain) and scheduled dispatch, alternating.  --rules 1: the schedule has that one rule, and
+             the warm-up round's tables and soc are the dispatch kind's bit for bit.  --rules 4: four hourly rules (the
+             rule of interval k is (k * interval // 3600) % 4) -- dispatch's own, one charging from the grid at a fifth of
+             --charge-w, a hold, and dispatch's with the thresholds and the limit halved; the script checks the schedule
+             table's identities, that the grid rule's intervals never discharge, the hold's neither charge nor
+             discharge, and that the table differs from the dispatch kind's.  The kind's three launches are timed for
+             both; schedule / dispatch for the whole expansion and per launch, with medians and ranges, beside the
+             spread (max / min) of the dispatch kind's own rounds.
 The script checks each run's variant, these identities (on the warm-up round's tables), that
 the statistics of all runs agree bit for bit and that every table's ok seconds equal the
 histogram's count.  One warm-up round, then --rounds timed ones.  Prints one JSON line: the
@@ -79,6 +88,7 @@ RUNS = {
     "battery_sweep": (("battery", "battery"), ("battery_sweep", "battery_sweep")),   # (sweep_cost: a loop of its own)
     "dispatch": (("battery", "battery"), ("dispatch", "dispatch")),                  # (dispatch_cost: likewise)
     "dispatch_sweep": (("dispatch", "dispatch"), ("dispatch_sweep", "dispatch_sweep")),   # (dsweep_cost: likewise)
+    "schedule": (("dispatch", "dispatch"), ("schedule", "schedule")),                     # (schedule_cost: likewise)
 }
 
 
@@ -338,6 +348,93 @@ def dsweep_cost(a, mp, lossy):
                 build_stamp=_lib.loaded_stamp())
 
 
+def schedule_cost(a, mp, lossy):
+    """--kind schedule: the dispatch kind and scheduled dispatch (a.rules rule sets) over the same batteries, alternating."""
+    import numpy as np
+    import torch
+    from tmhpvsim_amd import _lib
+    from tmhpvsim_amd.engine import BatchedSim
+    rule = dict(charge_above_w=a.charge_above_w, discharge_above_w=a.discharge_above_w, feed_in_limit_w=a.feed_in_limit_w)
+    n_iv = -(-a.steps // a.interval)
+    if a.rules == 1:
+        rules, roi = [dict(rule, grid_charge_w=0.0)], np.zeros(n_iv, dtype=np.uint8)
+    elif a.rules == 4:
+        rules = [dict(rule, grid_charge_w=0.0),
+                 dict(rule, grid_charge_w=a.charge_w / 5),
+                 dict(charge_above_w=32768.0, discharge_above_w=32768.0, feed_in_limit_w=a.feed_in_limit_w, grid_charge_w=0.0),
+                 dict(charge_above_w=a.charge_above_w / 2, discharge_above_w=a.discharge_above_w / 2,
+                      feed_in_limit_w=a.feed_in_limit_w / 2, grid_charge_w=0.0)]
+        roi = ((np.arange(n_iv) * a.interval // 3600) % 4).astype(np.uint8)
+    else:
+        sys.exit("--kind schedule: --rules 1 or 4")
+    parts = (("map", _lib.K_STORAGE_MAP), ("scan", _lib.K_STORAGE_SCAN), ("replay", _lib.K_STORAGE_REPLAY))
+    labels = ("dispatch", "schedule")
+
+    def one(label):
+        sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=mp, precision="fp64", device="cuda:0", horizon=a.steps)
+        sim.enable_stats()
+        raw = sim.enable_dispatch(a.steps, a.interval, **lossy, **rule) if label == "dispatch" else \
+            sim.enable_schedule(a.steps, a.interval, **lossy, rules=rules, rule_of_interval=roi)
+        _lib.check(sim.L.tmh_profile_enable(sim._eng, 1))
+        sim.run(a.steps, trace=(), window=a.steps)
+        torch.cuda.synchronize()
+        ms, launches = _lib.profile_read(sim._eng, _lib.K_EXPAND)
+        want = (_lib.OUT_DISPATCH if label == "dispatch" else _lib.OUT_SCHEDULE) | _lib.OUT_FP64
+        assert launches == 1 and sim.L.tmh_engine_last_expand(sim._eng) == want, (launches, want)
+        pm = {}
+        for name, kk in parts:
+            pm[name], pn = _lib.profile_read(sim._eng, kk)
+            assert pn == 1
+        assert int(raw[:, 2].sum()) == int(sim.hist.sum()) > 0
+        return ms, pm, raw, sim.hist.clone(), sim.soc.clone()
+
+    def check(dp, sc):   # the warm-up round's tables
+        d, s = dp[2], sc[2]
+        assert torch.equal(s[:, :4], d[:, :4]) and torch.equal(dp[3], sc[3])
+        assert bool((s[:, 4:8] >= 0).all()) and bool((s[:, 9:11] >= 0).all())
+        assert torch.equal(s[:, 4] - s[:, 5], s[:, 1] - s[:, 0] + s[:, 6] - s[:, 7] + s[:, 10])
+        assert torch.equal(s[:, 11] != 0, s[:, 2] > 0) and torch.equal(s[:, 12] != 0, s[:, 2] > 0)
+        assert int(d[:, 6].sum()) > 0 and int(d[:, 7].sum()) > 0 and int(d[:, 10].sum()) > 0
+        if a.rules == 1:   # the same rule: the dispatch kind's bits
+            assert torch.equal(s, d) and torch.equal(dp[4], sc[4])
+            return dict(tables_equal=True)
+        r = torch.from_numpy(roi.astype(np.int64)).to(s.device)
+        lim = torch.tensor([int(round(x["feed_in_limit_w"] * 4096)) for x in rules], device=s.device)[r]
+        assert bool(((s[:, 12] >> 32) <= lim[:, None]).all())
+        assert not bool(s[r == 1, 7].any()) and int(s[r == 1, 6].sum()) > 0          # the grid rule never discharges
+        assert not bool(s[r == 2, 6].any()) and not bool(s[r == 2, 7].any())         # hold
+        assert not torch.equal(s[:, 4:], d[:, 4:])
+        return dict(tables_equal=False, differing_cells_import=int((s[:, 4] != d[:, 4]).sum()),
+                    import_schedule_over_dispatch=int(s[:, 4].sum()) / int(d[:, 4].sum()),
+                    charge_schedule_over_dispatch=int(s[:, 6].sum()) / int(d[:, 6].sum()))
+
+    found = check(one("dispatch"), one("schedule"))   # warm-up: code objects, allocator
+    t = {k: [] for k in labels}
+    pt = {k: {name: [] for name, _ in parts} for k in labels}
+    for _ in range(a.rounds):
+        for label in labels:
+            ms, pm, _raw, _hist, _soc = one(label)
+            t[label].append(ms)
+            for name in pm:
+                pt[label][name].append(pm[name])
+            del _raw, _hist, _soc
+    med = {k: statistics.median(t[k]) for k in labels}
+    pmed = {k: {name: statistics.median(v) for name, v in pt[k].items()} for k in labels}
+    return dict(device=torch.cuda.get_device_name(0), chains=a.chains, steps=a.steps, interval_s=a.interval, precision="fp64",
+                start=a.start, rounds=a.rounds, modules=a.modules, battery=lossy, n_rules=a.rules, rules=rules,
+                rule_of_interval=roi.tolist(), **found,
+                **{f"{k}_ms": t[k] for k in labels}, **{f"{k}_median_ms": med[k] for k in labels},
+                **{f"{k}_range_ms": [min(t[k]), max(t[k])] for k in labels},
+                **{f"{k}_{name}_ms": v for k in labels for name, v in pt[k].items()},
+                **{f"{k}_{name}_median_ms": v for k in labels for name, v in pmed[k].items()},
+                **{f"{k}_{name}_range_ms": [min(v), max(v)] for k in labels for name, v in pt[k].items()},
+                ratio_schedule_dispatch=med["schedule"] / med["dispatch"],
+                **{f"ratio_{name}_schedule_dispatch": pmed["schedule"][name] / pmed["dispatch"][name] for name, _ in parts},
+                dispatch_spread=max(t["dispatch"]) / min(t["dispatch"]),
+                **{f"dispatch_{name}_spread": max(v) / min(v) for name, v in pt["dispatch"].items()},
+                build_stamp=_lib.loaded_stamp())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", choices=tuple(RUNS), required=True)
@@ -356,11 +453,12 @@ def main():
     ap.add_argument("--discharge-eff", type=float, default=0.95)
     ap.add_argument("--standby-w", type=float, default=2.0)
     ap.add_argument("--variants", type=int, default=5, help="--kind battery_sweep, dispatch_sweep: the variants per chain")
+    ap.add_argument("--rules", type=int, default=1, help="--kind schedule: 1 (the dispatch kind's rule) or 4 hourly rules")
     ap.add_argument("--charge-above-w", type=float, default=500.0, help="--kind dispatch: the charge threshold")
     ap.add_argument("--discharge-above-w", type=float, default=200.0, help="--kind dispatch: the discharge threshold")
     ap.add_argument("--feed-in-limit-w", type=float, default=1000.0, help="--kind dispatch: the feed-in limit")
     a = ap.parse_args()
-    if a.kind in ("storage", "battery", "battery_fleet", "battery_sweep", "dispatch", "dispatch_sweep"):
+    if a.kind in ("storage", "battery", "battery_fleet", "battery_sweep", "dispatch", "dispatch_sweep", "schedule"):
         a.precision = "fp64"   # (the kind's engines)
     import torch
     from tmhpvsim_amd import _lib
@@ -385,8 +483,9 @@ def main():
     battery = dict(capacity_wh=a.capacity_wh, charge_w=a.charge_w, discharge_w=a.discharge_w, soc0_wh=a.capacity_wh / 2)
     lossy = dict(battery, charge_eff=a.charge_eff, discharge_eff=a.discharge_eff, standby_w=a.standby_w)
     enable_kw = {"storage": battery, "battery": lossy}
-    if a.kind in ("battery_sweep", "dispatch", "dispatch_sweep"):
-        cost = {"battery_sweep": sweep_cost, "dispatch": dispatch_cost, "dispatch_sweep": dsweep_cost}[a.kind]
+    if a.kind in ("battery_sweep", "dispatch", "dispatch_sweep", "schedule"):
+        cost = {"battery_sweep": sweep_cost, "dispatch": dispatch_cost, "dispatch_sweep": dsweep_cost,
+                "schedule": schedule_cost}[a.kind]
         line = json.dumps(cost(a, mp, lossy))
         print(line)
         if a.out:

@@ -114,6 +114,14 @@ class DispatchSweep(C.Structure):
                 ("params", C.c_void_p), ("n_variants", C.c_uint32)]
 
 
+class Schedule(C.Structure):
+    """tmh_schedule: the schedule table (tmh_intervals with 13 columns), the per-chain state of charge, the
+    window's work buffer, the per-chain parameters int64 [6 + 4 * n_rules][ld] and the rule of each of the table's
+    intervals, uint8 [n_intervals] (tmh_set_schedule)."""
+    _fields_ = [("table", Intervals), ("soc", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t),
+                ("params", C.c_void_p), ("rule_of_interval", C.c_void_p), ("n_rules", C.c_uint32)]
+
+
 EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_bytes", "tmh_state_offsets", "tmh_plan_bytes",
            "tmh_scratch_bytes", "tmh_engine_scratch_bytes", "tmh_workspace_bytes", "tmh_engine_create", "tmh_engine_destroy", "tmh_engine_path",
            "tmh_init", "tmh_run", "tmh_plan", "tmh_step", "tmh_probe", "tmh_profile_enable", "tmh_profile_read",
@@ -124,7 +132,7 @@ EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_by
            "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals",
            "tmh_set_registers", "tmh_set_demand", "tmh_set_storage", "tmh_storage_work_bytes", "tmh_set_battery", "tmh_set_battery_fleet",
            "tmh_set_battery_sweep", "tmh_battery_sweep_work_bytes", "tmh_set_dispatch", "tmh_probe_pv",
-           "tmh_set_dispatch_sweep"]
+           "tmh_set_dispatch_sweep", "tmh_set_schedule"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
 K_STORAGE_MAP, K_STORAGE_SCAN, K_STORAGE_REPLAY = 4, 5, 6   # battery storage's three launches (inside K_EXPAND)
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
@@ -142,6 +150,8 @@ OUT_DISPATCH = 11       # battery dispatch (tmh_set_dispatch)
 OUT_DISPATCH_SWEEP = 12  # the dispatch sweep (tmh_set_dispatch_sweep)
 BATTERY_SWEEP_MAX = 16  # TMH_BATTERY_SWEEP_MAX
 DISPATCH_SWEEP_MAX = 16  # TMH_DISPATCH_SWEEP_MAX
+OUT_SCHEDULE = 13       # scheduled dispatch (tmh_set_schedule)
+SCHEDULE_RULES_MAX = 8  # TMH_SCHEDULE_RULES_MAX
 
 _lib = None
 
@@ -251,6 +261,8 @@ def load():
     L.tmh_set_battery_sweep.restype = C.c_int
     L.tmh_set_dispatch_sweep.argtypes = [p, C.POINTER(DispatchSweep)]
     L.tmh_set_dispatch_sweep.restype = C.c_int
+    L.tmh_set_schedule.argtypes = [p, C.POINTER(Schedule)]
+    L.tmh_set_schedule.restype = C.c_int
     L.tmh_battery_sweep_work_bytes.argtypes = [u32, u32, u32]
     L.tmh_battery_sweep_work_bytes.restype = sz
     L.tmh_storage_work_bytes.argtypes = [u32, u32]

@@ -27,6 +27,9 @@ tmhpvsim/metersim.py:79-95).
     python -m tmhpvsim_amd.cli dispatch FILE --batch N --no-realtime --interval S <the battery command's options>
                                              [--charge-above-w P[,P..]] [--discharge-above-w P[,P..]]
                                              [--feed-in-limit-w P|none[,..]] [--all-chains NPZ]
+    python -m tmhpvsim_amd.cli schedule FILE --batch N --no-realtime --interval S <the battery command's options>
+                                             --period HH:MM,CHARGE_ABOVE,DISCHARGE_ABOVE,LIMIT|none,GRID_CHARGE
+                                             [--period ...] [--all-chains NPZ]
 
 Without --batch the commands are the reference's AMQP pipelines (a fanout
 exchange carrying one JSON float per second, pvsim.py:43-84, metersim.py:13-62):
@@ -84,6 +87,11 @@ left of the surplus is fed in up to --feed-in-limit-w (`none`, the default: no l
 are dealt round-robin as `battery` deals them.  The CSV is `battery`'s with `curtailed_wh,peak_import_w,
 peak_export_w` after `n_ok` (export_wh is what was fed in after the limit, pv_wh the available PV); --all-chains
 writes every chain's raw table and its arrays to an .npz.
+`schedule` is `dispatch` under a daily tariff (tmhpvsim_amd.schedule): each --period starts a rule -- the two
+thresholds, the feed-in limit (`none`: no limit) and the power the battery also takes from the grid, in watts -- daily
+at that local time (1 to 8 of them; an interval that contains a period's start still belongs to the period before).
+The CSV is `dispatch`'s with a last column `rule`, the index of the --period in force in the interval; --all-chains
+writes every chain's raw table, its arrays and `rule` to an .npz.
 There is no CPU fallback: the batch mode fails if the engine cannot run.
 """
 from __future__ import annotations
@@ -135,7 +143,7 @@ def _fleet_run(n, start, seconds, seed, precision, bin_s):
 
 
 def _table_run(kind, n, start, seconds, seed, precision, interval_s, fleet_bin=None, **enable_kw):
-    """An engine run with the interval table `kind` ("intervals", "registers", "demand", "storage", "battery" or "dispatch")
+    """An engine run with the interval table `kind` ("intervals", "registers", "demand", "storage", "battery", "dispatch" or "schedule")
     only: the raw table, its watt / watt-hour arrays and, with fleet_bin (the battery kind), the battery fleet
     series' means per bin of fleet_bin seconds (else None).  enable_kw: the kind's own arguments."""
     from .engine import BatchedSim
@@ -286,21 +294,24 @@ FLEET_CSV = (("n_ok", "n_ok"), ("meter", "meter"), ("pv", "pv"), ("import_w", "i
 
 
 def _table_command(kind, file, batch, start, seconds, seed, precision, interval_s, all_chains, fleet=None, bin_s=1,
-                   **enable_kw):
-    """The `intervals`, `registers`, `demand`, `storage`, `battery` and `dispatch` commands: chain 0's rows to FILE, every chain
-    to the .npz; with `fleet` (the battery command's --fleet) the battery fleet series' means per bin to that CSV."""
+                   csv_extra=None, **enable_kw):
+    """The `intervals`, `registers`, `demand`, `storage`, `battery`, `dispatch` and `schedule` commands: chain 0's rows to
+    FILE, every chain to the .npz; with `fleet` (the battery command's --fleet) the battery fleet series' means per bin
+    to that CSV.  csv_extra: {header: one value per interval}, columns after the kind's (and arrays of the .npz)."""
+    csv_extra = csv_extra or {}
     raw, out, fl = _table_run(kind, batch, start, seconds, seed, precision, interval_s,
                               fleet_bin=bin_s if fleet else None, **enable_kw)
     t0 = dt.datetime.fromisoformat(str(start))
     rows = raw.shape[0]
     with open(file, mode="w", newline="") as fh:
         w = csv.writer(fh)
-        w.writerow(["time"] + [name for name, _ in TABLE_CSV[kind]])
+        w.writerow(["time"] + [name for name, _ in TABLE_CSV[kind]] + list(csv_extra))
         for k in range(rows):
-            w.writerow([t0 + dt.timedelta(seconds=k * interval_s)] + [float(out[key][k, 0]) for _, key in TABLE_CSV[kind]])
+            w.writerow([t0 + dt.timedelta(seconds=k * interval_s)] + [float(out[key][k, 0]) for _, key in TABLE_CSV[kind]]
+                       + [int(v[k]) for v in csv_extra.values()])
     if all_chains:
         import numpy as np
-        np.savez(all_chains, raw=raw, interval_s=interval_s, **out)
+        np.savez(all_chains, raw=raw, interval_s=interval_s, **out, **csv_extra)
     if fleet:
         with open(fleet, mode="w", newline="") as fh:
             w = csv.writer(fh)
@@ -454,6 +465,73 @@ def dispatch(file, amqp_url, exchange, verbose, realtime, batch, start, seconds,
                            discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh, charge_above_w=charge_above_w,
                            discharge_above_w=discharge_above_w, feed_in_limit_w=feed_in_limit_w).items()})
     except ValueError as e:   # (a quantity outside its range: dispatch.quantize_params)
+        raise click.ClickException(str(e))
+
+
+def parse_period(text):
+    """One --period of the schedule command, HH:MM,CHARGE_ABOVE,DISCHARGE_ABOVE,LIMIT|none,GRID_CHARGE (watts): the
+    period's start in seconds after local midnight and its rule as schedule.quantize_params takes it.  ValueError
+    naming the period on anything else."""
+    parts = [p.strip() for p in str(text).split(",")]
+    try:
+        if len(parts) != 5:
+            raise ValueError("five fields")
+        hh, mm = parts[0].split(":")
+        if not (hh.isdigit() and mm.isdigit() and 0 <= int(hh) < 24 and 0 <= int(mm) < 60):
+            raise ValueError("HH:MM")
+        lim = None if parts[3].lower() == "none" else float(parts[3])
+        rule = dict(charge_above_w=float(parts[1]), discharge_above_w=float(parts[2]), feed_in_limit_w=lim,
+                    grid_charge_w=float(parts[4]))
+    except ValueError:
+        raise ValueError(f"--period {text!r}: expected HH:MM,CHARGE_ABOVE,DISCHARGE_ABOVE,LIMIT|none,GRID_CHARGE")
+    return int(hh) * 3600 + int(mm) * 60, rule
+
+
+def _period(ctx, param, value):
+    try:
+        return [parse_period(v) for v in value]
+    except ValueError as e:
+        raise click.BadParameter(str(e))
+
+
+TABLE_CSV["schedule"] = TABLE_CSV["dispatch"]
+
+
+@main.command()
+@click.argument("file")
+@common
+@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
+@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
+              help="seconds per metering interval (a last partial interval is kept)")
+@click.option("--capacity-wh", callback=_dealt, required=True, help="battery capacity (Wh); a list is dealt to the chains")
+@click.option("--charge-w", callback=_dealt, required=True, help="charge power limit at the meter side (W)")
+@click.option("--discharge-w", callback=_dealt, required=True, help="discharge power limit at the meter side (W)")
+@click.option("--charge-eff", callback=_dealt, default="1.0", help="charge efficiency in [0.5, 1]")
+@click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]")
+@click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)")
+@click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)")
+@click.option("--period", multiple=True, required=True, callback=_period,
+              help="HH:MM,CHARGE_ABOVE,DISCHARGE_ABOVE,LIMIT|none,GRID_CHARGE: a rule (watts) that starts daily at that local "
+                   "time; 1 to 8 of them")
+def schedule(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
+             charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh, period):
+    """Scheduled dispatch (a daily tariff of rules, grid charging) of chain 0 over --batch chains to FILE (CSV with the
+    rule of each interval; fp64 engine run)."""
+    logging.basicConfig(level=logging.WARN - 10 * verbose)
+    _need_batch(realtime, batch, "schedule")
+    from . import schedule as S
+    from .params import ModelParams
+    if not 1 <= len(period) <= S.RULES_MAX:
+        raise click.ClickException(f"schedule: {len(period)} --period options outside [1, {S.RULES_MAX}]")
+    try:
+        rule_of_interval = S.daily(start, ModelParams(seed=int(seed)).site.tz, int(seconds), int(interval_s),
+                                   [(s, r) for r, (s, _) in enumerate(period)])
+        _table_command("schedule", file, batch, start, seconds, seed, "fp64", interval_s, all_chains,
+                       csv_extra={"rule": rule_of_interval}, rules=[rule for _, rule in period], rule_of_interval=rule_of_interval,
+                       **{k: _deal(v, batch) for k, v in dict(
+                           capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
+                           discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh).items()})
+    except ValueError as e:   # (a quantity outside its range, two periods at one time: schedule.quantize_params, daily)
         raise click.ClickException(str(e))
 
 

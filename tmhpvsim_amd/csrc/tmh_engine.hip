@@ -103,6 +103,12 @@ constexpr bool out_lossy_replay(int out) { return out_base(out) == OUT_STORAGE &
 //    64-bit sum, the two running peaks with their seconds and three more parameters live across the per-second
 //    loop take its spills from 24 to 105 VGPRs (144 B of scratch) and it runs 59.6 ms where the battery kind's
 //    replay runs 46.7 ms; at 2 waves (203 VGPRs, no spill, no scratch) it ran 62.5 ms (Battery dispatch)
+//  scheduled dispatch's map pass (fp64 single-site) walks the intervals' pieces as the replay passes do and reloads
+//    the lane's rule where a piece ends.  At the other map passes' shape (512-chain workgroups, 4 waves = 128 VGPRs) it
+//    spilled 75 VGPRs (224 B of scratch) where battery dispatch's map pass spills 21, and ran 62.3 ms against that
+//    pass's 39.9 ms; in the replay passes' shape, 256-chain workgroups at EXP_WAVES_LOSSY (168 VGPRs, 9 spilled, 32 B),
+//    it runs 39.8 ms (Scheduled dispatch).  Its replay pass runs at that shape as every lossy replay does.
+constexpr bool out_sched_map(int out) { return (out & OUT_SCHED) != 0 && (out & OUT_MAP) != 0; }
 constexpr int FIX_WAVES_SITES = 1;   // min waves per SIMD of the per-site fixup (its fp64 redo recomputes the site's geometry)
 
 struct BlockDesc {                 // as of the step before the block start; -1 = none in the window
@@ -2033,7 +2039,7 @@ constexpr int exp_tile_order()
 template <typename R, int OUT, bool SITES>
 constexpr int exp_wg()
 {
-    return out_lossy_replay(OUT) || out_sweep(OUT) ? 256 : out_no_trace(OUT) && !SITES ? EXP_WG_STATS : 256;
+    return out_lossy_replay(OUT) || out_sweep(OUT) || out_sched_map(OUT) ? 256 : out_no_trace(OUT) && !SITES ? EXP_WG_STATS : 256;
 }
 // the LDS histogram as 16-bit bin pairs when one tile (WG chains x 128 s) cannot fill a
 // 16-bit bin, else one 32-bit word per bin
@@ -2049,6 +2055,7 @@ constexpr int exp_waves()
            : out_dsweep(OUT)                  ? ((OUT & OUT_MAP) ? EXP_WAVES_DSWEEP_MAP : EXP_WAVES_DSWEEP_REPLAY)
            : out_sweep(OUT)                   ? ((OUT & OUT_MAP) ? EXP_WAVES_SWEEP_MAP : EXP_WAVES_SWEEP_REPLAY)
            : out_lossy_replay(OUT)            ? EXP_WAVES_LOSSY
+           : out_sched_map(OUT)               ? EXP_WAVES_LOSSY
            : sizeof(R) == 8                   ? EXP_WAVES_F64
            : out_base(OUT) == OUT_TRACE3      ? EXP_WAVES_TRACE
            : out_base(OUT) == OUT_DEMAND      ? EXP_WAVES_DEMAND
@@ -2218,7 +2225,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                             const PV64* pv_lds, const double* pv_lds_tab,
                                             const float4* nd_lds, const SeriesView& se, SeriesLds* ser_lds,
                                             const IntervalsView& ivv, const StorageView& sto, const long long* batp,
-                                            FleetLds<WGT / 32>* flt_lds, const SweepView& swv)
+                                            FleetLds<WGT / 32>* flt_lds, const SweepView& swv, const ScheduleView& scv)
 {
     constexpr bool SER = out_base(OUT) == OUT_SERIES;
     // Battery storage (fp64 only), two passes over the same per-second body:
@@ -2255,6 +2262,13 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // per variant three more parameters (sw_dsp), and in the replay the curtailed sum (sw_cu) and the four peak
     // registers (sw_im, sw_imj, sw_xm, sw_xmj) beside the sweep's; a variant's parameters are 9 rows, its cells 13 columns
     constexpr bool DSW = SWP && DSP;
+    // SCH: scheduled dispatch on battery dispatch's two passes -- the lane's rule (dsp and the grid-charge power
+    // sc_g) is that of the metering interval, reloaded where the interval ends (schedule_load of the rule the shared
+    // array names, a wave-uniform index), and schedule_ask in place of dispatch_ask.  The replay pass walks the
+    // intervals' pieces already; the map pass (PCS below) walks them too, so that a second's rule is its own
+    // interval's also inside a four-second group that straddles a boundary, and flushes nothing.
+    constexpr bool SCH = (OUT & OUT_SCHED) != 0;
+    static_assert(!SCH || (DSP && !SWP && !SITES), "scheduled dispatch: a flag of battery dispatch's two passes, single site");
     constexpr int KV = DSW ? DSWEEP_KV : SWP ? SWEEP_KV : 1;
     constexpr int KD = DSW ? KV : 1;          // the per-variant dispatch state: one unused set elsewhere
     constexpr int PROWS = DSP ? TMH_DISPATCH_PARAMS : 6;   // a variant's parameter rows
@@ -2267,6 +2281,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     constexpr bool REG = out_base(OUT) == OUT_REGISTERS || DEM;
     constexpr bool IVL = out_base(OUT) == OUT_INTERVALS || REG || REP;
     constexpr int IVC = interval_cols(OUT);
+    constexpr bool PCS = IVL || (SCH && MAP);   // the loops walk the block piece by piece (iv_k, iv_next)
     const uint32_t c = cblk * blockDim.x + threadIdx.x;
     const bool live = c < n;
     const uint32_t j0 = b * BLOCK_STEPS, j1 = min(j0 + (uint32_t)BLOCK_STEPS, nsteps);
@@ -2466,9 +2481,25 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // st_dis) - (iv_pv - iv_m); the peaks are the demand kind's dm_im / dm_ex with their seconds.
     DispatchParams dsp = dispatch_none();
     long long ds_cu = 0;
-    if constexpr (DSP && !SWP) {
+    if constexpr (DSP && !SWP && !SCH) {
         if (live) dsp = dispatch_load(batp, ivv.ld, gid(kp.ids, c));
     }
+    // scheduled dispatch: the rule of interval k into dsp and sc_g.  k is wave-uniform, so the array's entry is one
+    // byte at a uniform address, clamped below the rule count; four lane-consecutive loads per lane follow.  (k is
+    // inside the table for every second of a window check_interval_tables accepted; the min keeps the address
+    // inside the array whatever k.)
+    int sc_g = 0;
+    auto sch_rule = [&](uint32_t k) __attribute__((always_inline)) {
+        if constexpr (SCH) {
+            const uint32_t e = scv.rules[min(k, scv.n_iv - 1u)];
+            const uint32_t rule = __builtin_amdgcn_readfirstlane(min(e, scv.n_rules - 1u));
+            if (live) {
+                const ScheduleRule sr = schedule_load(batp, ivv.ld, gid(kp.ids, c), rule);
+                dsp = sr.dp;
+                sc_g = sr.g;
+            }
+        }
+    };
     if constexpr (REP && !SWP) {
         if (live) sx = sto.work[(size_t)b * 3 * n + c];
         sx0 = sx;
@@ -2521,11 +2552,12 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         }
     };
     uint32_t iv_k = 0, iv_next = j1;
-    if constexpr (IVL) {
+    if constexpr (PCS) {
         iv_k = __builtin_amdgcn_readfirstlane((ivv.rel0 + j0) / ivv.interval_s);
         const uint64_t nb = (uint64_t)(iv_k + 1u) * ivv.interval_s - ivv.rel0;   // the next boundary, as a window step
         iv_next = __builtin_amdgcn_readfirstlane((uint32_t)min(nb, (uint64_t)j1));
     }
+    sch_rule(iv_k);
     auto iv_flush = [&](uint32_t pa, uint32_t pb) __attribute__((always_inline)) {
         if constexpr (SWP && REP) {
             // the sweep: the piece's ten columns into every variant's table -- columns 0-3 the same in each,
@@ -2755,7 +2787,9 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 // meter side b from how far the state of charge really moved
                 // (battery dispatch: its thresholded ask in place of the greedy one, the rest of the second unchanged)
                 int ab;
-                if constexpr (DSP) ab = dispatch_ask(d, dsp.tc, dsp.td, bp.pc, bp.pd);
+                // (scheduled dispatch: the interval's rule, and its grid-charge power on top of the ask)
+                if constexpr (SCH) ab = schedule_ask(d, dsp.tc, dsp.td, sc_g, bp.pc, bp.pd);
+                else if constexpr (DSP) ab = dispatch_ask(d, dsp.tc, dsp.td, bp.pc, bp.pd);
                 else ab = soc_ask(d, bp.pc, bp.pd);
                 const int s = bat_stored(ab, bp);
                 if constexpr (MAP) {
@@ -2773,6 +2807,9 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                         // what is left at the meter, r = d - b: the deficit is the import, the surplus is fed in up
                         // to the limit and curtailed above it.  A night second's literal pv = 0 has d <= 0 and b in
                         // [d, 0] (q(meter) >= 0), so no surplus: it neither exports nor curtails.
+                        // (Scheduled dispatch under a grid-charging rule: b >= 0 >= d there, beyond [d, 0], and r =
+                        // d - b <= 0 all the same: no surplus either; what b exceeds max(d, 0) by is bought from the
+                        // grid and lies in the import, vi < 2^26 + 2^27, which the peak's key holds.)
                         const int r = d - bm, vi = ok ? max(-r, 0) : 0;
                         dm_imj = vi > dm_im ? jb : dm_imj;
                         dm_im = max(vi, dm_im);
@@ -2977,10 +3014,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             return;
         }
         // the piece [pa, je) of the block that one metering interval covers (IVL; else the whole block)
-        uint32_t pa = j0, je = IVL ? iv_next : j1;
+        uint32_t pa = j0, je = PCS ? iv_next : j1;
         do {
             if (((W0 + j0) & 3) == 0) {
-                if constexpr (IVL) {   // a piece that starts inside a four-second group: single seconds up to the grid
+                if constexpr (PCS) {   // a piece that starts inside a four-second group: single seconds up to the grid
                     for (; j < je && (j & 3u); ++j) {
                         flt_mid(j);
                         const uint64_t g = (uint64_t)(W0 + j) >> 2;
@@ -3047,8 +3084,15 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                 iv_flush(pa, je);
                 pa = je;
                 je = ivv.interval_s >= j1 - je ? j1 : je + ivv.interval_s;
+            } else if constexpr (PCS) {   // scheduled dispatch's map pass: the piece ends, nothing to flush
+                ++iv_k;
+                pa = je;
+                je = ivv.interval_s >= j1 - je ? j1 : je + ivv.interval_s;
             }
-        } while (IVL && j < j1);
+            // scheduled dispatch: the next piece lies in interval iv_k, under its rule
+            if constexpr (SCH)
+                if (j < j1) sch_rule(iv_k);
+        } while (PCS && j < j1);
     };
     // (fp32 single-site only: in the fp64 and per-site kernels, which sit at their
     // register bounds, the second copy adds spills)
@@ -3112,9 +3156,10 @@ using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView,
                                                           out_base(OUT) == OUT_DEMAND,
                                                       IntervalsView,
                                                       std::conditional_t<out_base(OUT) == OUT_STORAGE,
+                                                                         std::conditional_t<(OUT & OUT_SCHED) != 0, ScheduleView,
                                                                          std::conditional_t<(OUT & OUT_SWEEP) != 0, SweepView,
                                                                          std::conditional_t<(OUT & OUT_FLEET) != 0, BatteryFleetView,
-                                                                                            std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>>>,
+                                                                                            std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>>>>,
                                                                          TraceView>>>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
@@ -3135,6 +3180,13 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     StorageView sto{};
     const long long* batp = nullptr;
     SweepView swv{};
+    ScheduleView scv{};
+    if constexpr ((OUT & OUT_SCHED) != 0) {   // scheduled dispatch: battery dispatch's view + the rule array
+        scv = ov;
+        sto = ov.bt.st;
+        ivv = ov.bt.st.iv;
+        batp = ov.bt.params;
+    } else
     if constexpr ((OUT & OUT_SWEEP) != 0) {   // the battery sweep: the battery kind's view of the group's first variant + the strides
         swv = ov;
         sto = ov.bt.st;
@@ -3181,7 +3233,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     auto tile = [&](uint32_t b, uint32_t cblk, auto night) __attribute__((always_inline)) {
         expand_tile<R, OUT, SITES, WGT, decltype(night)::value>(
             b, cblk, kp, dp, st, chain0, n, W0, nsteps, utc0, tab64, tab32, sun, events, n_events, desc, sg, tr, sv,
-            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv, sto, batp, flt_lds, swv);
+            lds_hist, cov_lds, min_lds, held_lds, pv_lds, pv_tab, nd_tab, se, ser_lds, ivv, sto, batp, flt_lds, swv, scv);
     };
     // the workgroup's LDS histogram into the device histogram
     auto hist_flush = [&]() __attribute__((always_inline)) {
@@ -3882,7 +3934,7 @@ void with_real(bool f64, F&& f)
 // one kind per engine at a step.  A kind is its column count, the expansion's and the fixup's
 // output, and the words the refusals name it by; a new kind is a row here, its columns in
 // expand_tile and the fixup, and its exported setter.
-enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_DISPATCH_SWEEP, TBL_KINDS };
+enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_DISPATCH_SWEEP, TBL_SCHEDULE, TBL_KINDS };
 struct TableKindInfo {
     int cols, out;      // out: TMH_OUT_* as tmh_engine_last_expand reports it (the expansion's OutKind but for TBL_BATTERY)
     const char* what;   // in the setter's and the checks' messages
@@ -3907,12 +3959,17 @@ constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
     // the dispatch sweep (tmh_dispatch_sweep: n_variants rule sets per chain; tmh_engine::dsweep): battery dispatch's
     // three launches per group of DSWEEP_KV variants on the OUT_SWEEP | OUT_DISPATCH instantiations, TMH_OUT_DISPATCH_SWEEP
     {TMH_DISPATCH_COLS, TMH_OUT_DISPATCH_SWEEP, "dispatch sweep tables", "the dispatch sweep"},
+    // scheduled dispatch (tmh_schedule: up to TMH_SCHEDULE_RULES_MAX rule sets per chain, one per metering interval,
+    // and grid charging; tmh_engine::schedule): battery dispatch's three launches on the OUT_SCHED instantiations
+    // (the scan is the battery kind's own), TMH_OUT_SCHEDULE
+    {TMH_DISPATCH_COLS, TMH_OUT_SCHEDULE, "schedule tables", "the schedule"},
 };
 static_assert(TMH_OUT_BATTERY > out_base(~0) && TMH_OUT_BATTERY < TMH_OUT_SITES, "TMH_OUT_BATTERY: a code of its own below the flags");
 static_assert(TMH_OUT_BATTERY_FLEET > TMH_OUT_BATTERY && TMH_OUT_BATTERY_FLEET < TMH_OUT_SITES, "TMH_OUT_BATTERY_FLEET: likewise");
 static_assert(TMH_OUT_BATTERY_SWEEP > TMH_OUT_BATTERY_FLEET && TMH_OUT_BATTERY_SWEEP < TMH_OUT_SITES, "TMH_OUT_BATTERY_SWEEP: likewise");
 static_assert(TMH_OUT_DISPATCH > TMH_OUT_BATTERY_SWEEP && TMH_OUT_DISPATCH < TMH_OUT_SITES, "TMH_OUT_DISPATCH: likewise");
 static_assert(TMH_OUT_DISPATCH_SWEEP > TMH_OUT_DISPATCH && TMH_OUT_DISPATCH_SWEEP < TMH_OUT_SITES, "TMH_OUT_DISPATCH_SWEEP: likewise");
+static_assert(TMH_OUT_SCHEDULE > TMH_OUT_DISPATCH_SWEEP && TMH_OUT_SCHEDULE < TMH_OUT_SITES, "TMH_OUT_SCHEDULE: likewise");
 static_assert(DSWEEP_KV >= 2 && DSWEEP_KV <= TMH_DISPATCH_SWEEP_MAX, "a group of one variant runs battery dispatch's own kernels");
 static_assert(interval_cols(OUT_INTERVALS) == TABLE_KINDS[TBL_INTERVALS].cols &&
                   interval_cols(OUT_REGISTERS) == TABLE_KINDS[TBL_REGISTERS].cols &&
@@ -3921,7 +3978,8 @@ static_assert(interval_cols(OUT_INTERVALS) == TABLE_KINDS[TBL_INTERVALS].cols &&
                   interval_cols(OUT_STORAGE | OUT_LOSSY) == TABLE_KINDS[TBL_BATTERY].cols &&
                   interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_SWEEP) == TABLE_KINDS[TBL_SWEEP].cols &&
                   interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH) == TABLE_KINDS[TBL_DISPATCH].cols &&
-                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SWEEP) == TABLE_KINDS[TBL_DISPATCH_SWEEP].cols,
+                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SWEEP) == TABLE_KINDS[TBL_DISPATCH_SWEEP].cols &&
+                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SCHED) == TABLE_KINDS[TBL_SCHEDULE].cols,
               "the kernels' cells");
 
 }  // namespace
@@ -3950,6 +4008,7 @@ struct tmh_engine {
     tmh_battery_sweep sweep{};   // tmh_set_battery_sweep: the variants' soc, work buffer and parameters beside tables[TBL_SWEEP]
     tmh_dispatch dispatch{};   // tmh_set_dispatch: soc, the work buffer and the parameters beside tables[TBL_DISPATCH]
     tmh_dispatch_sweep dsweep{};   // tmh_set_dispatch_sweep: the variants' soc, work buffer and parameters beside tables[TBL_DISPATCH_SWEEP]
+    tmh_schedule schedule{};   // tmh_set_schedule: soc, the work buffer, the parameters and the rule array beside tables[TBL_SCHEDULE]
     bool has_fleet = false;  // tmh_set_battery_fleet: the battery kind's replay pass adds its window to `fleet` too
     tmh_series fleet{};
     // the first set kind (TBL_KINDS: none); a step is refused unless it is the only one (check_interval_tables)
@@ -4583,6 +4642,40 @@ int tmh_set_dispatch_sweep(struct tmh_engine* eng, const tmh_dispatch_sweep* sw)
     return TMH_OK;
 }
 
+// scheduled dispatch: tmh_set_dispatch's checks in its own words, the rule count and the rule array
+int tmh_set_schedule(struct tmh_engine* eng, const tmh_schedule* sc)
+{
+    if (!sc) {
+        if (int rc = set_interval_table(eng, TBL_SCHEDULE, nullptr)) return rc;
+        eng->schedule = tmh_schedule{};
+        return TMH_OK;
+    }
+    const char* what = TABLE_KINDS[TBL_SCHEDULE].what;
+    if (!sc->table.sum || sc->table.n_steps == 0 || sc->table.ld == 0 || ((uintptr_t)sc->table.sum & 7) ||
+        sc->table.interval_s == 0)   // (the struct's cases, in the setter's words)
+        return set_interval_table(nullptr, TBL_SCHEDULE, &sc->table);
+    if (sc->table.interval_s > (1u << 23) - 1)
+        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
+                    sc->table.interval_s);
+    if (sc->n_rules == 0 || sc->n_rules > TMH_SCHEDULE_RULES_MAX)
+        return fail(TMH_E_INVAL, "%s: n_rules %u outside [1, %d]", what, sc->n_rules, TMH_SCHEDULE_RULES_MAX);
+    if (!sc->soc || ((uintptr_t)sc->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer", what);
+    if (!sc->work || ((uintptr_t)sc->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
+    if (!sc->params || ((uintptr_t)sc->params & 7))
+        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor [6 + %d * n_rules][ld]", what, TMH_SCHEDULE_RULE_PARAMS);
+    if (!sc->rule_of_interval)
+        return fail(TMH_E_INVAL, "%s need a rule_of_interval array [n_intervals] (the schedule: each interval's rule)", what);
+    if (sc->work_bytes < tmh_storage_work_bytes(1, 1))
+        return fail(TMH_E_INVAL, "%s work buffer too small: %zu < %zu", what, sc->work_bytes, tmh_storage_work_bytes(1, 1));
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (eng->kp.precision != TMH_FP64)   // (as tmh_set_battery)
+        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
+                                 "expansion, and the state of charge depends on every earlier second)", what);
+    if (int rc = set_interval_table(eng, TBL_SCHEDULE, &sc->table)) return rc;
+    eng->schedule = *sc;
+    return TMH_OK;
+}
+
 // the battery fleet series: tmh_set_series' struct cases in its own words (the struct first, as the tables'
 // setters: a bad one is named whatever the engine), and the battery kind's engines only
 int tmh_set_battery_fleet(struct tmh_engine* eng, const tmh_series* fleet)
@@ -4639,6 +4732,18 @@ static int check_interval_tables(const tmh_engine* eng, uint32_t n_chains, int64
                has_demand = eng->tables[TBL_DEMAND].set;
     if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
         return fail(TMH_E_INVAL, "%s are set: no traces in the same call (a caller with traces can sum them)", what);
+    if (eng->tables[TBL_SCHEDULE].set) {   // the schedule runs alone (the last kind: `kind` is another table when there is one)
+        if (kind != TBL_SCHEDULE)
+            return fail(TMH_E_INVAL, "the schedule and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
+        if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
+        if (eng->has_fleet)
+            return fail(TMH_E_INVAL, "the schedule and a battery fleet series are both set: the fleet series is the battery kind's");
+        if (eng->kp.sites)
+            return fail(TMH_E_INVAL, "the schedule cannot run with per-chain sites (tmh_set_sites)");
+        if (eng->schedule.work_bytes < tmh_storage_work_bytes(n_chains, n_steps))
+            return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->schedule.work_bytes,
+                        tmh_storage_work_bytes(n_chains, n_steps));
+    }
     if (eng->tables[TBL_DISPATCH_SWEEP].set) {   // the dispatch sweep runs alone (the last kind: `kind` is another table when there is one)
         if (kind != TBL_DISPATCH_SWEEP)
             return fail(TMH_E_INVAL, "the dispatch sweep and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
@@ -5097,6 +5202,27 @@ static int phase_expand(const StepCtx& c)
                     eng->close(TMH_K_STORAGE_SCAN, t, c.s);
                     t = eng->mark(c.s);
                     launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH>{}, st, btv, sv);
+                    eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
+                }
+            } else if (table == TBL_SCHEDULE) {
+                // scheduled dispatch (fp64, one site: tmh_set_schedule): battery dispatch's three launches with the
+                // OUT_SCHED map and replay passes, which read the rule array of the table's intervals; the scan is
+                // the battery kind's own (params rows 0-5 sit where its rows sit); the same timers
+                if constexpr (!F32 && !S) {
+                    const tmh_schedule& sd = eng->schedule;
+                    const long long* params = reinterpret_cast<const long long*>(sd.params);
+                    const uint64_t n_iv = ((uint64_t)eng->tables[TBL_SCHEDULE].t.n_steps + c.ivv.interval_s - 1) / c.ivv.interval_s;
+                    const ScheduleView scv{BatteryView{StorageView{c.ivv, reinterpret_cast<long long*>(sd.work), 0, 0, 0}, params},
+                                           sd.rule_of_interval, (uint32_t)n_iv, sd.n_rules};
+                    hipEvent_t t = eng->mark(c.s);
+                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SCHED | OUT_MAP>{}, st, scv, StatsView{});
+                    eng->close(TMH_K_STORAGE_MAP, t, c.s);
+                    t = eng->mark(c.s);
+                    hipLaunchKernelGGL(battery_scan_kernel, dim3(c.cb()), dim3(256), 0, c.s, scv.bt.st.work,
+                                       reinterpret_cast<long long*>(sd.soc), params, eng->kp.ids, c.n_chains, c.sg.nblk);
+                    eng->close(TMH_K_STORAGE_SCAN, t, c.s);
+                    t = eng->mark(c.s);
+                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SCHED>{}, st, scv, sv);
                     eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
                 }
             } else if (table == TBL_SWEEP) {

@@ -1584,7 +1584,11 @@ enum OutKind : int {
     // flag on OUT_STORAGE | OUT_LOSSY, both passes: battery dispatch (tmh_dispatch) -- the battery kind with a
     // charge threshold, a discharge threshold and a feed-in limit per chain (params rows 6-8), the curtailed
     // energy and the two peak keys behind the battery (13 columns); TMH_OUT_DISPATCH
-    OUT_DISPATCH = 512
+    OUT_DISPATCH = 512,
+    // flag on OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH, both passes, single site: scheduled dispatch (tmh_schedule) --
+    // the rule (Tc, Td, L and the grid-charge power G) reloaded at every metering-interval boundary from the
+    // rule the shared array names for the interval; the map pass walks the intervals' pieces too; TMH_OUT_SCHEDULE
+    OUT_SCHED = 1024
 };
 constexpr int out_base(int out) { return out & 7; }
 // no trace: the statistics-only expansion's workgroup shape
@@ -1654,6 +1658,15 @@ constexpr int dispatch_ask(int d, int tc, int td, int p_charge, int p_discharge)
 {
     const int up = d - tc > 0 ? d - tc : 0, dn = -d - td > 0 ? -d - td : 0;
     return d >= 0 ? (up < p_charge ? up : p_charge) : -(dn < p_discharge ? dn : p_discharge);
+}
+// Scheduled dispatch (tmh_schedule): the rule in force may also charge from the grid with the power g on top
+// of what dispatch_ask takes from the surplus, within Pc; such a rule never discharges.  g = 0 is dispatch_ask.
+// The ask depends on d, per-chain constants and the time, never on the state of charge; |a| <= max(Pc, Pd).
+constexpr int schedule_ask(int d, int tc, int td, int g, int p_charge, int p_discharge)
+{
+    const int a0 = dispatch_ask(d, tc, td, p_charge, p_discharge);
+    const int up = (a0 > 0 ? a0 : 0) + g;   // <= 2^28
+    return g == 0 ? a0 : up < p_charge ? up : p_charge;
 }
 // The SoC key of table column 8: the second's offset o in its interval (+ 1, so every key is positive)
 // above the state of charge after it (0 <= x < 2^40); the maximum key is the interval's last ok second's.
@@ -1741,11 +1754,36 @@ __device__ __forceinline__ DispatchParams dispatch_load(const long long* __restr
     return p;
 }
 constexpr DispatchParams dispatch_none() { return DispatchParams{0, 0, DISPATCH_NO_LIMIT}; }
+// Scheduled dispatch: one rule of a chain -- rows 6 + 4 rule .. 9 + 4 rule of params[6 + 4 R][ld], four
+// lane-consecutive 8-byte loads, each clamped into [0, 2^27].  `rule` is below R (the caller clamps it).  Loaded
+// by the OUT_SCHED instantiations only, at a tile's start and at every interval boundary inside it.
+struct ScheduleRule {
+    DispatchParams dp;   // Tc, Td, L
+    int g;               // G: the grid-charge power, 0 = none
+};
+__device__ __forceinline__ ScheduleRule schedule_load(const long long* __restrict__ params, uint64_t ld, uint32_t i, uint32_t rule)
+{
+    const long long* p = params + (size_t)(6u + TMH_SCHEDULE_RULE_PARAMS * rule) * ld + i;
+    ScheduleRule r;
+    r.dp.tc = bat_clamp_int(p[0], 0, DISPATCH_NO_LIMIT);
+    r.dp.td = bat_clamp_int(p[ld], 0, DISPATCH_NO_LIMIT);
+    r.dp.lim = bat_clamp_int(p[2 * ld], 0, DISPATCH_NO_LIMIT);
+    r.g = bat_clamp_int(p[3 * ld], 0, BAT_POWER_MAX);
+    return r;
+}
 // The battery kind's view: the storage kind's (cap, p_charge, p_discharge unused) and the parameters ([6][ld];
 // battery dispatch: [9][ld], the battery's rows first).
 struct BatteryView {
     StorageView st;
     const long long* params;
+};
+// Scheduled dispatch's view (OUT_SCHED): battery dispatch's, the rule array of the table's n_iv intervals (entry
+// k: interval k's rule, on the table's grid and origin, as IntervalsView's k) and the rule count R.  The kernels
+// read entry min(k, n_iv - 1) and use min(entry, R - 1).
+struct ScheduleView {
+    BatteryView bt;
+    const uint8_t* rules;
+    uint32_t n_iv, n_rules;
 };
 // The battery fleet series beside the battery kind's table (OUT_FLEET): the kind's view and the window's rows of
 // the fleet table through the series' view -- rows of TMH_BATTERY_FLEET_COLS int64 per step, `sum` at the window's

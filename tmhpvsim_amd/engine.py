@@ -94,6 +94,18 @@ _TABLES = {
         run_excludes=(("_intervals", "_registers", "_demand", "_storage", "_battery"),
                       "battery dispatch and another interval table are both enabled: one of them per sim"),
         no_trace="a dispatch run takes no traces (trace=()): run the battery over the traces instead (dispatch.from_traces)"),
+    # scheduled dispatch (enable_schedule: battery dispatch with a rule per metering interval and grid charging; fp64
+    # sims, one site)
+    "schedule": dict(
+        noun="schedule tables", name="the schedule",
+        enable_excludes=tuple(
+            (attr, f"{what} is enabled: one table output per sim (the schedule runs alone)")
+            for attr, what in (("_series", "a fleet series"), ("_intervals", "interval metering"),
+                               ("_registers", "the import / export registers"), ("_demand", "the demand registers"),
+                               ("_battery_fleet", "a battery fleet series"))),
+        run_excludes=(("_intervals", "_registers", "_demand", "_storage", "_battery", "_dispatch"),
+                      "the schedule and another interval table are both enabled: one of them per sim"),
+        no_trace="a schedule run takes no traces (trace=()): run the battery over the traces instead (schedule.from_traces)"),
 }
 for _kind, _t in _TABLES.items():   # no table beside battery storage, whichever was enabled first
     if _kind != "storage":
@@ -111,6 +123,10 @@ for _kind, _t in _TABLES.items():   # no table beside battery storage, whichever
     # (enable_dispatch_sweep: the dispatch sweep, likewise)
     _t["enable_excludes"] += (("_dispatch_sweep", "the dispatch sweep is enabled: one table output per sim "
                                                   "(the dispatch sweep runs alone)"),)
+    # (enable_schedule: the last kind, so that everything refused before it is refused in the same words)
+    if _kind != "schedule":
+        _t["enable_excludes"] += (("_schedule", "the schedule is enabled: one table output per sim "
+                                                "(the schedule runs alone)"),)
 
 
 class BatchedSim:
@@ -216,6 +232,9 @@ class BatchedSim:
         self._battery_desc = None
         self.dispatch_params = None   # int64 [9, n]: the batteries' and the dispatch rule's parameters (enable_dispatch)
         self._dispatch_desc = None
+        self.schedule_params = None   # int64 [6 + 4 R, n]: the batteries' parameters and the R rules' (enable_schedule)
+        self.schedule_rules = None    # uint8 [n_intervals]: the rule of each of the table's intervals
+        self._schedule_desc = None
         self.battery_fleet_raw = None   # int64 [n_groups, n_steps, 8]: the battery fleet series (enable_battery_fleet)
         self._battery_fleet = None
         self.battery_sweep_raw = None   # int64 [K, n_intervals, 10, n]: the battery sweep's tables (enable_battery_sweep)
@@ -312,7 +331,7 @@ class BatchedSim:
     def _enable_table(self, kind, n_steps, interval_s, step0, buffer):
         """enable_intervals, enable_registers and enable_demand (_TABLES[kind])."""
         torch = _torch()
-        if kind in ("storage", "battery", "dispatch"):   # (its descriptor holds the table's: _set_storage, _set_battery, _set_dispatch)
+        if kind in ("storage", "battery", "dispatch", "schedule"):   # (its descriptor holds the table's: _set_storage, _set_battery, _set_dispatch, _set_schedule)
             setter = lambda eng, st: getattr(self, "_set_" + kind)(st._obj if st is not None else None)
         else:
             setter = getattr(self.L, "tmh_set_" + kind)
@@ -428,7 +447,7 @@ class BatchedSim:
         other table; compaction is allowed.  n_steps=None switches the output off."""
         torch = _torch()
         if n_steps is None:
-            if self._battery is None and self._dispatch is None:   # (soc and the work buffer may be enable_battery's or enable_dispatch's)
+            if self._battery is None and self._dispatch is None and self._schedule is None:   # (soc and the work buffer may be another kind's)
                 self.soc = self._storage_work = self._storage_desc = None
             return self._enable_table("storage", None, interval_s, step0, buffer)
         if self.precision != _lib.TMH_FP64:
@@ -483,6 +502,8 @@ class BatchedSim:
                 _lib.check(self._set_battery(self._battery))
             elif self._dispatch is not None:
                 _lib.check(self._set_dispatch(self._dispatch))
+            elif self._schedule is not None:
+                _lib.check(self._set_schedule(self._schedule))
             else:
                 _lib.check(self._set_storage(self._storage))
 
@@ -647,6 +668,107 @@ class BatchedSim:
         """The dispatch table in watts and watt-hours (dispatch.to_watts of dispatch_raw): the battery kind's keys
         plus energy_wh_curtailed, curtailed_share and the peaks behind the battery, [n_intervals, n] each."""
         return self._table_watts("dispatch")
+
+    # ------------------------------------------------------------------ scheduled dispatch
+    def enable_schedule(self, n_steps, interval_s=900, *, capacity_wh=None, charge_w=None, discharge_w=None, charge_eff=1.0,
+                        discharge_eff=1.0, standby_w=0.0, rules=None, params=None, rule_of_interval=None, n_rules=None,
+                        soc0_wh=0.0, soc=None, buffer=None, step0=None):
+        """enable_dispatch with a rule that changes at known times (tmhpvsim_amd.schedule): each chain has one
+        battery and R <= schedule.RULES_MAX rule sets -- `rules`, a list of dicts with charge_above_w,
+        discharge_above_w, feed_in_limit_w (None: no limit) and grid_charge_w (the power the battery also takes from
+        the grid; a grid-charging rule never discharges), each a scalar or [n] -- and rule_of_interval, a uint8
+        sequence, array or device tensor [n_intervals] shared by all chains, names the rule in force in each
+        metering interval of the table (schedule.daily builds one from a daily local-time tariff).  Returns the raw
+        int64 tensor [n_intervals, 13, n], battery dispatch's columns.  `sim.soc` is the int64 state of charge [n],
+        `sim.schedule_params` the int64 parameters [6 + 4 R, n] and `sim.schedule_rules` the uint8 array on the
+        device.  params: a ready int64 device tensor [6 + 4 R, n] instead of the quantities and `rules` -- it may be a
+        column slice of a wider one whose row stride is the table's ld; its values must lie in their ranges
+        (schedule.check_params; the kernels clamp).  n_rules, when given, is checked against R; entries of
+        rule_of_interval at or above R are refused (schedule.check_rules).  soc0_wh, soc, buffer, step0, fp64 only, no
+        traces, no fleet series, no battery fleet series, no other table, compaction: as enable_dispatch; per-chain
+        sites are refused.  A refused call leaves what was enabled before as it was.  n_steps=None switches the
+        output off."""
+        torch = _torch()
+        if n_steps is None:
+            if self._schedule is not None:   # (soc and the work buffer may be another kind's)
+                self.soc = self._storage_work = self._schedule_desc = self.schedule_params = self.schedule_rules = None
+            return self._enable_table("schedule", None, interval_s, step0, buffer)
+        if self.precision != _lib.TMH_FP64:
+            raise ValueError("the schedule needs precision='fp64': an fp32 engine replaces its guard-band seconds "
+                             "after the expansion, and the state of charge depends on every earlier second")
+        if self.sites is not None:
+            raise ValueError("the schedule cannot run with per-chain sites")
+        from . import schedule
+        if int(n_steps) < 1 or int(interval_s) < 1 or int(interval_s) > schedule.MAX_INTERVAL_S:
+            raise ValueError(f"enable_schedule: n_steps >= 1 and 1 <= interval_s <= {schedule.MAX_INTERVAL_S}")
+        if params is None:
+            if capacity_wh is None or charge_w is None or discharge_w is None or rules is None:
+                raise ValueError("enable_schedule: capacity_wh, charge_w, discharge_w and rules (or params) are required")
+            host = schedule.quantize_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
+                                            rules=rules, n=self.n)
+            params = torch.from_numpy(host).to(self.device)
+        else:
+            if (params.dtype != torch.int64 or params.device != self.device or params.dim() != 2
+                    or params.shape[1] != self.n or (self.n > 1 and params.stride(1) != 1)):
+                raise ValueError(f"schedule params must be an int64 [6 + 4 R, {self.n}] tensor on {self.device}, chains contiguous")
+            host = schedule.check_params(params)
+        R = schedule.n_rules_of(host)
+        if n_rules is not None and int(n_rules) != R:
+            raise ValueError(f"enable_schedule: n_rules {int(n_rules)} but the schedule params hold {R} rules")
+        if rule_of_interval is None:
+            raise ValueError("enable_schedule: the schedule needs rule_of_interval (the rule of each metering interval)")
+        nk = schedule.n_intervals(int(n_steps), int(interval_s))
+        if torch.is_tensor(rule_of_interval):
+            if rule_of_interval.dtype != torch.uint8 or rule_of_interval.dim() != 1:
+                raise ValueError("schedule rule_of_interval must be a uint8 [n_intervals] array")
+            schedule.check_rules(rule_of_interval, R, nk)
+            roi = rule_of_interval.to(self.device).contiguous()
+        else:
+            a = np.asarray(rule_of_interval)
+            if a.dtype != np.uint8:
+                if a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) > 255)):
+                    raise ValueError("schedule rule_of_interval must hold integers in [0, 255]")
+                a = a.astype(np.uint8)
+            roi = torch.from_numpy(np.ascontiguousarray(schedule.check_rules(a, R, nk))).to(self.device)
+        if soc is None:
+            soc = torch.from_numpy(schedule.quantize_soc(soc0_wh, host[:6])).to(self.device)
+        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (self.n,)
+              or (self.n > 1 and soc.stride(0) != 1)):
+            raise ValueError(f"schedule soc must be a contiguous int64 [{self.n}] tensor on {self.device}")
+        kept = self._storage_args
+        self._storage_args = (soc, params, roi, R)
+        try:
+            raw = self._enable_table("schedule", n_steps, interval_s, step0, buffer)
+        except Exception:   # (refused: what was enabled before stays as it was)
+            self._storage_args = kept
+            raise
+        self.soc, self.schedule_params, self.schedule_rules = soc, params, roi
+        return raw
+
+    def _set_schedule(self, table):
+        """tmh_set_schedule with the table descriptor `table` (or None); the work buffer as _set_storage's.
+        The parameters' row stride must be the table's ld (one ld for both: tmh_schedule)."""
+        if table is None:
+            return self.L.tmh_set_schedule(self._eng, None)
+        torch = _torch()
+        soc, params, roi, R = self._storage_args
+        if int(params.stride(0)) != int(table.ld):
+            raise ValueError(f"schedule params row stride {int(params.stride(0))} != the table's ld {int(table.ld)}: "
+                             "slice both from tensors of the same width")
+        if self._storage_work is None:
+            nb = self.L.tmh_storage_work_bytes(self.n, min(int(table.n_steps), 86400))
+            self._storage_work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
+        work = self._storage_work
+        sc = _lib.Schedule(table, soc.data_ptr(), work.data_ptr(), work.numel(), params.data_ptr(), roi.data_ptr(), R)
+        rc = self.L.tmh_set_schedule(self._eng, C.byref(sc))
+        if rc == 0:
+            self._schedule_desc = sc
+        return rc
+
+    def schedule(self):
+        """The schedule table in watts and watt-hours (schedule.to_watts of schedule_raw): battery dispatch's keys,
+        [n_intervals, n] each."""
+        return self._table_watts("schedule")
 
     # ------------------------------------------------------------------ the battery sweep
     def enable_battery_sweep(self, n_steps, interval_s=900, *, n_variants=None, capacity_wh=None, charge_w=None,
@@ -996,7 +1118,7 @@ class BatchedSim:
         res = out if out is not None else self._alloc(n_steps, trace)
         st = self._stats_struct()
         win = max(1, min(int(window), n_steps))
-        if self._storage is not None or self._battery is not None or self._dispatch is not None:
+        if self._storage is not None or self._battery is not None or self._dispatch is not None or self._schedule is not None:
             self._storage_window(win)
         if self._battery_sweep is not None:
             self._sweep_window(win)
