@@ -3332,7 +3332,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
 // waits for another: the only dependent chain is the lane's own add and two clamps per block.  The
 // loads are lane-consecutive and do not depend on the state, so SCAN_G blocks' maps are loaded ahead
 // of the chain that consumes them.  (soc: per chain index, ids[slot] in a compacted window.)
-// BAT (battery_scan_kernel, the battery kind): the state of charge read from soc is clamped into the chain's
+// BAT (battery_scan_kernel, every kind but storage): the state of charge read from soc is clamped into the chain's
 // [0, C] first (params row 0, clamped as battery_load clamps it), so a caller's soc above C cannot leave a
 // block start outside the range the replay pass assumes.
 constexpr uint32_t SCAN_G = 8;
@@ -3373,31 +3373,15 @@ __global__ __launch_bounds__(256) void storage_scan_kernel(long long* __restrict
 {
     storage_scan<false>(work, soc, nullptr, ids, n, nblk);
 }
+// the kinds with parameters: the walk per (chain, variant), the variant the grid's y (one for the single kinds), a
+// variant's work buffer wstride, soc row ld and `rows` parameter rows apart (row 0 of a variant's rows is its capacity)
 __global__ __launch_bounds__(256) void battery_scan_kernel(long long* __restrict__ work, long long* __restrict__ soc,
                                                            const long long* __restrict__ params,
-                                                           const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk)
-{
-    storage_scan<true>(work, soc, params, ids, n, nblk);
-}
-
-// the battery sweep: battery_scan_kernel's walk per (chain, variant), the variant the grid's y
-__global__ __launch_bounds__(256) void battery_sweep_scan_kernel(long long* __restrict__ work, long long* __restrict__ soc,
-                                                                 const long long* __restrict__ params,
-                                                                 const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk,
-                                                                 uint64_t wstride, uint64_t ld)
+                                                           const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk,
+                                                           uint64_t wstride, uint64_t ld, uint32_t rows)
 {
     const size_t v = blockIdx.y;
-    storage_scan<true>(work + v * wstride, soc + v * ld, params + v * 6 * ld, ids, n, nblk);
-}
-// the dispatch sweep: the same walk, a variant's nine parameter rows apart (row 0 of a variant's params sits where the
-// battery kind's sits); a kernel of its own, so that the battery sweep's stays as it is
-__global__ __launch_bounds__(256) void dispatch_sweep_scan_kernel(long long* __restrict__ work, long long* __restrict__ soc,
-                                                                  const long long* __restrict__ params,
-                                                                  const uint32_t* __restrict__ ids, uint32_t n, uint32_t nblk,
-                                                                  uint64_t wstride, uint64_t ld)
-{
-    const size_t v = blockIdx.y;
-    storage_scan<true>(work + v * wstride, soc + v * ld, params + v * TMH_DISPATCH_PARAMS * ld, ids, n, nblk);
+    storage_scan<true>(work + v * wstride, soc + v * ld, params + v * rows * ld, ids, n, nblk);
 }
 
 // ------------------------------------------------------------ compaction
@@ -3923,6 +3907,8 @@ void with_value(int v, F&& f)
 {
     (void)(... || (v == Vs && (f(std::integral_constant<int, Vs>{}), true)));
 }
+template <int V>
+constexpr std::integral_constant<int, V> out_c{};
 template <typename F>
 void with_real(bool f64, F&& f)
 {
@@ -3934,36 +3920,54 @@ void with_real(bool f64, F&& f)
 // one kind per engine at a step.  A kind is its column count, the expansion's and the fixup's
 // output, and the words the refusals name it by; a new kind is a row here, its columns in
 // expand_tile and the fixup, and its exported setter.
+// The battery family (replay != 0: fp64 engines only, no fixup) keeps a state of charge per chain and runs alone.
+// Its rows also say what its one setter (set_battery_table), its one refusal (check_interval_tables) and its one
+// launch sequence (phase_expand) differ in from kind to kind; a new kind of the family is a row, its public struct
+// and the few lines of its exported setter that copy the struct into a BatteryDesc.
 enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_DISPATCH_SWEEP, TBL_SCHEDULE, TBL_KINDS };
 struct TableKindInfo {
-    int cols, out;      // out: TMH_OUT_* as tmh_engine_last_expand reports it (the expansion's OutKind but for TBL_BATTERY)
+    int cols, out;      // out: TMH_OUT_* as tmh_engine_last_expand reports it (the expansion's OutKind but for the battery family)
     const char* what;   // in the setter's and the checks' messages
     const char* name;   // as the other table of a both-set refusal
+    int replay = 0;     // the replay pass's OUT_* flags (the map pass: the same | OUT_MAP)
+    int rows = 0, rule_rows = 0;   // parameter rows per variant: rows + rule_rows * n_rules (0: storage's three integers instead)
+    int kv = 1;         // variants per launch
+    int count_max = 0;  // the most variants (n_variants) or rules (n_rules); 0: the kind has neither
+    const char* count = nullptr;   // the count's name in the setter's refusal
+    bool floor = false;      // the setter refuses a work buffer smaller than one block's
+    bool one_site = false;   // per-chain sites are refused
+    // how the refusal beside a battery fleet series ends; nullptr: none here (the battery kind fills the series,
+    // and storage is refused in check_battery_fleet's words)
+    const char* no_fleet = nullptr;
+    const char* soc_shape = "";      // after "soc buffer" in the setter's refusal
+    const char* params_shape = "";   // the params tensor's shape in the setter's refusal
 };
+constexpr int OUT_BAT = OUT_STORAGE | OUT_LOSSY, OUT_DSP = OUT_BAT | OUT_DISPATCH;
 constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
     {4, OUT_INTERVALS, "intervals", "interval metering"},
     {TMH_REGISTERS_COLS, OUT_REGISTERS, "registers", "the import / export registers"},
     {TMH_DEMAND_COLS, OUT_DEMAND, "demand registers", "the demand registers"},
-    // battery storage (tmh_storage: the descriptor's other fields sit beside the slot, tmh_engine::storage);
-    // fp64 engines only, three launches (phase_expand), no fixup
-    {TMH_STORAGE_COLS, OUT_STORAGE, "storage tables", "battery storage"},
-    // the battery kind (tmh_battery: losses and per-chain parameters; tmh_engine::battery): storage's three
-    // launches on the OUT_STORAGE | OUT_LOSSY instantiations, reported as TMH_OUT_BATTERY
-    {TMH_BATTERY_COLS, TMH_OUT_BATTERY, "battery tables", "the battery kind"},
-    // the battery sweep (tmh_battery_sweep: n_variants batteries per chain; tmh_engine::sweep): the battery kind's
-    // three launches per group of SWEEP_KV variants on the OUT_SWEEP instantiations, TMH_OUT_BATTERY_SWEEP
-    {TMH_BATTERY_COLS, TMH_OUT_BATTERY_SWEEP, "battery sweep tables", "the battery sweep"},
-    // battery dispatch (tmh_dispatch: thresholds and a feed-in limit per chain; tmh_engine::dispatch): the battery
-    // kind's three launches on the OUT_DISPATCH instantiations, TMH_OUT_DISPATCH
-    {TMH_DISPATCH_COLS, TMH_OUT_DISPATCH, "battery dispatch tables", "battery dispatch"},
-    // the dispatch sweep (tmh_dispatch_sweep: n_variants rule sets per chain; tmh_engine::dsweep): battery dispatch's
-    // three launches per group of DSWEEP_KV variants on the OUT_SWEEP | OUT_DISPATCH instantiations, TMH_OUT_DISPATCH_SWEEP
-    {TMH_DISPATCH_COLS, TMH_OUT_DISPATCH_SWEEP, "dispatch sweep tables", "the dispatch sweep"},
-    // scheduled dispatch (tmh_schedule: up to TMH_SCHEDULE_RULES_MAX rule sets per chain, one per metering interval,
-    // and grid charging; tmh_engine::schedule): battery dispatch's three launches on the OUT_SCHED instantiations
-    // (the scan is the battery kind's own), TMH_OUT_SCHEDULE
-    {TMH_DISPATCH_COLS, TMH_OUT_SCHEDULE, "schedule tables", "the schedule"},
+    // battery storage (tmh_storage): lossless, one battery for the batch
+    {TMH_STORAGE_COLS, OUT_STORAGE, "storage tables", "battery storage", OUT_STORAGE},
+    // the battery kind (tmh_battery): losses and per-chain parameters; the battery fleet series runs beside it
+    {TMH_BATTERY_COLS, TMH_OUT_BATTERY, "battery tables", "the battery kind", OUT_BAT, 6, 0, 1, 0, nullptr, false, false,
+     nullptr, "", "[6][ld]"},
+    // the battery sweep (tmh_battery_sweep): n_variants batteries per chain, SWEEP_KV of them per launch
+    {TMH_BATTERY_COLS, TMH_OUT_BATTERY_SWEEP, "battery sweep tables", "the battery sweep", OUT_BAT | OUT_SWEEP, 6, 0, SWEEP_KV,
+     TMH_BATTERY_SWEEP_MAX, "n_variants", true, true, " (one battery per chain)", " [n_variants][ld]", "[n_variants][6][ld]"},
+    // battery dispatch (tmh_dispatch): thresholds and a feed-in limit per chain
+    {TMH_DISPATCH_COLS, TMH_OUT_DISPATCH, "battery dispatch tables", "battery dispatch", OUT_DSP, TMH_DISPATCH_PARAMS, 0, 1, 0,
+     nullptr, false, false, "", "", "[9][ld]"},
+    // the dispatch sweep (tmh_dispatch_sweep): n_variants rule sets per chain, DSWEEP_KV of them per launch
+    {TMH_DISPATCH_COLS, TMH_OUT_DISPATCH_SWEEP, "dispatch sweep tables", "the dispatch sweep", OUT_DSP | OUT_SWEEP,
+     TMH_DISPATCH_PARAMS, 0, DSWEEP_KV, TMH_DISPATCH_SWEEP_MAX, "n_variants", true, true, " (one battery per chain)",
+     " [n_variants][ld]", "[n_variants][9][ld]"},
+    // scheduled dispatch (tmh_schedule): up to TMH_SCHEDULE_RULES_MAX rule sets per chain, one per metering interval,
+    // and grid charging
+    {TMH_DISPATCH_COLS, TMH_OUT_SCHEDULE, "schedule tables", "the schedule", OUT_DSP | OUT_SCHED, 6, TMH_SCHEDULE_RULE_PARAMS, 1,
+     TMH_SCHEDULE_RULES_MAX, "n_rules", true, true, "", "", "[6 + 4 * n_rules][ld]"},
 };
+static_assert(TMH_DISPATCH_PARAMS == 9 && TMH_SCHEDULE_RULE_PARAMS == 4, "the params shapes in TABLE_KINDS' words");
 static_assert(TMH_OUT_BATTERY > out_base(~0) && TMH_OUT_BATTERY < TMH_OUT_SITES, "TMH_OUT_BATTERY: a code of its own below the flags");
 static_assert(TMH_OUT_BATTERY_FLEET > TMH_OUT_BATTERY && TMH_OUT_BATTERY_FLEET < TMH_OUT_SITES, "TMH_OUT_BATTERY_FLEET: likewise");
 static_assert(TMH_OUT_BATTERY_SWEEP > TMH_OUT_BATTERY_FLEET && TMH_OUT_BATTERY_SWEEP < TMH_OUT_SITES, "TMH_OUT_BATTERY_SWEEP: likewise");
@@ -3971,16 +3975,32 @@ static_assert(TMH_OUT_DISPATCH > TMH_OUT_BATTERY_SWEEP && TMH_OUT_DISPATCH < TMH
 static_assert(TMH_OUT_DISPATCH_SWEEP > TMH_OUT_DISPATCH && TMH_OUT_DISPATCH_SWEEP < TMH_OUT_SITES, "TMH_OUT_DISPATCH_SWEEP: likewise");
 static_assert(TMH_OUT_SCHEDULE > TMH_OUT_DISPATCH_SWEEP && TMH_OUT_SCHEDULE < TMH_OUT_SITES, "TMH_OUT_SCHEDULE: likewise");
 static_assert(DSWEEP_KV >= 2 && DSWEEP_KV <= TMH_DISPATCH_SWEEP_MAX, "a group of one variant runs battery dispatch's own kernels");
-static_assert(interval_cols(OUT_INTERVALS) == TABLE_KINDS[TBL_INTERVALS].cols &&
-                  interval_cols(OUT_REGISTERS) == TABLE_KINDS[TBL_REGISTERS].cols &&
-                  interval_cols(OUT_DEMAND) == TABLE_KINDS[TBL_DEMAND].cols &&
-                  interval_cols(OUT_STORAGE) == TABLE_KINDS[TBL_STORAGE].cols &&
-                  interval_cols(OUT_STORAGE | OUT_LOSSY) == TABLE_KINDS[TBL_BATTERY].cols &&
-                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_SWEEP) == TABLE_KINDS[TBL_SWEEP].cols &&
-                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH) == TABLE_KINDS[TBL_DISPATCH].cols &&
-                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SWEEP) == TABLE_KINDS[TBL_DISPATCH_SWEEP].cols &&
-                  interval_cols(OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SCHED) == TABLE_KINDS[TBL_SCHEDULE].cols,
-              "the kernels' cells");
+constexpr bool table_cols_ok()
+{
+    for (int k = 0; k < TBL_KINDS; ++k)
+        if (interval_cols(TABLE_KINDS[k].replay ? TABLE_KINDS[k].replay : TABLE_KINDS[k].out) != TABLE_KINDS[k].cols) return false;
+    return true;
+}
+static_assert(table_cols_ok(), "the kernels' cells");
+
+// What a battery-family kind keeps beside its table (the public structs' fields after `table`; the fields a kind does
+// not have stay 0, n_variants 1)
+struct BatteryDesc {
+    long long* soc = nullptr;    // [n_variants][ld]
+    long long* work = nullptr;
+    size_t work_bytes = 0;
+    const long long* params = nullptr;   // [n_variants][rows + rule_rows * n_rules][ld]
+    uint32_t n_variants = 1;
+    const uint8_t* rule_of_interval = nullptr;
+    uint32_t n_rules = 0;
+    int64_t capacity = 0, p_charge = 0, p_discharge = 0;   // storage's battery
+    BatteryDesc() = default;
+    BatteryDesc(int64_t* soc, void* work, size_t work_bytes, const int64_t* params = nullptr)
+        : soc(reinterpret_cast<long long*>(soc)), work(static_cast<long long*>(work)), work_bytes(work_bytes),
+          params(reinterpret_cast<const long long*>(params))
+    {
+    }
+};
 
 }  // namespace
 
@@ -4000,15 +4020,10 @@ struct tmh_engine {
     bool has_series = false;  // tmh_set_series: every expansion adds its window to `series`
     tmh_series series{};
     struct {
-        bool set = false;   // tmh_set_intervals / _registers / _demand: every expansion adds its window to `t`
+        bool set = false;   // the kind's setter: every expansion adds its window to `t`
         tmh_intervals t{};
+        BatteryDesc b{};    // the battery family's kinds: soc, the work buffer and the parameters (set_battery_table)
     } tables[TBL_KINDS];
-    tmh_storage storage{};   // tmh_set_storage: the battery, soc and the work buffer beside tables[TBL_STORAGE]
-    tmh_battery battery{};   // tmh_set_battery: soc, the work buffer and the parameters beside tables[TBL_BATTERY]
-    tmh_battery_sweep sweep{};   // tmh_set_battery_sweep: the variants' soc, work buffer and parameters beside tables[TBL_SWEEP]
-    tmh_dispatch dispatch{};   // tmh_set_dispatch: soc, the work buffer and the parameters beside tables[TBL_DISPATCH]
-    tmh_dispatch_sweep dsweep{};   // tmh_set_dispatch_sweep: the variants' soc, work buffer and parameters beside tables[TBL_DISPATCH_SWEEP]
-    tmh_schedule schedule{};   // tmh_set_schedule: soc, the work buffer, the parameters and the rule array beside tables[TBL_SCHEDULE]
     bool has_fleet = false;  // tmh_set_battery_fleet: the battery kind's replay pass adds its window to `fleet` too
     tmh_series fleet{};
     // the first set kind (TBL_KINDS: none); a step is refused unless it is the only one (check_interval_tables)
@@ -4482,198 +4497,93 @@ size_t tmh_storage_work_bytes(uint32_t n_chains, uint32_t n_steps)
 {
     return (size_t)nblk_of(n_steps) * 3 * n_chains * sizeof(long long);
 }
-// battery storage: the table through the kinds' one setter, the battery's own fields checked here
-int tmh_set_storage(struct tmh_engine* eng, const tmh_storage* st)
+size_t tmh_battery_sweep_work_bytes(uint32_t n_chains, uint32_t n_steps, uint32_t n_variants)
 {
-    if (!st) {
-        if (int rc = set_interval_table(eng, TBL_STORAGE, nullptr)) return rc;
-        eng->storage = tmh_storage{};
+    return (size_t)n_variants * tmh_storage_work_bytes(n_chains, n_steps);
+}
+// The battery family's setters (tmh_set_storage ... tmh_set_schedule): one sequence, TABLE_KINDS[kind] naming what
+// a kind has.  table NULL switches the kind off.  The parameters' values are the kernels' to clamp: the host never
+// reads the tensor.
+static int set_battery_table(tmh_engine* eng, TableKind kind, const tmh_intervals* table, const BatteryDesc& d)
+{
+    if (!table) {
+        if (int rc = set_interval_table(eng, kind, nullptr)) return rc;
+        eng->tables[kind].b = BatteryDesc{};
         return TMH_OK;
     }
-    const char* what = TABLE_KINDS[TBL_STORAGE].what;
-    if (!st->table.sum || st->table.n_steps == 0 || st->table.ld == 0 || ((uintptr_t)st->table.sum & 7) ||
-        st->table.interval_s == 0)   // (the struct's cases, in the setter's words)
-        return set_interval_table(nullptr, TBL_STORAGE, &st->table);
-    if (st->table.interval_s > (1u << 23) - 1)
+    const TableKindInfo& ki = TABLE_KINDS[kind];
+    const char* what = ki.what;
+    if (!table->sum || table->n_steps == 0 || table->ld == 0 || ((uintptr_t)table->sum & 7) || table->interval_s == 0)
+        return set_interval_table(nullptr, kind, table);   // (the struct's cases, in the setter's words)
+    if (table->interval_s > (1u << 23) - 1)
         return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
-                    st->table.interval_s);
-    if (!st->soc || ((uintptr_t)st->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer", what);
-    if (!st->work || ((uintptr_t)st->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
-    if (st->capacity < 0 || st->capacity >= (1ll << 40))
-        return fail(TMH_E_INVAL, "%s: capacity %lld outside [0, 2^40)", what, (long long)st->capacity);
-    if (st->p_charge < 0 || st->p_charge > (1ll << 27) || st->p_discharge < 0 || st->p_discharge > (1ll << 27))
-        return fail(TMH_E_INVAL, "%s: p_charge %lld, p_discharge %lld outside [0, 2^27]", what, (long long)st->p_charge,
-                    (long long)st->p_discharge);
+                    table->interval_s);
+    const uint32_t count = ki.rule_rows ? d.n_rules : d.n_variants;
+    if (ki.count_max && (count == 0 || count > (uint32_t)ki.count_max))
+        return fail(TMH_E_INVAL, "%s: %s %u outside [1, %d]", what, ki.count, count, ki.count_max);
+    if (!d.soc || ((uintptr_t)d.soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer%s", what, ki.soc_shape);
+    if (!d.work || ((uintptr_t)d.work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
+    if (ki.rows == 0) {   // storage's battery
+        if (d.capacity < 0 || d.capacity >= (1ll << 40))
+            return fail(TMH_E_INVAL, "%s: capacity %lld outside [0, 2^40)", what, (long long)d.capacity);
+        if (d.p_charge < 0 || d.p_charge > (1ll << 27) || d.p_discharge < 0 || d.p_discharge > (1ll << 27))
+            return fail(TMH_E_INVAL, "%s: p_charge %lld, p_discharge %lld outside [0, 2^27]", what, (long long)d.p_charge,
+                        (long long)d.p_discharge);
+    } else if (!d.params || ((uintptr_t)d.params & 7)) {
+        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor %s", what, ki.params_shape);
+    }
+    if (ki.rule_rows && !d.rule_of_interval)
+        return fail(TMH_E_INVAL, "%s need a rule_of_interval array [n_intervals] (the schedule: each interval's rule)", what);
+    if (ki.floor && d.work_bytes < tmh_battery_sweep_work_bytes(1, 1, d.n_variants))
+        return fail(TMH_E_INVAL, "%s work buffer too small: %zu < %zu", what, d.work_bytes,
+                    tmh_battery_sweep_work_bytes(1, 1, d.n_variants));
     if (!eng) return fail(TMH_E_INVAL, "NULL engine");
     // an fp32 engine replaces its guard-band seconds after the expansion (fixup_kernel): a correction that
     // is additive for a sum, but a changed second changes the state of charge of every later one
     if (eng->kp.precision != TMH_FP64)
         return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
                                  "expansion, and the state of charge depends on every earlier second)", what);
-    if (int rc = set_interval_table(eng, TBL_STORAGE, &st->table)) return rc;
-    eng->storage = *st;
+    if (int rc = set_interval_table(eng, kind, table)) return rc;
+    eng->tables[kind].b = d;
     return TMH_OK;
 }
-
-// the battery kind: tmh_set_storage's checks in its own words, the parameters in place of the three integers
-// (their values are the kernels' to clamp: the host never reads the tensor)
+int tmh_set_storage(struct tmh_engine* eng, const tmh_storage* st)
+{
+    if (!st) return set_battery_table(eng, TBL_STORAGE, nullptr, {});
+    BatteryDesc d(st->soc, st->work, st->work_bytes);
+    d.capacity = st->capacity, d.p_charge = st->p_charge, d.p_discharge = st->p_discharge;
+    return set_battery_table(eng, TBL_STORAGE, &st->table, d);
+}
 int tmh_set_battery(struct tmh_engine* eng, const tmh_battery* bt)
 {
-    if (!bt) {
-        if (int rc = set_interval_table(eng, TBL_BATTERY, nullptr)) return rc;
-        eng->battery = tmh_battery{};
-        return TMH_OK;
-    }
-    const char* what = TABLE_KINDS[TBL_BATTERY].what;
-    if (!bt->table.sum || bt->table.n_steps == 0 || bt->table.ld == 0 || ((uintptr_t)bt->table.sum & 7) ||
-        bt->table.interval_s == 0)   // (the struct's cases, in the setter's words)
-        return set_interval_table(nullptr, TBL_BATTERY, &bt->table);
-    if (bt->table.interval_s > (1u << 23) - 1)
-        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
-                    bt->table.interval_s);
-    if (!bt->soc || ((uintptr_t)bt->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer", what);
-    if (!bt->work || ((uintptr_t)bt->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
-    if (!bt->params || ((uintptr_t)bt->params & 7))
-        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor [6][ld]", what);
-    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
-    if (eng->kp.precision != TMH_FP64)   // (as tmh_set_storage)
-        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
-                                 "expansion, and the state of charge depends on every earlier second)", what);
-    if (int rc = set_interval_table(eng, TBL_BATTERY, &bt->table)) return rc;
-    eng->battery = *bt;
-    return TMH_OK;
-}
-
-// the battery sweep: tmh_set_battery's checks in its own words, and the variant count
-size_t tmh_battery_sweep_work_bytes(uint32_t n_chains, uint32_t n_steps, uint32_t n_variants)
-{
-    return (size_t)n_variants * tmh_storage_work_bytes(n_chains, n_steps);
+    if (!bt) return set_battery_table(eng, TBL_BATTERY, nullptr, {});
+    return set_battery_table(eng, TBL_BATTERY, &bt->table, BatteryDesc(bt->soc, bt->work, bt->work_bytes, bt->params));
 }
 int tmh_set_battery_sweep(struct tmh_engine* eng, const tmh_battery_sweep* sw)
 {
-    if (!sw) {
-        if (int rc = set_interval_table(eng, TBL_SWEEP, nullptr)) return rc;
-        eng->sweep = tmh_battery_sweep{};
-        return TMH_OK;
-    }
-    const char* what = TABLE_KINDS[TBL_SWEEP].what;
-    if (!sw->table.sum || sw->table.n_steps == 0 || sw->table.ld == 0 || ((uintptr_t)sw->table.sum & 7) ||
-        sw->table.interval_s == 0)   // (the struct's cases, in the setter's words)
-        return set_interval_table(nullptr, TBL_SWEEP, &sw->table);
-    if (sw->table.interval_s > (1u << 23) - 1)
-        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
-                    sw->table.interval_s);
-    if (sw->n_variants == 0 || sw->n_variants > TMH_BATTERY_SWEEP_MAX)
-        return fail(TMH_E_INVAL, "%s: n_variants %u outside [1, %d]", what, sw->n_variants, TMH_BATTERY_SWEEP_MAX);
-    if (!sw->soc || ((uintptr_t)sw->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer [n_variants][ld]", what);
-    if (!sw->work || ((uintptr_t)sw->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
-    if (!sw->params || ((uintptr_t)sw->params & 7))
-        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor [n_variants][6][ld]", what);
-    if (sw->work_bytes < tmh_battery_sweep_work_bytes(1, 1, sw->n_variants))
-        return fail(TMH_E_INVAL, "%s work buffer too small: %zu < %zu", what, sw->work_bytes,
-                    tmh_battery_sweep_work_bytes(1, 1, sw->n_variants));
-    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
-    if (eng->kp.precision != TMH_FP64)   // (as tmh_set_battery)
-        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
-                                 "expansion, and the state of charge depends on every earlier second)", what);
-    if (int rc = set_interval_table(eng, TBL_SWEEP, &sw->table)) return rc;
-    eng->sweep = *sw;
-    return TMH_OK;
+    if (!sw) return set_battery_table(eng, TBL_SWEEP, nullptr, {});
+    BatteryDesc d(sw->soc, sw->work, sw->work_bytes, sw->params);
+    d.n_variants = sw->n_variants;
+    return set_battery_table(eng, TBL_SWEEP, &sw->table, d);
 }
-
-// battery dispatch: tmh_set_battery's checks in its own words, nine parameter rows
 int tmh_set_dispatch(struct tmh_engine* eng, const tmh_dispatch* dp)
 {
-    if (!dp) {
-        if (int rc = set_interval_table(eng, TBL_DISPATCH, nullptr)) return rc;
-        eng->dispatch = tmh_dispatch{};
-        return TMH_OK;
-    }
-    const char* what = TABLE_KINDS[TBL_DISPATCH].what;
-    if (!dp->table.sum || dp->table.n_steps == 0 || dp->table.ld == 0 || ((uintptr_t)dp->table.sum & 7) ||
-        dp->table.interval_s == 0)   // (the struct's cases, in the setter's words)
-        return set_interval_table(nullptr, TBL_DISPATCH, &dp->table);
-    if (dp->table.interval_s > (1u << 23) - 1)
-        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
-                    dp->table.interval_s);
-    if (!dp->soc || ((uintptr_t)dp->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer", what);
-    if (!dp->work || ((uintptr_t)dp->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
-    if (!dp->params || ((uintptr_t)dp->params & 7))
-        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor [%d][ld]", what, TMH_DISPATCH_PARAMS);
-    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
-    if (eng->kp.precision != TMH_FP64)   // (as tmh_set_battery)
-        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
-                                 "expansion, and the state of charge depends on every earlier second)", what);
-    if (int rc = set_interval_table(eng, TBL_DISPATCH, &dp->table)) return rc;
-    eng->dispatch = *dp;
-    return TMH_OK;
+    if (!dp) return set_battery_table(eng, TBL_DISPATCH, nullptr, {});
+    return set_battery_table(eng, TBL_DISPATCH, &dp->table, BatteryDesc(dp->soc, dp->work, dp->work_bytes, dp->params));
 }
-
-// the dispatch sweep: tmh_set_battery_sweep's checks in its own words, nine parameter rows per variant
 int tmh_set_dispatch_sweep(struct tmh_engine* eng, const tmh_dispatch_sweep* sw)
 {
-    if (!sw) {
-        if (int rc = set_interval_table(eng, TBL_DISPATCH_SWEEP, nullptr)) return rc;
-        eng->dsweep = tmh_dispatch_sweep{};
-        return TMH_OK;
-    }
-    const char* what = TABLE_KINDS[TBL_DISPATCH_SWEEP].what;
-    if (!sw->table.sum || sw->table.n_steps == 0 || sw->table.ld == 0 || ((uintptr_t)sw->table.sum & 7) ||
-        sw->table.interval_s == 0)   // (the struct's cases, in the setter's words)
-        return set_interval_table(nullptr, TBL_DISPATCH_SWEEP, &sw->table);
-    if (sw->table.interval_s > (1u << 23) - 1)
-        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
-                    sw->table.interval_s);
-    if (sw->n_variants == 0 || sw->n_variants > TMH_DISPATCH_SWEEP_MAX)
-        return fail(TMH_E_INVAL, "%s: n_variants %u outside [1, %d]", what, sw->n_variants, TMH_DISPATCH_SWEEP_MAX);
-    if (!sw->soc || ((uintptr_t)sw->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer [n_variants][ld]", what);
-    if (!sw->work || ((uintptr_t)sw->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
-    if (!sw->params || ((uintptr_t)sw->params & 7))
-        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor [n_variants][%d][ld]", what, TMH_DISPATCH_PARAMS);
-    if (sw->work_bytes < tmh_battery_sweep_work_bytes(1, 1, sw->n_variants))
-        return fail(TMH_E_INVAL, "%s work buffer too small: %zu < %zu", what, sw->work_bytes,
-                    tmh_battery_sweep_work_bytes(1, 1, sw->n_variants));
-    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
-    if (eng->kp.precision != TMH_FP64)   // (as tmh_set_battery)
-        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
-                                 "expansion, and the state of charge depends on every earlier second)", what);
-    if (int rc = set_interval_table(eng, TBL_DISPATCH_SWEEP, &sw->table)) return rc;
-    eng->dsweep = *sw;
-    return TMH_OK;
+    if (!sw) return set_battery_table(eng, TBL_DISPATCH_SWEEP, nullptr, {});
+    BatteryDesc d(sw->soc, sw->work, sw->work_bytes, sw->params);
+    d.n_variants = sw->n_variants;
+    return set_battery_table(eng, TBL_DISPATCH_SWEEP, &sw->table, d);
 }
-
-// scheduled dispatch: tmh_set_dispatch's checks in its own words, the rule count and the rule array
 int tmh_set_schedule(struct tmh_engine* eng, const tmh_schedule* sc)
 {
-    if (!sc) {
-        if (int rc = set_interval_table(eng, TBL_SCHEDULE, nullptr)) return rc;
-        eng->schedule = tmh_schedule{};
-        return TMH_OK;
-    }
-    const char* what = TABLE_KINDS[TBL_SCHEDULE].what;
-    if (!sc->table.sum || sc->table.n_steps == 0 || sc->table.ld == 0 || ((uintptr_t)sc->table.sum & 7) ||
-        sc->table.interval_s == 0)   // (the struct's cases, in the setter's words)
-        return set_interval_table(nullptr, TBL_SCHEDULE, &sc->table);
-    if (sc->table.interval_s > (1u << 23) - 1)
-        return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
-                    sc->table.interval_s);
-    if (sc->n_rules == 0 || sc->n_rules > TMH_SCHEDULE_RULES_MAX)
-        return fail(TMH_E_INVAL, "%s: n_rules %u outside [1, %d]", what, sc->n_rules, TMH_SCHEDULE_RULES_MAX);
-    if (!sc->soc || ((uintptr_t)sc->soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer", what);
-    if (!sc->work || ((uintptr_t)sc->work & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned work buffer", what);
-    if (!sc->params || ((uintptr_t)sc->params & 7))
-        return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor [6 + %d * n_rules][ld]", what, TMH_SCHEDULE_RULE_PARAMS);
-    if (!sc->rule_of_interval)
-        return fail(TMH_E_INVAL, "%s need a rule_of_interval array [n_intervals] (the schedule: each interval's rule)", what);
-    if (sc->work_bytes < tmh_storage_work_bytes(1, 1))
-        return fail(TMH_E_INVAL, "%s work buffer too small: %zu < %zu", what, sc->work_bytes, tmh_storage_work_bytes(1, 1));
-    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
-    if (eng->kp.precision != TMH_FP64)   // (as tmh_set_battery)
-        return fail(TMH_E_INVAL, "%s need an fp64 engine (an fp32 engine fixes its guard-band seconds after the "
-                                 "expansion, and the state of charge depends on every earlier second)", what);
-    if (int rc = set_interval_table(eng, TBL_SCHEDULE, &sc->table)) return rc;
-    eng->schedule = *sc;
-    return TMH_OK;
+    if (!sc) return set_battery_table(eng, TBL_SCHEDULE, nullptr, {});
+    BatteryDesc d(sc->soc, sc->work, sc->work_bytes, sc->params);
+    d.rule_of_interval = sc->rule_of_interval, d.n_rules = sc->n_rules;
+    return set_battery_table(eng, TBL_SCHEDULE, &sc->table, d);
 }
 
 // the battery fleet series: tmh_set_series' struct cases in its own words (the struct first, as the tables'
@@ -4689,7 +4599,7 @@ int tmh_set_battery_fleet(struct tmh_engine* eng, const tmh_series* fleet)
                         fleet->group_chains, fleet->n_groups);
     }
     if (!eng) return fail(TMH_E_INVAL, "NULL engine");
-    if (fleet && eng->kp.precision != TMH_FP64)   // (as tmh_set_battery)
+    if (fleet && eng->kp.precision != TMH_FP64)
         return fail(TMH_E_INVAL, "a battery fleet series needs an fp64 engine, as the battery kind whose replay pass fills it");
     eng->has_fleet = fleet != nullptr;
     eng->fleet = fleet ? *fleet : tmh_series{};
@@ -4732,65 +4642,28 @@ static int check_interval_tables(const tmh_engine* eng, uint32_t n_chains, int64
                has_demand = eng->tables[TBL_DEMAND].set;
     if (trace && (trace->csi || trace->pv || trace->meter || trace->residual || trace->covered))
         return fail(TMH_E_INVAL, "%s are set: no traces in the same call (a caller with traces can sum them)", what);
-    if (eng->tables[TBL_SCHEDULE].set) {   // the schedule runs alone (the last kind: `kind` is another table when there is one)
-        if (kind != TBL_SCHEDULE)
-            return fail(TMH_E_INVAL, "the schedule and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
+    // A kind of the battery family runs alone (`kind` is the first set one, so another table when there is one).  The
+    // last three kinds name the other table before a fleet series, the first three after it.
+    auto runs_alone = [&](int k) -> int {
+        const TableKindInfo& ki = TABLE_KINDS[k];
+        if (!eng->tables[k].set) return TMH_OK;
+        if (kind != k) return fail(TMH_E_INVAL, "%s and %s are both set: one table kind per engine", ki.name, TABLE_KINDS[kind].name);
         if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
-        if (eng->has_fleet)
-            return fail(TMH_E_INVAL, "the schedule and a battery fleet series are both set: the fleet series is the battery kind's");
-        if (eng->kp.sites)
-            return fail(TMH_E_INVAL, "the schedule cannot run with per-chain sites (tmh_set_sites)");
-        if (eng->schedule.work_bytes < tmh_storage_work_bytes(n_chains, n_steps))
-            return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->schedule.work_bytes,
-                        tmh_storage_work_bytes(n_chains, n_steps));
-    }
-    if (eng->tables[TBL_DISPATCH_SWEEP].set) {   // the dispatch sweep runs alone (the last kind: `kind` is another table when there is one)
-        if (kind != TBL_DISPATCH_SWEEP)
-            return fail(TMH_E_INVAL, "the dispatch sweep and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
-        if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
-        if (eng->has_fleet)
-            return fail(TMH_E_INVAL, "the dispatch sweep and a battery fleet series are both set: the fleet series is the battery "
-                                     "kind's (one battery per chain)");
-        if (eng->kp.sites)
-            return fail(TMH_E_INVAL, "the dispatch sweep cannot run with per-chain sites (tmh_set_sites)");
-        if (eng->dsweep.work_bytes < tmh_battery_sweep_work_bytes(n_chains, n_steps, eng->dsweep.n_variants))
-            return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->dsweep.work_bytes,
-                        tmh_battery_sweep_work_bytes(n_chains, n_steps, eng->dsweep.n_variants));
-    }
-    if (eng->tables[TBL_DISPATCH].set) {   // battery dispatch runs alone (kind: the first set one, so another table when there is one)
-        const char* dsp = TABLE_KINDS[TBL_DISPATCH].name;
-        if (kind != TBL_DISPATCH)
-            return fail(TMH_E_INVAL, "%s and %s are both set: one table kind per engine", dsp, TABLE_KINDS[kind].name);
-        if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
-        if (eng->has_fleet)
-            return fail(TMH_E_INVAL, "%s and a battery fleet series are both set: the fleet series is the battery kind's", dsp);
-        if (eng->dispatch.work_bytes < tmh_storage_work_bytes(n_chains, n_steps))
-            return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->dispatch.work_bytes,
-                        tmh_storage_work_bytes(n_chains, n_steps));
-    }
+        if (eng->has_fleet && ki.no_fleet)
+            return fail(TMH_E_INVAL, "%s and a battery fleet series are both set: the fleet series is the battery kind's%s", ki.name,
+                        ki.no_fleet);
+        if (eng->kp.sites && ki.one_site) return fail(TMH_E_INVAL, "%s cannot run with per-chain sites (tmh_set_sites)", ki.name);
+        const BatteryDesc& d = eng->tables[k].b;
+        const size_t need = tmh_battery_sweep_work_bytes(n_chains, n_steps, d.n_variants);
+        if (d.work_bytes < need)
+            return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, d.work_bytes, need);
+        return TMH_OK;
+    };
+    for (int k = TBL_SCHEDULE; k >= TBL_DISPATCH; --k)
+        if (int rc = runs_alone(k)) return rc;
     if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
-    if (eng->tables[TBL_SWEEP].set) {   // the battery sweep runs alone (kind: the first set one, so another table when there is one)
-        if (kind != TBL_SWEEP)
-            return fail(TMH_E_INVAL, "the battery sweep and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
-        if (eng->has_fleet)
-            return fail(TMH_E_INVAL, "the battery sweep and a battery fleet series are both set: the fleet series is the battery "
-                                     "kind's (one battery per chain)");
-        if (eng->kp.sites)
-            return fail(TMH_E_INVAL, "the battery sweep cannot run with per-chain sites (tmh_set_sites)");
-        if (eng->sweep.work_bytes < tmh_battery_sweep_work_bytes(n_chains, n_steps, eng->sweep.n_variants))
-            return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->sweep.work_bytes,
-                        tmh_battery_sweep_work_bytes(n_chains, n_steps, eng->sweep.n_variants));
-    }
-    if (eng->tables[TBL_BATTERY].set && kind != TBL_BATTERY)   // (kind: the first set one, so another table, storage included)
-        return fail(TMH_E_INVAL, "the battery kind and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
-    if (kind == TBL_BATTERY && eng->battery.work_bytes < tmh_storage_work_bytes(n_chains, n_steps))
-        return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->battery.work_bytes,
-                    tmh_storage_work_bytes(n_chains, n_steps));
-    if (eng->tables[TBL_STORAGE].set && kind != TBL_STORAGE)   // (kind: the first set one, so another table)
-        return fail(TMH_E_INVAL, "battery storage and %s are both set: one table kind per engine", TABLE_KINDS[kind].name);
-    if (kind == TBL_STORAGE && eng->storage.work_bytes < tmh_storage_work_bytes(n_chains, n_steps))
-        return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, eng->storage.work_bytes,
-                    tmh_storage_work_bytes(n_chains, n_steps));
+    for (int k = TBL_SWEEP; k >= TBL_STORAGE; --k)
+        if (int rc = runs_alone(k)) return rc;
     if (has_intervals && has_registers)
         return fail(TMH_E_INVAL, "registers and intervals are both set: one of the two per engine (the registers table holds "
                                  "the intervals' columns)");
@@ -5141,163 +5014,78 @@ static int phase_expand(const StepCtx& c)
             constexpr bool F32 = sizeof(r) == 4, S = decltype(st)::value;
             auto traces = [&](auto okind) { launch(r, okind, st, tv, sv); };
             auto ivl = [&](auto okind) { launch(r, okind, st, c.ivv, sv); };
-            if (table == TBL_STORAGE) {
-                // battery storage (fp64: tmh_set_storage), three launches in stream order, none waiting on
-                // another workgroup: the map pass (each (chain, block)'s composed SoC map, no statistics), the
-                // scan (each block's starting SoC, the window's end into soc), the replay pass (the table, with
-                // the statistics when given).  Each timed on its own beside TMH_K_EXPAND.
-                if constexpr (!F32) {
-                    const tmh_storage& sb = eng->storage;
-                    const StorageView stv{c.ivv, reinterpret_cast<long long*>(sb.work), (long long)sb.capacity,
-                                          (int)sb.p_charge, (int)sb.p_discharge};
-                    hipEvent_t t = eng->mark(c.s);
-                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_MAP>{}, st, stv, StatsView{});
-                    eng->close(TMH_K_STORAGE_MAP, t, c.s);
-                    t = eng->mark(c.s);
-                    hipLaunchKernelGGL(storage_scan_kernel, dim3(c.cb()), dim3(256), 0, c.s, stv.work,
-                                       reinterpret_cast<long long*>(sb.soc), eng->kp.ids, c.n_chains, c.sg.nblk);
-                    eng->close(TMH_K_STORAGE_SCAN, t, c.s);
-                    t = eng->mark(c.s);
-                    launch(r, std::integral_constant<int, OUT_STORAGE>{}, st, stv, sv);
-                    eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
-                }
-            } else if (table == TBL_BATTERY) {
-                // the battery kind (fp64: tmh_set_battery): storage's three launches and work buffer, the
-                // parameters from memory, the scan clamping the state of charge it reads; the same timers
-                if constexpr (!F32) {
-                    const tmh_battery& bb = eng->battery;
-                    const long long* params = reinterpret_cast<const long long*>(bb.params);
-                    const BatteryView btv{StorageView{c.ivv, reinterpret_cast<long long*>(bb.work), 0, 0, 0}, params};
-                    hipEvent_t t = eng->mark(c.s);
-                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_MAP>{}, st, btv, StatsView{});
-                    eng->close(TMH_K_STORAGE_MAP, t, c.s);
-                    t = eng->mark(c.s);
-                    hipLaunchKernelGGL(battery_scan_kernel, dim3(c.cb()), dim3(256), 0, c.s, btv.st.work,
-                                       reinterpret_cast<long long*>(bb.soc), params, eng->kp.ids, c.n_chains, c.sg.nblk);
-                    eng->close(TMH_K_STORAGE_SCAN, t, c.s);
-                    t = eng->mark(c.s);
-                    if (eng->has_fleet) {   // the battery fleet series beside the table: the replay pass's OUT_FLEET instantiation
-                        launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_FLEET>{}, st,
-                               BatteryFleetView{btv, c.sev}, sv);
+            // The battery family (fp64: set_battery_table), three launches in stream order, none waiting on another
+            // workgroup: the map pass (each (chain, block)'s composed SoC map, no statistics), the scan (each block's
+            // starting SoC, the window's end into soc), the replay pass (the table, with the statistics `rsv`).  Each
+            // timed on its own beside TMH_K_EXPAND.  okind: the replay pass's flags; view: both passes'; nv variants.
+            auto passes = [&](auto okind, const auto& view, const BatteryView& bt, long long* soc, uint32_t nv, uint64_t wstride,
+                              uint32_t rows, const StatsView& rsv) {
+                constexpr int O = decltype(okind)::value;
+                hipEvent_t t = eng->mark(c.s);
+                launch(r, out_c<O | OUT_MAP>, st, view, StatsView{});
+                eng->close(TMH_K_STORAGE_MAP, t, c.s);
+                t = eng->mark(c.s);
+                if constexpr (O == OUT_STORAGE)
+                    hipLaunchKernelGGL(storage_scan_kernel, dim3(c.cb()), dim3(256), 0, c.s, bt.st.work, soc, eng->kp.ids, c.n_chains,
+                                       c.sg.nblk);
+                else
+                    hipLaunchKernelGGL(battery_scan_kernel, dim3(c.cb(), nv), dim3(256), 0, c.s, bt.st.work, soc, bt.params,
+                                       eng->kp.ids, c.n_chains, c.sg.nblk, wstride, c.ivv.ld, rows);
+                eng->close(TMH_K_STORAGE_SCAN, t, c.s);
+                t = eng->mark(c.s);
+                if constexpr (O == OUT_BAT) {   // the battery fleet series beside the table: the replay pass's OUT_FLEET instantiation
+                    if (eng->has_fleet) {
+                        launch(r, out_c<O | OUT_FLEET>, st, BatteryFleetView{view, c.sev}, rsv);
                         out = TMH_OUT_BATTERY_FLEET;
                     } else {
-                        launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY>{}, st, btv, sv);
+                        launch(r, okind, st, view, rsv);
                     }
-                    eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
+                } else {
+                    launch(r, okind, st, view, rsv);
                 }
-            } else if (table == TBL_DISPATCH) {
-                // battery dispatch (fp64: tmh_set_dispatch): the battery kind's three launches with the OUT_DISPATCH
-                // map and replay passes; the scan is the battery kind's own (params rows 0-5 sit where its rows
-                // sit); the same timers
-                if constexpr (!F32) {
-                    const tmh_dispatch& dd = eng->dispatch;
-                    const long long* params = reinterpret_cast<const long long*>(dd.params);
-                    const BatteryView btv{StorageView{c.ivv, reinterpret_cast<long long*>(dd.work), 0, 0, 0}, params};
-                    hipEvent_t t = eng->mark(c.s);
-                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_MAP>{}, st, btv, StatsView{});
-                    eng->close(TMH_K_STORAGE_MAP, t, c.s);
-                    t = eng->mark(c.s);
-                    hipLaunchKernelGGL(battery_scan_kernel, dim3(c.cb()), dim3(256), 0, c.s, btv.st.work,
-                                       reinterpret_cast<long long*>(dd.soc), params, eng->kp.ids, c.n_chains, c.sg.nblk);
-                    eng->close(TMH_K_STORAGE_SCAN, t, c.s);
-                    t = eng->mark(c.s);
-                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH>{}, st, btv, sv);
-                    eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
-                }
-            } else if (table == TBL_SCHEDULE) {
-                // scheduled dispatch (fp64, one site: tmh_set_schedule): battery dispatch's three launches with the
-                // OUT_SCHED map and replay passes, which read the rule array of the table's intervals; the scan is
-                // the battery kind's own (params rows 0-5 sit where its rows sit); the same timers
-                if constexpr (!F32 && !S) {
-                    const tmh_schedule& sd = eng->schedule;
-                    const long long* params = reinterpret_cast<const long long*>(sd.params);
-                    const uint64_t n_iv = ((uint64_t)eng->tables[TBL_SCHEDULE].t.n_steps + c.ivv.interval_s - 1) / c.ivv.interval_s;
-                    const ScheduleView scv{BatteryView{StorageView{c.ivv, reinterpret_cast<long long*>(sd.work), 0, 0, 0}, params},
-                                           sd.rule_of_interval, (uint32_t)n_iv, sd.n_rules};
-                    hipEvent_t t = eng->mark(c.s);
-                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SCHED | OUT_MAP>{}, st, scv, StatsView{});
-                    eng->close(TMH_K_STORAGE_MAP, t, c.s);
-                    t = eng->mark(c.s);
-                    hipLaunchKernelGGL(battery_scan_kernel, dim3(c.cb()), dim3(256), 0, c.s, scv.bt.st.work,
-                                       reinterpret_cast<long long*>(sd.soc), params, eng->kp.ids, c.n_chains, c.sg.nblk);
-                    eng->close(TMH_K_STORAGE_SCAN, t, c.s);
-                    t = eng->mark(c.s);
-                    launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SCHED>{}, st, scv, sv);
-                    eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
-                }
-            } else if (table == TBL_SWEEP) {
-                // the battery sweep (fp64, one site: tmh_set_battery_sweep): the battery kind's three launches per
-                // group of up to SWEEP_KV variants, group after group in stream order, each variant with its own
-                // table, work buffer, soc row and parameters; the statistics go to the first group's replay
-                // launch alone (the per-second body is the same in every group: they would count twice)
-                if constexpr (!F32 && !S) {
-                    const tmh_battery_sweep& sw = eng->sweep;
-                    const uint64_t ld = c.ivv.ld;
-                    const uint64_t n_iv = ((uint64_t)eng->tables[TBL_SWEEP].t.n_steps + c.ivv.interval_s - 1) / c.ivv.interval_s;
-                    const uint64_t tstride = n_iv * TMH_BATTERY_COLS * ld;
-                    const uint64_t wstride = tmh_storage_work_bytes(c.n_chains, c.n_steps) / sizeof(long long);
-                    for (uint32_t v0 = 0; v0 < sw.n_variants; v0 += SWEEP_KV) {
-                        const uint32_t nv = std::min<uint32_t>(SWEEP_KV, sw.n_variants - v0);
-                        IntervalsView iv = c.ivv;
-                        iv.sum += (size_t)v0 * tstride;
-                        long long* const work = reinterpret_cast<long long*>(sw.work) + (size_t)v0 * wstride;
-                        long long* const soc = reinterpret_cast<long long*>(sw.soc) + (size_t)v0 * ld;
-                        const long long* const params = reinterpret_cast<const long long*>(sw.params) + (size_t)v0 * 6 * ld;
-                        const BatteryView btv{StorageView{iv, work, 0, 0, 0}, params};
-                        const SweepView swv{btv, tstride, wstride, nv, 0u};
-                        const StatsView& gsv = v0 == 0 ? sv : StatsView{};
-                        // a group of one variant is the battery kind itself: its own instantiations, at their
-                        // occupancy, instead of SWEEP_KV - 1 idle sets of registers at the sweep's
-                        hipEvent_t t = eng->mark(c.s);
-                        if (nv == 1) launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_MAP>{}, st, btv, StatsView{});
-                        else launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_MAP | OUT_SWEEP>{}, st, swv, StatsView{});
-                        eng->close(TMH_K_STORAGE_MAP, t, c.s);
-                        t = eng->mark(c.s);
-                        hipLaunchKernelGGL(battery_sweep_scan_kernel, dim3(c.cb(), nv), dim3(256), 0, c.s, work, soc, params,
-                                           eng->kp.ids, c.n_chains, c.sg.nblk, wstride, ld);
-                        eng->close(TMH_K_STORAGE_SCAN, t, c.s);
-                        t = eng->mark(c.s);
-                        if (nv == 1) launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY>{}, st, btv, gsv);
-                        else launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_SWEEP>{}, st, swv, gsv);
-                        eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
+                eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
+            };
+            if (table != TBL_KINDS && TABLE_KINDS[table].replay) {
+                with_value<TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_DISPATCH_SWEEP, TBL_SCHEDULE>(table, [&](auto k) {
+                    constexpr int K = decltype(k)::value;
+                    constexpr TableKindInfo ki = TABLE_KINDS[K];
+                    constexpr int O = ki.replay;
+                    if constexpr (!F32 && !(S && ki.one_site)) {
+                        // Groups of up to ki.kv variants (the single kinds: one group of one), group after group in stream
+                        // order, each variant with its own table, work buffer, soc row and parameter rows.  The statistics go
+                        // to the first group's replay launch alone (the per-second body is the same in every group: they
+                        // would count twice).
+                        const BatteryDesc& d = eng->tables[K].b;
+                        const uint64_t ld = c.ivv.ld;
+                        const uint32_t rows = ki.rows + ki.rule_rows * d.n_rules;
+                        const uint64_t n_iv = ((uint64_t)eng->tables[K].t.n_steps + c.ivv.interval_s - 1) / c.ivv.interval_s;
+                        const uint64_t tstride = n_iv * ki.cols * ld;
+                        const uint64_t wstride = tmh_storage_work_bytes(c.n_chains, c.n_steps) / sizeof(long long);
+                        for (uint32_t v0 = 0; v0 < d.n_variants; v0 += ki.kv) {
+                            const uint32_t nv = std::min<uint32_t>(ki.kv, d.n_variants - v0);
+                            IntervalsView iv = c.ivv;
+                            iv.sum += (size_t)v0 * tstride;
+                            long long* const soc = d.soc + (size_t)v0 * ld;
+                            const StorageView stv{iv, d.work + (size_t)v0 * wstride, (long long)d.capacity, (int)d.p_charge,
+                                                  (int)d.p_discharge};
+                            const BatteryView btv{stv, d.params + (size_t)v0 * rows * ld};
+                            const StatsView gsv = v0 == 0 ? sv : StatsView{};
+                            if constexpr (O == OUT_STORAGE) {
+                                passes(out_c<O>, stv, btv, soc, nv, wstride, rows, gsv);
+                            } else if constexpr ((O & OUT_SCHED) != 0) {
+                                passes(out_c<O>, ScheduleView{btv, d.rule_of_interval, (uint32_t)n_iv, d.n_rules}, btv, soc, nv, wstride,
+                                       rows, gsv);
+                            } else if constexpr ((O & OUT_SWEEP) != 0) {
+                                // a group of one variant is the single kind itself: its own instantiations, at their
+                                // occupancy, instead of kv - 1 idle sets of registers at the sweep's
+                                if (nv == 1) passes(out_c<O & ~OUT_SWEEP>, btv, btv, soc, nv, wstride, rows, gsv);
+                                else passes(out_c<O>, SweepView{btv, tstride, wstride, nv, 0u}, btv, soc, nv, wstride, rows, gsv);
+                            } else {
+                                passes(out_c<O>, btv, btv, soc, nv, wstride, rows, gsv);
+                            }
+                        }
                     }
-                }
-            } else if (table == TBL_DISPATCH_SWEEP) {
-                // the dispatch sweep (fp64, one site: tmh_set_dispatch_sweep): the battery sweep's groups with battery
-                // dispatch's second -- three launches per group of up to DSWEEP_KV variants, group after group in
-                // stream order, each variant with its own table (13 columns), work buffer, soc row and nine
-                // parameter rows; the statistics go to the first group's replay launch alone
-                if constexpr (!F32 && !S) {
-                    const tmh_dispatch_sweep& sw = eng->dsweep;
-                    const uint64_t ld = c.ivv.ld;
-                    const uint64_t n_iv = ((uint64_t)eng->tables[TBL_DISPATCH_SWEEP].t.n_steps + c.ivv.interval_s - 1) / c.ivv.interval_s;
-                    const uint64_t tstride = n_iv * TMH_DISPATCH_COLS * ld;
-                    const uint64_t wstride = tmh_storage_work_bytes(c.n_chains, c.n_steps) / sizeof(long long);
-                    for (uint32_t v0 = 0; v0 < sw.n_variants; v0 += DSWEEP_KV) {
-                        const uint32_t nv = std::min<uint32_t>(DSWEEP_KV, sw.n_variants - v0);
-                        IntervalsView iv = c.ivv;
-                        iv.sum += (size_t)v0 * tstride;
-                        long long* const work = reinterpret_cast<long long*>(sw.work) + (size_t)v0 * wstride;
-                        long long* const soc = reinterpret_cast<long long*>(sw.soc) + (size_t)v0 * ld;
-                        const long long* const params = reinterpret_cast<const long long*>(sw.params) + (size_t)v0 * TMH_DISPATCH_PARAMS * ld;
-                        const BatteryView btv{StorageView{iv, work, 0, 0, 0}, params};
-                        const SweepView swv{btv, tstride, wstride, nv, 0u};
-                        const StatsView& gsv = v0 == 0 ? sv : StatsView{};
-                        // a group of one variant is battery dispatch itself: its own instantiations, at their occupancy
-                        hipEvent_t t = eng->mark(c.s);
-                        if (nv == 1) launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_MAP>{}, st, btv, StatsView{});
-                        else launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_MAP | OUT_SWEEP>{}, st, swv, StatsView{});
-                        eng->close(TMH_K_STORAGE_MAP, t, c.s);
-                        t = eng->mark(c.s);
-                        hipLaunchKernelGGL(dispatch_sweep_scan_kernel, dim3(c.cb(), nv), dim3(256), 0, c.s, work, soc, params,
-                                           eng->kp.ids, c.n_chains, c.sg.nblk, wstride, ld);
-                        eng->close(TMH_K_STORAGE_SCAN, t, c.s);
-                        t = eng->mark(c.s);
-                        if (nv == 1) launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH>{}, st, btv, gsv);
-                        else launch(r, std::integral_constant<int, OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SWEEP>{}, st, swv, gsv);
-                        eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
-                    }
-                }
+                });
             } else if (table != TBL_KINDS) {
                 // an interval table (+ statistics when given, binned as the statistics-only kernel of the
                 // same histogram spec bins them: no per-second run-time choice)

@@ -127,6 +127,37 @@ for _kind, _t in _TABLES.items():   # no table beside battery storage, whichever
     if _kind != "schedule":
         _t["enable_excludes"] += (("_schedule", "the schedule is enabled: one table output per sim "
                                                 "(the schedule runs alone)"),)
+# the sweeps: a table per variant; what they refuse beside them at enable_<kind> is _enable_battery's to say
+_TABLES["battery_sweep"] = dict(
+    noun="battery sweep tables", name="the battery sweep", enable_excludes=(), run_excludes=(),
+    no_trace="a battery sweep run takes no traces (trace=()): run the batteries over the traces instead "
+             "(battery.sweep_from_traces)")
+_TABLES["dispatch_sweep"] = dict(
+    noun="dispatch sweep tables", name="the dispatch sweep", enable_excludes=(), run_excludes=(),
+    no_trace="a dispatch sweep run takes no traces (trace=()): run the rules over the traces instead "
+             "(dispatch.sweep_from_traces)")
+
+# The battery family: the kinds of _TABLES that carry a state of charge per chain (`sim.soc`) through a work buffer,
+# one of them per sim, through one enabler (_enable_battery), one setter (_set_battery) and one work buffer
+# (_work_window).  Per kind: its module; its parameter rows per variant (0: storage's three integers, None: the
+# schedule's 6 + 4 R); its ctypes struct (the C setter is tmh_set_<kind>); whether it has variants; whether per-chain
+# sites are refused; how enable_<kind> checks the window ("long": n_steps and interval_s, "short": interval_s <=
+# MAX_INTERVAL_S, None: the kind's own arguments do); the attribute its parameters are published in; the attribute
+# that keeps its descriptor.
+_BATTERIES = {
+    "storage": dict(mod="storage", rows=0, cls=_lib.Storage, variants=False, one_site=False, window=None,
+                    params=None, desc="_storage_desc"),
+    "battery": dict(mod="battery", rows=6, cls=_lib.Battery, variants=False, one_site=False, window="short",
+                    params="battery_params", desc="_battery_desc"),
+    "dispatch": dict(mod="dispatch", rows=9, cls=_lib.Dispatch, variants=False, one_site=False, window="short",
+                     params="dispatch_params", desc="_dispatch_desc"),
+    "schedule": dict(mod="schedule", rows=None, cls=_lib.Schedule, variants=False, one_site=True, window="long",
+                     params="schedule_params", desc="_schedule_desc"),
+    "battery_sweep": dict(mod="battery", rows=6, cls=_lib.BatterySweep, variants=True, one_site=True, window="long",
+                          params="battery_params", desc="_sweep_desc"),
+    "dispatch_sweep": dict(mod="dispatch", rows=9, cls=_lib.DispatchSweep, variants=True, one_site=True, window="long",
+                           params="dispatch_params", desc="_dsweep_desc"),
+}
 
 
 class BatchedSim:
@@ -223,24 +254,18 @@ class BatchedSim:
         self._hist_spec = None
         self.series_raw = None    # int64 [n_groups, n_steps, 4] (enable_series)
         self._series = None
-        for kind in _TABLES:   # intervals_raw, registers_raw, demand_raw: int64 [n_intervals, 4 / 6 / 8, n] (enable_<kind>)
+        for kind in _TABLES:   # <kind>_raw: int64 [n_intervals, cols, n] ([K, n_intervals, cols, n]: a sweep) (enable_<kind>)
             setattr(self, kind + "_raw", None)
             setattr(self, "_" + kind, None)
-        self.soc = None           # int64 [n]: the batteries' state of charge (enable_storage)
-        self._storage_args = self._storage_work = self._storage_desc = None
-        self.battery_params = None   # int64 [6, n]: the batteries' parameters (enable_battery); soc and the work buffer as storage's
-        self._battery_desc = None
-        self.dispatch_params = None   # int64 [9, n]: the batteries' and the dispatch rule's parameters (enable_dispatch)
-        self._dispatch_desc = None
-        self.schedule_params = None   # int64 [6 + 4 R, n]: the batteries' parameters and the R rules' (enable_schedule)
-        self.schedule_rules = None    # uint8 [n_intervals]: the rule of each of the table's intervals
-        self._schedule_desc = None
+        # the battery family (_BATTERIES): soc int64 [n] ([K, n]: a sweep), the batteries' state of charge; the
+        # parameters int64 [6, n] (enable_battery), [9, n] (enable_dispatch), [6 + 4 R, n] (enable_schedule) or
+        # [K, 6 / 9, n] (the sweeps); schedule_rules uint8 [n_intervals]: the rule of each of the table's intervals
+        self.soc = self.battery_params = self.dispatch_params = self.schedule_params = self.schedule_rules = None
+        self._battery_args = self._battery_work = None   # (soc, params, the struct's last fields), the work buffer
+        for t in _BATTERIES.values():
+            setattr(self, t["desc"], None)
         self.battery_fleet_raw = None   # int64 [n_groups, n_steps, 8]: the battery fleet series (enable_battery_fleet)
         self._battery_fleet = None
-        self.battery_sweep_raw = None   # int64 [K, n_intervals, 10, n]: the battery sweep's tables (enable_battery_sweep)
-        self._battery_sweep = self._sweep_args = self._sweep_work = self._sweep_desc = None
-        self.dispatch_sweep_raw = None   # int64 [K, n_intervals, 13, n]: the dispatch sweep's tables (enable_dispatch_sweep)
-        self._dispatch_sweep = self._dsweep_args = self._dsweep_work = self._dsweep_desc = None
         self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
@@ -331,8 +356,8 @@ class BatchedSim:
     def _enable_table(self, kind, n_steps, interval_s, step0, buffer):
         """enable_intervals, enable_registers and enable_demand (_TABLES[kind])."""
         torch = _torch()
-        if kind in ("storage", "battery", "dispatch", "schedule"):   # (its descriptor holds the table's: _set_storage, _set_battery, _set_dispatch, _set_schedule)
-            setter = lambda eng, st: getattr(self, "_set_" + kind)(st._obj if st is not None else None)
+        if kind in _BATTERIES:   # (its descriptor holds the table's: _set_battery)
+            setter = lambda eng, st: self._set_battery(kind, st._obj if st is not None else None)
         else:
             setter = getattr(self.L, "tmh_set_" + kind)
         if n_steps is None:
@@ -430,6 +455,150 @@ class BatchedSim:
         load_factor, [n_intervals, n] each."""
         return self._table_watts("demand")
 
+    # ------------------------------------------------------------------ the battery family
+    def _enable_battery(self, kind, n_steps, interval_s, step0, buffer, soc, params, soc0_wh, quantize, n_variants=None,
+                        last=lambda host: ()):
+        """enable_storage, enable_battery, enable_dispatch, enable_schedule and the two sweeps (_BATTERIES[kind]).
+        quantize(): the kind's quantities as host parameters, called when no params tensor is given (storage: its
+        three integers and the starting state of charge); last(host): the fields of the kind's struct after params
+        (the schedule's rule array and rule count).  A refused call leaves what was enabled before as it was."""
+        torch = _torch()
+        t, name, label = _BATTERIES[kind], _TABLES[kind]["name"], kind.replace("_", " ")
+        if n_steps is None:
+            if getattr(self, "_" + kind) is not None:   # (else soc and the work buffer may be another kind's)
+                self.soc = self._battery_work = self._battery_args = None
+                setattr(self, t["desc"], None)
+                for attr in (t["params"],) + (("schedule_rules",) if kind == "schedule" else ()):
+                    if attr:
+                        setattr(self, attr, None)
+            return self._enable_table(kind, None, interval_s, step0, buffer)
+        if self.precision != _lib.TMH_FP64:
+            raise ValueError(f"{name} needs precision='fp64': an fp32 engine replaces its guard-band seconds "
+                             "after the expansion, and the state of charge depends on every earlier second")
+        if t["variants"]:
+            if self._series is not None:
+                raise ValueError(f"a fleet series is enabled: one table output per sim ({name} runs alone)")
+            if self._battery_fleet is not None:
+                raise ValueError(f"a battery fleet series is enabled: it is the battery kind's ({name} runs alone)")
+            for other, ot in _TABLES.items():
+                if other != kind and getattr(self, "_" + other) is not None:
+                    raise ValueError(f"{ot['name']} is enabled: one table output per sim ({name} runs alone)")
+        if t["one_site"] and self.sites is not None:
+            raise ValueError(f"{name} cannot run with per-chain sites")
+        mod = importlib.import_module("." + t["mod"], __package__)
+        if t["window"] == "long" and (int(n_steps) < 1 or int(interval_s) < 1 or int(interval_s) > mod.MAX_INTERVAL_S):
+            raise ValueError(f"enable_{kind}: n_steps >= 1 and 1 <= interval_s <= {mod.MAX_INTERVAL_S}")
+        if t["window"] == "short" and int(interval_s) > mod.MAX_INTERVAL_S:
+            raise ValueError(f"enable_{kind}: interval_s <= {mod.MAX_INTERVAL_S}")
+        rows, lead = t["rows"], "K, " if t["variants"] else ""
+        if rows == 0:
+            host, (*tail, x0) = None, quantize()
+        elif params is None:
+            host = quantize()
+            params = torch.from_numpy(host).to(self.device)
+        else:
+            if (params.dtype != torch.int64 or params.device != self.device or params.dim() != (3 if t["variants"] else 2)
+                    or params.shape[-1] != self.n or (rows is not None and params.shape[-2] != rows)
+                    or (self.n > 1 and params.stride(-1) != 1)):
+                raise ValueError(f"{label} params must be an int64 [{lead}{'6 + 4 R' if rows is None else rows}, {self.n}] "
+                                 f"tensor on {self.device}, chains contiguous")
+            host = getattr(mod, "check_sweep_params" if t["variants"] else "check_params")(params)
+        if t["variants"]:
+            K = int(host.shape[0])
+            if n_variants is not None and int(n_variants) != K:
+                raise ValueError(f"enable_{kind}: n_variants {n_variants} but parameters of {K} variants")
+            tail, shape = (K,), (K, self.n)
+        else:
+            if rows != 0:
+                tail = last(host)
+            shape = (self.n,)
+        if soc is None:
+            soc = (torch.full(shape, x0, dtype=torch.int64, device=self.device) if rows == 0 else
+                   torch.from_numpy(mod.quantize_sweep_soc(soc0_wh, host) if t["variants"]
+                                    else mod.quantize_soc(soc0_wh, host[:6])).to(self.device))
+        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != shape
+              or (self.n > 1 and soc.stride(-1) != 1)):
+            raise ValueError(f"{label} soc must be an int64 [{K}, {self.n}] tensor on {self.device}, chains contiguous"
+                             if t["variants"] else
+                             f"{label} soc must be a contiguous int64 [{self.n}] tensor on {self.device}")
+        kept = self._battery_args
+        self._battery_args = (soc, params, tuple(tail))
+        try:
+            if t["variants"]:
+                raw = self._enable_sweep_table(kind, int(n_steps), int(interval_s), step0, buffer, len(mod.COLUMNS))
+            else:
+                raw = self._enable_table(kind, n_steps, interval_s, step0, buffer)
+        except Exception:   # (refused: what was enabled before stays as it was)
+            self._battery_args = kept
+            raise
+        self.soc = soc
+        if t["params"]:
+            setattr(self, t["params"], params)
+        return raw
+
+    def _enable_sweep_table(self, kind, n_steps, interval_s, step0, buffer, nc):
+        """_enable_table for the sweeps: a table per variant, [K, n_intervals, nc, n], and the variants' parameters and
+        state of charge (_battery_args) at the table's ld."""
+        torch = _torch()
+        label, (soc, params, (K,)) = kind.replace("_", " "), self._battery_args
+        npar, nk = int(params.shape[1]), -(-n_steps // interval_s)
+        if buffer is None:
+            buffer = torch.zeros(K, nk, nc, self.n, dtype=torch.int64, device=self.device)
+        elif buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (K, nk, nc, self.n):
+            raise ValueError(f"{label} buffer must be an int64 [{K}, {nk}, {nc}, {self.n}] tensor on {self.device}")
+        ld = int(buffer.stride(2))
+        if (ld < self.n or (self.n > 1 and buffer.stride(3) != 1) or (nk > 1 and buffer.stride(1) != nc * ld)
+                or (K > 1 and buffer.stride(0) != nk * nc * ld)):
+            raise ValueError(f"{label} buffer strides {tuple(buffer.stride())}: need ({nk * nc} ld, {nc} ld, ld, 1) "
+                             f"with ld >= {self.n}")
+        if int(params.stride(1)) != ld or (K > 1 and (int(params.stride(0)) != npar * ld or int(soc.stride(0)) != ld)):
+            raise ValueError(f"{label} params strides {tuple(params.stride())}, soc strides {tuple(soc.stride())}: need "
+                             f"({npar} ld, ld, 1) and (ld, 1) with the table's ld {ld}: slice them from tensors of the same width")
+        table = _lib.Intervals(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
+        _lib.check(self._set_battery(kind, table))
+        setattr(self, kind + "_raw", buffer)
+        setattr(self, "_" + kind, table)
+        return buffer
+
+    def _set_battery(self, kind, table):
+        """tmh_set_<kind> of a battery-family kind with the table descriptor `table` (or None) and _battery_args.  The
+        work buffer is sized for the default window of a run and grown by run() when a window needs more
+        (_work_window).  The parameters' row stride must be the table's ld (one ld for both)."""
+        t, setter = _BATTERIES[kind], getattr(self.L, "tmh_set_" + kind)
+        if table is None:
+            return setter(self._eng, None)
+        torch = _torch()
+        soc, params, tail = self._battery_args
+        K = tail[0] if t["variants"] else 1
+        if params is not None and not t["variants"] and int(params.stride(0)) != int(table.ld):
+            raise ValueError(f"{kind} params row stride {int(params.stride(0))} != the table's ld {int(table.ld)}: "
+                             "slice both from tensors of the same width")
+        nb = self.L.tmh_battery_sweep_work_bytes(self.n, min(int(table.n_steps), 86400), K)
+        work = self._battery_work   # (kept from enable to enable; a sweep enabled again with more variants: the setter's floor)
+        if work is None or (t["variants"] and work.numel() < nb):
+            work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
+        st = t["cls"](table, soc.data_ptr(), work.data_ptr(), work.numel(), *(() if params is None else (params.data_ptr(),)),
+                      *(x.data_ptr() if torch.is_tensor(x) else x for x in tail))
+        rc = setter(self._eng, C.byref(st))
+        if rc == 0:
+            self._battery_work = work
+            setattr(self, t["desc"], st)
+        return rc
+
+    def _work_window(self, win):
+        """run(): the enabled battery-family kind's work buffer holds a window of `win` steps (a larger one replaces
+        it, and the descriptor is set again)."""
+        for kind, t in _BATTERIES.items():
+            table = getattr(self, "_" + kind)
+            if table is None:
+                continue
+            K = self._battery_args[2][0] if t["variants"] else 1
+            need = self.L.tmh_battery_sweep_work_bytes(self.n, int(win), K)
+            if self._battery_work.numel() < need:
+                _torch().cuda.synchronize(self.device)   # (launches of earlier runs may still read the old one)
+                self._battery_work = _torch().empty(need, dtype=torch_uint8(), device=self.device)
+                _lib.check(self._set_battery(kind, table))
+
     # ------------------------------------------------------------------ battery storage
     def enable_storage(self, n_steps, interval_s=900, *, capacity_wh=None, charge_w=None, discharge_w=None, soc0_wh=0.0,
                        step0=None, buffer=None, soc=None):
@@ -445,67 +614,15 @@ class BatchedSim:
         sims only: an fp32 engine replaces guard-band seconds after the expansion, and the state of
         charge depends on every earlier second.  Runs with storage take no traces, no fleet series and no
         other table; compaction is allowed.  n_steps=None switches the output off."""
-        torch = _torch()
-        if n_steps is None:
-            if self._battery is None and self._dispatch is None and self._schedule is None:   # (soc and the work buffer may be another kind's)
-                self.soc = self._storage_work = self._storage_desc = None
-            return self._enable_table("storage", None, interval_s, step0, buffer)
-        if self.precision != _lib.TMH_FP64:
-            raise ValueError("battery storage needs precision='fp64': an fp32 engine replaces its guard-band seconds "
-                             "after the expansion, and the state of charge depends on every earlier second")
-        if capacity_wh is None or charge_w is None or discharge_w is None:
-            raise ValueError("enable_storage: capacity_wh, charge_w and discharge_w are required")
-        from . import storage
-        cap, pc, pd, x0 = storage.quantize_params(capacity_wh, charge_w, discharge_w, soc0_wh)
-        if int(interval_s) > storage.MAX_INTERVAL_S:
-            raise ValueError(f"enable_storage: interval_s <= {storage.MAX_INTERVAL_S}")
-        if soc is None:
-            soc = torch.full((self.n,), x0, dtype=torch.int64, device=self.device)
-        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (self.n,)
-              or (self.n > 1 and soc.stride(0) != 1)):
-            raise ValueError(f"storage soc must be a contiguous int64 [{self.n}] tensor on {self.device}")
-        kept = self._storage_args
-        self._storage_args = (soc, cap, pc, pd)
-        try:
-            raw = self._enable_table("storage", n_steps, interval_s, step0, buffer)
-        except Exception:   # (refused: what was enabled before stays as it was)
-            self._storage_args = kept
-            raise
-        self.soc = soc
-        return raw
-
-    def _set_storage(self, table):
-        """tmh_set_storage with the table descriptor `table` (or None) and the battery's fields; the work
-        buffer is sized for the default window of a run and grown by run() when a window needs more."""
-        if table is None:
-            return self.L.tmh_set_storage(self._eng, None)
-        torch = _torch()
-        soc, cap, pc, pd = self._storage_args
-        if self._storage_work is None:
-            nb = self.L.tmh_storage_work_bytes(self.n, min(int(table.n_steps), 86400))
-            self._storage_work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
-        work = self._storage_work
-        st = _lib.Storage(table, soc.data_ptr(), work.data_ptr(), work.numel(), cap, pc, pd)
-        rc = self.L.tmh_set_storage(self._eng, C.byref(st))
-        if rc == 0:
-            self._storage_desc = st
-        return rc
-
-    def _storage_window(self, win):
-        """run(): the work buffer (storage's, the battery kind's or battery dispatch's) holds a window of `win`
-        steps (a larger one replaces it)."""
-        need = self.L.tmh_storage_work_bytes(self.n, int(win))
-        if self._storage_work.numel() < need:
-            _torch().cuda.synchronize(self.device)   # (launches of earlier runs may still read the old one)
-            self._storage_work = _torch().empty(need, dtype=torch_uint8(), device=self.device)
-            if self._battery is not None:
-                _lib.check(self._set_battery(self._battery))
-            elif self._dispatch is not None:
-                _lib.check(self._set_dispatch(self._dispatch))
-            elif self._schedule is not None:
-                _lib.check(self._set_schedule(self._schedule))
-            else:
-                _lib.check(self._set_storage(self._storage))
+        def quantize():
+            if capacity_wh is None or charge_w is None or discharge_w is None:
+                raise ValueError("enable_storage: capacity_wh, charge_w and discharge_w are required")
+            from . import storage
+            q = storage.quantize_params(capacity_wh, charge_w, discharge_w, soc0_wh)
+            if int(interval_s) > storage.MAX_INTERVAL_S:
+                raise ValueError(f"enable_storage: interval_s <= {storage.MAX_INTERVAL_S}")
+            return q
+        return self._enable_battery("storage", n_steps, interval_s, step0, buffer, soc, None, soc0_wh, quantize)
 
     def storage(self):
         """The storage table in watts and watt-hours (storage.to_watts of storage_raw): the intervals'
@@ -528,63 +645,15 @@ class BatchedSim:
         [0, capacity]; a caller's soc tensor is clamped into it by the first window.  buffer, soc, step0,
         fp64 only, no traces, no fleet series, no other table, compaction: as enable_storage.  n_steps=None
         switches the output off."""
-        torch = _torch()
-        if n_steps is None:
-            if self._battery is not None:   # (soc and the work buffer may be enable_storage's)
-                self.soc = self._storage_work = self._battery_desc = self.battery_params = None
-            if self._battery_fleet is not None:   # (the kind's own output: off with it)
-                self.enable_battery_fleet(None)
-            return self._enable_table("battery", None, interval_s, step0, buffer)
-        if self.precision != _lib.TMH_FP64:
-            raise ValueError("the battery kind needs precision='fp64': an fp32 engine replaces its guard-band seconds "
-                             "after the expansion, and the state of charge depends on every earlier second")
-        from . import battery
-        if int(interval_s) > battery.MAX_INTERVAL_S:
-            raise ValueError(f"enable_battery: interval_s <= {battery.MAX_INTERVAL_S}")
-        if params is None:
+        if n_steps is None and self._battery_fleet is not None:   # (the kind's own output: off with it)
+            self.enable_battery_fleet(None)
+
+        def quantize():
             if capacity_wh is None or charge_w is None or discharge_w is None:
                 raise ValueError("enable_battery: capacity_wh, charge_w and discharge_w (or params) are required")
-            host = battery.quantize_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w, n=self.n)
-            params = torch.from_numpy(host).to(self.device)
-        else:
-            if (params.dtype != torch.int64 or params.device != self.device or tuple(params.shape) != (6, self.n)
-                    or (self.n > 1 and params.stride(1) != 1)):
-                raise ValueError(f"battery params must be an int64 [6, {self.n}] tensor on {self.device}, chains contiguous")
-            host = battery.check_params(params)
-        if soc is None:
-            soc = torch.from_numpy(battery.quantize_soc(soc0_wh, host)).to(self.device)
-        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (self.n,)
-              or (self.n > 1 and soc.stride(0) != 1)):
-            raise ValueError(f"battery soc must be a contiguous int64 [{self.n}] tensor on {self.device}")
-        kept = self._storage_args
-        self._storage_args = (soc, params)
-        try:
-            raw = self._enable_table("battery", n_steps, interval_s, step0, buffer)
-        except Exception:   # (refused: what was enabled before stays as it was)
-            self._storage_args = kept
-            raise
-        self.soc, self.battery_params = soc, params
-        return raw
-
-    def _set_battery(self, table):
-        """tmh_set_battery with the table descriptor `table` (or None); the work buffer as _set_storage's.
-        The parameters' row stride must be the table's ld (one ld for both: tmh_battery)."""
-        if table is None:
-            return self.L.tmh_set_battery(self._eng, None)
-        torch = _torch()
-        soc, params = self._storage_args
-        if int(params.stride(0)) != int(table.ld):
-            raise ValueError(f"battery params row stride {int(params.stride(0))} != the table's ld {int(table.ld)}: "
-                             "slice both from tensors of the same width")
-        if self._storage_work is None:
-            nb = self.L.tmh_storage_work_bytes(self.n, min(int(table.n_steps), 86400))
-            self._storage_work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
-        work = self._storage_work
-        bt = _lib.Battery(table, soc.data_ptr(), work.data_ptr(), work.numel(), params.data_ptr())
-        rc = self.L.tmh_set_battery(self._eng, C.byref(bt))
-        if rc == 0:
-            self._battery_desc = bt
-        return rc
+            from . import battery
+            return battery.quantize_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w, n=self.n)
+        return self._enable_battery("battery", n_steps, interval_s, step0, buffer, soc, params, soc0_wh, quantize)
 
     def battery(self):
         """The battery table in watts and watt-hours (battery.to_watts of battery_raw): storage's keys plus
@@ -607,62 +676,13 @@ class BatchedSim:
         [n_intervals, 13, N]); its values must lie in dispatch.RANGES (checked here; the kernels clamp).
         soc0_wh, soc, buffer, step0, fp64 only, no traces, no fleet series, no battery fleet series, no other
         table, compaction: as enable_battery.  n_steps=None switches the output off."""
-        torch = _torch()
-        if n_steps is None:
-            if self._dispatch is not None:   # (soc and the work buffer may be another kind's)
-                self.soc = self._storage_work = self._dispatch_desc = self.dispatch_params = None
-            return self._enable_table("dispatch", None, interval_s, step0, buffer)
-        if self.precision != _lib.TMH_FP64:
-            raise ValueError("battery dispatch needs precision='fp64': an fp32 engine replaces its guard-band seconds "
-                             "after the expansion, and the state of charge depends on every earlier second")
-        from . import dispatch
-        if int(interval_s) > dispatch.MAX_INTERVAL_S:
-            raise ValueError(f"enable_dispatch: interval_s <= {dispatch.MAX_INTERVAL_S}")
-        if params is None:
+        def quantize():
             if capacity_wh is None or charge_w is None or discharge_w is None:
                 raise ValueError("enable_dispatch: capacity_wh, charge_w and discharge_w (or params) are required")
-            host = dispatch.quantize_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
+            from . import dispatch
+            return dispatch.quantize_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
                                             charge_above_w, discharge_above_w, feed_in_limit_w, n=self.n)
-            params = torch.from_numpy(host).to(self.device)
-        else:
-            if (params.dtype != torch.int64 or params.device != self.device or tuple(params.shape) != (9, self.n)
-                    or (self.n > 1 and params.stride(1) != 1)):
-                raise ValueError(f"dispatch params must be an int64 [9, {self.n}] tensor on {self.device}, chains contiguous")
-            host = dispatch.check_params(params)
-        if soc is None:
-            soc = torch.from_numpy(dispatch.quantize_soc(soc0_wh, host)).to(self.device)
-        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (self.n,)
-              or (self.n > 1 and soc.stride(0) != 1)):
-            raise ValueError(f"dispatch soc must be a contiguous int64 [{self.n}] tensor on {self.device}")
-        kept = self._storage_args
-        self._storage_args = (soc, params)
-        try:
-            raw = self._enable_table("dispatch", n_steps, interval_s, step0, buffer)
-        except Exception:   # (refused: what was enabled before stays as it was)
-            self._storage_args = kept
-            raise
-        self.soc, self.dispatch_params = soc, params
-        return raw
-
-    def _set_dispatch(self, table):
-        """tmh_set_dispatch with the table descriptor `table` (or None); the work buffer as _set_storage's.
-        The parameters' row stride must be the table's ld (one ld for both: tmh_dispatch)."""
-        if table is None:
-            return self.L.tmh_set_dispatch(self._eng, None)
-        torch = _torch()
-        soc, params = self._storage_args
-        if int(params.stride(0)) != int(table.ld):
-            raise ValueError(f"dispatch params row stride {int(params.stride(0))} != the table's ld {int(table.ld)}: "
-                             "slice both from tensors of the same width")
-        if self._storage_work is None:
-            nb = self.L.tmh_storage_work_bytes(self.n, min(int(table.n_steps), 86400))
-            self._storage_work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
-        work = self._storage_work
-        dp = _lib.Dispatch(table, soc.data_ptr(), work.data_ptr(), work.numel(), params.data_ptr())
-        rc = self.L.tmh_set_dispatch(self._eng, C.byref(dp))
-        if rc == 0:
-            self._dispatch_desc = dp
-        return rc
+        return self._enable_battery("dispatch", n_steps, interval_s, step0, buffer, soc, params, soc0_wh, quantize)
 
     def dispatch(self):
         """The dispatch table in watts and watt-hours (dispatch.to_watts of dispatch_raw): the battery kind's keys
@@ -688,82 +708,37 @@ class BatchedSim:
         traces, no fleet series, no battery fleet series, no other table, compaction: as enable_dispatch; per-chain
         sites are refused.  A refused call leaves what was enabled before as it was.  n_steps=None switches the
         output off."""
-        torch = _torch()
-        if n_steps is None:
-            if self._schedule is not None:   # (soc and the work buffer may be another kind's)
-                self.soc = self._storage_work = self._schedule_desc = self.schedule_params = self.schedule_rules = None
-            return self._enable_table("schedule", None, interval_s, step0, buffer)
-        if self.precision != _lib.TMH_FP64:
-            raise ValueError("the schedule needs precision='fp64': an fp32 engine replaces its guard-band seconds "
-                             "after the expansion, and the state of charge depends on every earlier second")
-        if self.sites is not None:
-            raise ValueError("the schedule cannot run with per-chain sites")
         from . import schedule
-        if int(n_steps) < 1 or int(interval_s) < 1 or int(interval_s) > schedule.MAX_INTERVAL_S:
-            raise ValueError(f"enable_schedule: n_steps >= 1 and 1 <= interval_s <= {schedule.MAX_INTERVAL_S}")
-        if params is None:
+
+        def quantize():
             if capacity_wh is None or charge_w is None or discharge_w is None or rules is None:
                 raise ValueError("enable_schedule: capacity_wh, charge_w, discharge_w and rules (or params) are required")
-            host = schedule.quantize_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
+            return schedule.quantize_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
                                             rules=rules, n=self.n)
-            params = torch.from_numpy(host).to(self.device)
-        else:
-            if (params.dtype != torch.int64 or params.device != self.device or params.dim() != 2
-                    or params.shape[1] != self.n or (self.n > 1 and params.stride(1) != 1)):
-                raise ValueError(f"schedule params must be an int64 [6 + 4 R, {self.n}] tensor on {self.device}, chains contiguous")
-            host = schedule.check_params(params)
-        R = schedule.n_rules_of(host)
-        if n_rules is not None and int(n_rules) != R:
-            raise ValueError(f"enable_schedule: n_rules {int(n_rules)} but the schedule params hold {R} rules")
-        if rule_of_interval is None:
-            raise ValueError("enable_schedule: the schedule needs rule_of_interval (the rule of each metering interval)")
-        nk = schedule.n_intervals(int(n_steps), int(interval_s))
-        if torch.is_tensor(rule_of_interval):
-            if rule_of_interval.dtype != torch.uint8 or rule_of_interval.dim() != 1:
-                raise ValueError("schedule rule_of_interval must be a uint8 [n_intervals] array")
-            schedule.check_rules(rule_of_interval, R, nk)
-            roi = rule_of_interval.to(self.device).contiguous()
-        else:
+
+        def last(host):   # the rule array of the table's intervals on the device, and the rule count
+            torch = _torch()
+            R = schedule.n_rules_of(host)
+            if n_rules is not None and int(n_rules) != R:
+                raise ValueError(f"enable_schedule: n_rules {int(n_rules)} but the schedule params hold {R} rules")
+            if rule_of_interval is None:
+                raise ValueError("enable_schedule: the schedule needs rule_of_interval (the rule of each metering interval)")
+            nk = schedule.n_intervals(int(n_steps), int(interval_s))
+            if torch.is_tensor(rule_of_interval):
+                if rule_of_interval.dtype != torch.uint8 or rule_of_interval.dim() != 1:
+                    raise ValueError("schedule rule_of_interval must be a uint8 [n_intervals] array")
+                schedule.check_rules(rule_of_interval, R, nk)
+                return rule_of_interval.to(self.device).contiguous(), R
             a = np.asarray(rule_of_interval)
             if a.dtype != np.uint8:
                 if a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) > 255)):
                     raise ValueError("schedule rule_of_interval must hold integers in [0, 255]")
                 a = a.astype(np.uint8)
-            roi = torch.from_numpy(np.ascontiguousarray(schedule.check_rules(a, R, nk))).to(self.device)
-        if soc is None:
-            soc = torch.from_numpy(schedule.quantize_soc(soc0_wh, host[:6])).to(self.device)
-        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (self.n,)
-              or (self.n > 1 and soc.stride(0) != 1)):
-            raise ValueError(f"schedule soc must be a contiguous int64 [{self.n}] tensor on {self.device}")
-        kept = self._storage_args
-        self._storage_args = (soc, params, roi, R)
-        try:
-            raw = self._enable_table("schedule", n_steps, interval_s, step0, buffer)
-        except Exception:   # (refused: what was enabled before stays as it was)
-            self._storage_args = kept
-            raise
-        self.soc, self.schedule_params, self.schedule_rules = soc, params, roi
+            return torch.from_numpy(np.ascontiguousarray(schedule.check_rules(a, R, nk))).to(self.device), R
+        raw = self._enable_battery("schedule", n_steps, interval_s, step0, buffer, soc, params, soc0_wh, quantize, last=last)
+        if n_steps is not None:
+            self.schedule_rules = self._battery_args[2][0]
         return raw
-
-    def _set_schedule(self, table):
-        """tmh_set_schedule with the table descriptor `table` (or None); the work buffer as _set_storage's.
-        The parameters' row stride must be the table's ld (one ld for both: tmh_schedule)."""
-        if table is None:
-            return self.L.tmh_set_schedule(self._eng, None)
-        torch = _torch()
-        soc, params, roi, R = self._storage_args
-        if int(params.stride(0)) != int(table.ld):
-            raise ValueError(f"schedule params row stride {int(params.stride(0))} != the table's ld {int(table.ld)}: "
-                             "slice both from tensors of the same width")
-        if self._storage_work is None:
-            nb = self.L.tmh_storage_work_bytes(self.n, min(int(table.n_steps), 86400))
-            self._storage_work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
-        work = self._storage_work
-        sc = _lib.Schedule(table, soc.data_ptr(), work.data_ptr(), work.numel(), params.data_ptr(), roi.data_ptr(), R)
-        rc = self.L.tmh_set_schedule(self._eng, C.byref(sc))
-        if rc == 0:
-            self._schedule_desc = sc
-        return rc
 
     def schedule(self):
         """The schedule table in watts and watt-hours (schedule.to_watts of schedule_raw): battery dispatch's keys,
@@ -784,85 +759,14 @@ class BatchedSim:
         soc, params: tensors of those shapes to use, possibly column slices of wider [.., N] tensors of one width.
         fp64 only, no traces, no fleet series, no battery fleet series, no other table, no per-chain sites;
         compaction is allowed.  n_steps=None switches the output off."""
-        torch = _torch()
-        L = self.L
-        if n_steps is None:
-            _lib.check(L.tmh_set_battery_sweep(self._eng, None))
-            if self._battery_sweep is not None:
-                self.soc = self.battery_params = None
-            self.battery_sweep_raw = self._battery_sweep = self._sweep_args = self._sweep_work = self._sweep_desc = None
-            return None
-        if self.precision != _lib.TMH_FP64:
-            raise ValueError("the battery sweep needs precision='fp64': an fp32 engine replaces its guard-band seconds "
-                             "after the expansion, and the state of charge depends on every earlier second")
-        if self._series is not None:
-            raise ValueError("a fleet series is enabled: one table output per sim (the battery sweep runs alone)")
-        if self._battery_fleet is not None:
-            raise ValueError("a battery fleet series is enabled: it is the battery kind's (the battery sweep runs alone)")
-        for kind, t in _TABLES.items():
-            if getattr(self, "_" + kind) is not None:
-                raise ValueError(f"{t['name']} is enabled: one table output per sim (the battery sweep runs alone)")
-        if self._dispatch_sweep is not None:
-            raise ValueError("the dispatch sweep is enabled: one table output per sim (the battery sweep runs alone)")
-        if self.sites is not None:
-            raise ValueError("the battery sweep cannot run with per-chain sites")
-        from . import battery
-        n_steps, interval_s = int(n_steps), int(interval_s)
-        if n_steps < 1 or interval_s < 1 or interval_s > battery.MAX_INTERVAL_S:
-            raise ValueError(f"enable_battery_sweep: n_steps >= 1 and 1 <= interval_s <= {battery.MAX_INTERVAL_S}")
-        if params is None:
+        def quantize():
             if capacity_wh is None or charge_w is None or discharge_w is None:
                 raise ValueError("enable_battery_sweep: capacity_wh, charge_w and discharge_w (or params) are required")
-            host = battery.quantize_sweep_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
+            from . import battery
+            return battery.quantize_sweep_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
                                                  n=self.n, n_variants=n_variants)
-            params = torch.from_numpy(host).to(self.device)
-        else:
-            if (params.dtype != torch.int64 or params.device != self.device or params.dim() != 3
-                    or tuple(params.shape[1:]) != (6, self.n) or (self.n > 1 and params.stride(2) != 1)):
-                raise ValueError(f"battery sweep params must be an int64 [K, 6, {self.n}] tensor on {self.device}, chains contiguous")
-            host = battery.check_sweep_params(params)
-        K = int(host.shape[0])
-        if n_variants is not None and int(n_variants) != K:
-            raise ValueError(f"enable_battery_sweep: n_variants {n_variants} but parameters of {K} variants")
-        if soc is None:
-            soc = torch.from_numpy(battery.quantize_sweep_soc(soc0_wh, host)).to(self.device)
-        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (K, self.n)
-              or (self.n > 1 and soc.stride(1) != 1)):
-            raise ValueError(f"battery sweep soc must be an int64 [{K}, {self.n}] tensor on {self.device}, chains contiguous")
-        nk, nc = battery.n_intervals(n_steps, interval_s), len(battery.COLUMNS)
-        if buffer is None:
-            buffer = torch.zeros(K, nk, nc, self.n, dtype=torch.int64, device=self.device)
-        elif buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (K, nk, nc, self.n):
-            raise ValueError(f"battery sweep buffer must be an int64 [{K}, {nk}, {nc}, {self.n}] tensor on {self.device}")
-        ld = int(buffer.stride(2))
-        if (ld < self.n or (self.n > 1 and buffer.stride(3) != 1) or (nk > 1 and buffer.stride(1) != nc * ld)
-                or (K > 1 and buffer.stride(0) != nk * nc * ld)):
-            raise ValueError(f"battery sweep buffer strides {tuple(buffer.stride())}: need ({nk * nc} ld, {nc} ld, ld, 1) "
-                             f"with ld >= {self.n}")
-        if int(params.stride(1)) != ld or (K > 1 and (int(params.stride(0)) != 6 * ld or int(soc.stride(0)) != ld)):
-            raise ValueError(f"battery sweep params strides {tuple(params.stride())}, soc strides {tuple(soc.stride())}: need "
-                             f"(6 ld, ld, 1) and (ld, 1) with the table's ld {ld}: slice them from tensors of the same width")
-        table = _lib.Intervals(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
-        nb = L.tmh_battery_sweep_work_bytes(self.n, min(n_steps, 86400), K)
-        work = self._sweep_work
-        if work is None or work.numel() < nb:
-            work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
-        sw = _lib.BatterySweep(table, soc.data_ptr(), work.data_ptr(), work.numel(), params.data_ptr(), K)
-        _lib.check(L.tmh_set_battery_sweep(self._eng, C.byref(sw)))
-        self._battery_sweep, self._sweep_desc, self._sweep_args, self._sweep_work = table, sw, (soc, params), work
-        self.battery_sweep_raw, self.soc, self.battery_params = buffer, soc, params
-        return buffer
-
-    def _sweep_window(self, win):
-        """run(): the sweep's work buffer holds a window of `win` steps (a larger one is allocated and the
-        descriptor set again; the sim has synchronised nothing: the old buffer's launches are in stream order)."""
-        sw = self._sweep_desc
-        need = self.L.tmh_battery_sweep_work_bytes(self.n, int(win), int(sw.n_variants))
-        if self._sweep_work.numel() < need:
-            _torch().cuda.synchronize(self.device)
-            self._sweep_work = _torch().empty(need, dtype=torch_uint8(), device=self.device)
-            sw.work, sw.work_bytes = self._sweep_work.data_ptr(), self._sweep_work.numel()
-            _lib.check(self.L.tmh_set_battery_sweep(self._eng, C.byref(sw)))
+        return self._enable_battery("battery_sweep", n_steps, interval_s, step0, buffer, soc, params, soc0_wh, quantize,
+                                    n_variants=n_variants)
 
     def battery_sweep(self):
         """The sweep's tables in watts and watt-hours: a list of battery.to_watts dicts, one per variant."""
@@ -888,86 +792,15 @@ class BatchedSim:
         the parameters [K, 9, n].  buffer, soc, params: tensors of those shapes to use, possibly column slices of
         wider [.., N] tensors of one width.  fp64 only, no traces, no fleet series, no battery fleet series, no
         other table, no per-chain sites; compaction is allowed.  n_steps=None switches the output off."""
-        torch = _torch()
-        L = self.L
-        if n_steps is None:
-            _lib.check(L.tmh_set_dispatch_sweep(self._eng, None))
-            if self._dispatch_sweep is not None:
-                self.soc = self.dispatch_params = None
-            self.dispatch_sweep_raw = self._dispatch_sweep = self._dsweep_args = self._dsweep_work = self._dsweep_desc = None
-            return None
-        if self.precision != _lib.TMH_FP64:
-            raise ValueError("the dispatch sweep needs precision='fp64': an fp32 engine replaces its guard-band seconds "
-                             "after the expansion, and the state of charge depends on every earlier second")
-        if self._series is not None:
-            raise ValueError("a fleet series is enabled: one table output per sim (the dispatch sweep runs alone)")
-        if self._battery_fleet is not None:
-            raise ValueError("a battery fleet series is enabled: it is the battery kind's (the dispatch sweep runs alone)")
-        for kind, t in _TABLES.items():
-            if getattr(self, "_" + kind) is not None:
-                raise ValueError(f"{t['name']} is enabled: one table output per sim (the dispatch sweep runs alone)")
-        if self._battery_sweep is not None:
-            raise ValueError("the battery sweep is enabled: one table output per sim (the dispatch sweep runs alone)")
-        if self.sites is not None:
-            raise ValueError("the dispatch sweep cannot run with per-chain sites")
-        from . import dispatch
-        n_steps, interval_s = int(n_steps), int(interval_s)
-        if n_steps < 1 or interval_s < 1 or interval_s > dispatch.MAX_INTERVAL_S:
-            raise ValueError(f"enable_dispatch_sweep: n_steps >= 1 and 1 <= interval_s <= {dispatch.MAX_INTERVAL_S}")
-        npar = len(dispatch.PARAMS)
-        if params is None:
+        def quantize():
             if capacity_wh is None or charge_w is None or discharge_w is None:
                 raise ValueError("enable_dispatch_sweep: capacity_wh, charge_w and discharge_w (or params) are required")
-            host = dispatch.quantize_sweep_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
+            from . import dispatch
+            return dispatch.quantize_sweep_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
                                                   charge_above_w, discharge_above_w, feed_in_limit_w, n=self.n,
                                                   n_variants=n_variants)
-            params = torch.from_numpy(host).to(self.device)
-        else:
-            if (params.dtype != torch.int64 or params.device != self.device or params.dim() != 3
-                    or tuple(params.shape[1:]) != (npar, self.n) or (self.n > 1 and params.stride(2) != 1)):
-                raise ValueError(f"dispatch sweep params must be an int64 [K, {npar}, {self.n}] tensor on {self.device}, chains contiguous")
-            host = dispatch.check_sweep_params(params)
-        K = int(host.shape[0])
-        if n_variants is not None and int(n_variants) != K:
-            raise ValueError(f"enable_dispatch_sweep: n_variants {n_variants} but parameters of {K} variants")
-        if soc is None:
-            soc = torch.from_numpy(dispatch.quantize_sweep_soc(soc0_wh, host)).to(self.device)
-        elif (soc.dtype != torch.int64 or soc.device != self.device or tuple(soc.shape) != (K, self.n)
-              or (self.n > 1 and soc.stride(1) != 1)):
-            raise ValueError(f"dispatch sweep soc must be an int64 [{K}, {self.n}] tensor on {self.device}, chains contiguous")
-        nk, nc = dispatch.n_intervals(n_steps, interval_s), len(dispatch.COLUMNS)
-        if buffer is None:
-            buffer = torch.zeros(K, nk, nc, self.n, dtype=torch.int64, device=self.device)
-        elif buffer.dtype != torch.int64 or buffer.device != self.device or tuple(buffer.shape) != (K, nk, nc, self.n):
-            raise ValueError(f"dispatch sweep buffer must be an int64 [{K}, {nk}, {nc}, {self.n}] tensor on {self.device}")
-        ld = int(buffer.stride(2))
-        if (ld < self.n or (self.n > 1 and buffer.stride(3) != 1) or (nk > 1 and buffer.stride(1) != nc * ld)
-                or (K > 1 and buffer.stride(0) != nk * nc * ld)):
-            raise ValueError(f"dispatch sweep buffer strides {tuple(buffer.stride())}: need ({nk * nc} ld, {nc} ld, ld, 1) "
-                             f"with ld >= {self.n}")
-        if int(params.stride(1)) != ld or (K > 1 and (int(params.stride(0)) != npar * ld or int(soc.stride(0)) != ld)):
-            raise ValueError(f"dispatch sweep params strides {tuple(params.stride())}, soc strides {tuple(soc.stride())}: need "
-                             f"({npar} ld, ld, 1) and (ld, 1) with the table's ld {ld}: slice them from tensors of the same width")
-        table = _lib.Intervals(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, interval_s, ld)
-        nb = L.tmh_battery_sweep_work_bytes(self.n, min(n_steps, 86400), K)
-        work = self._dsweep_work
-        if work is None or work.numel() < nb:
-            work = torch.empty(max(nb, 8), dtype=torch.uint8, device=self.device)
-        sw = _lib.DispatchSweep(table, soc.data_ptr(), work.data_ptr(), work.numel(), params.data_ptr(), K)
-        _lib.check(L.tmh_set_dispatch_sweep(self._eng, C.byref(sw)))
-        self._dispatch_sweep, self._dsweep_desc, self._dsweep_args, self._dsweep_work = table, sw, (soc, params), work
-        self.dispatch_sweep_raw, self.soc, self.dispatch_params = buffer, soc, params
-        return buffer
-
-    def _dsweep_window(self, win):
-        """run(): the dispatch sweep's work buffer holds a window of `win` steps (as _sweep_window)."""
-        sw = self._dsweep_desc
-        need = self.L.tmh_battery_sweep_work_bytes(self.n, int(win), int(sw.n_variants))
-        if self._dsweep_work.numel() < need:
-            _torch().cuda.synchronize(self.device)
-            self._dsweep_work = _torch().empty(need, dtype=torch_uint8(), device=self.device)
-            sw.work, sw.work_bytes = self._dsweep_work.data_ptr(), self._dsweep_work.numel()
-            _lib.check(self.L.tmh_set_dispatch_sweep(self._eng, C.byref(sw)))
+        return self._enable_battery("dispatch_sweep", n_steps, interval_s, step0, buffer, soc, params, soc0_wh, quantize,
+                                    n_variants=n_variants)
 
     def dispatch_sweep(self):
         """The sweep's tables in watts and watt-hours: a list of dispatch.to_watts dicts, one per variant."""
@@ -1078,24 +911,6 @@ class BatchedSim:
                 raise ValueError(t["no_trace"])
             if self.step < tb.step0 or self.step + n_steps > tb.step0 + tb.n_steps:
                 raise ValueError(f"steps [{self.step}, +{n_steps}) outside the {t['noun']} [{tb.step0}, +{tb.n_steps})")
-        if self._battery_sweep is not None:   # (likewise; compact=True is allowed)
-            tb = self._battery_sweep
-            if self._series is not None:
-                raise ValueError("the battery sweep and a fleet series are both enabled: one of the two per sim")
-            if trace:
-                raise ValueError("a battery sweep run takes no traces (trace=()): run the batteries over the traces instead "
-                                 "(battery.sweep_from_traces)")
-            if self.step < tb.step0 or self.step + n_steps > tb.step0 + tb.n_steps:
-                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the battery sweep tables [{tb.step0}, +{tb.n_steps})")
-        if self._dispatch_sweep is not None:   # (likewise; compact=True is allowed)
-            tb = self._dispatch_sweep
-            if self._series is not None:
-                raise ValueError("the dispatch sweep and a fleet series are both enabled: one of the two per sim")
-            if trace:
-                raise ValueError("a dispatch sweep run takes no traces (trace=()): run the rules over the traces instead "
-                                 "(dispatch.sweep_from_traces)")
-            if self.step < tb.step0 or self.step + n_steps > tb.step0 + tb.n_steps:
-                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the dispatch sweep tables [{tb.step0}, +{tb.n_steps})")
         if self._battery_fleet is not None:   # (the library refuses each too, window by window)
             if compact:
                 raise ValueError("a battery fleet series cannot run compacted (a compacted tile would mix groups)")
@@ -1118,12 +933,7 @@ class BatchedSim:
         res = out if out is not None else self._alloc(n_steps, trace)
         st = self._stats_struct()
         win = max(1, min(int(window), n_steps))
-        if self._storage is not None or self._battery is not None or self._dispatch is not None or self._schedule is not None:
-            self._storage_window(win)
-        if self._battery_sweep is not None:
-            self._sweep_window(win)
-        if self._dispatch_sweep is not None:
-            self._dsweep_window(win)
+        self._work_window(win)
         if compact and n_steps > win:
             with torch.cuda.device(self.device):
                 self._run_compacted(n_steps, win, st)
