@@ -96,6 +96,7 @@ There is no CPU fallback: the batch mode fails if the engine cannot run.
 """
 from __future__ import annotations
 
+import contextlib
 import csv
 import datetime as dt
 import json
@@ -107,38 +108,49 @@ import click
 logger = logging.getLogger(__name__)
 
 
-def _batch_run(n, start, seconds, seed, precision, fields):
+def _open_sim(n, start, seconds, seed, precision):
+    """The batch mode's engine: n chains from `start` with a horizon of `seconds`, or the refusal without a GPU."""
     from .engine import BatchedSim
     from .params import ModelParams
     import torch
     if not torch.cuda.is_available():
         raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
     params = ModelParams(seed=int(seed))
-    sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
-                     horizon=int(seconds))
-    out = sim.run(int(seconds), trace=fields)
-    torch.cuda.synchronize()
+    return BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
+                      horizon=int(seconds))
+
+
+def _warn_faulted(sim, n, what):
     bad = int((sim.status() != 0).sum())
     if bad:
-        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their values are NaN")
+        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); {what}")
+
+
+@contextlib.contextmanager
+def _refusals():
+    """A ValueError inside the block (a quantity outside its range: the kind's quantize_params and its like) is the
+    command's refusal."""
+    try:
+        yield
+    except ValueError as e:
+        raise click.ClickException(str(e))
+
+
+def _batch_run(n, start, seconds, seed, precision, fields):
+    import torch
+    sim = _open_sim(n, start, seconds, seed, precision)
+    out = sim.run(int(seconds), trace=fields)
+    torch.cuda.synchronize()
+    _warn_faulted(sim, n, "their values are NaN")
     return {k: v.double().cpu().numpy() if v.dtype != torch.uint8 else v.cpu().numpy() for k, v in out.items()}
 
 
 def _fleet_run(n, start, seconds, seed, precision, bin_s):
-    from .engine import BatchedSim
-    from .params import ModelParams
-    import torch
-    if not torch.cuda.is_available():
-        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
-    params = ModelParams(seed=int(seed))
-    sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
-                     horizon=int(seconds))
+    sim = _open_sim(n, start, seconds, seed, precision)
     sim.enable_series(int(seconds))
     sim.run(int(seconds), trace=())
     out = sim.series(bin_s=int(bin_s), mean=True)
-    bad = int((sim.status() != 0).sum())
-    if bad:
-        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); the means are over the ok chains")
+    _warn_faulted(sim, n, "the means are over the ok chains")
     return {k: v[0] for k, v in out.items()}
 
 
@@ -146,24 +158,14 @@ def _table_run(kind, n, start, seconds, seed, precision, interval_s, fleet_bin=N
     """An engine run with the interval table `kind` ("intervals", "registers", "demand", "storage", "battery", "dispatch" or "schedule")
     only: the raw table, its watt / watt-hour arrays and, with fleet_bin (the battery kind), the battery fleet
     series' means per bin of fleet_bin seconds (else None).  enable_kw: the kind's own arguments."""
-    from .engine import BatchedSim
-    from .params import ModelParams
-    import torch
-    if not torch.cuda.is_available():
-        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
-    params = ModelParams(seed=int(seed))
-    sim = BatchedSim(int(n), start, tz=params.site.tz, params=params, precision=precision, device="cuda:0",
-                     horizon=int(seconds))
+    sim = _open_sim(n, start, seconds, seed, precision)
     raw = getattr(sim, "enable_" + kind)(int(seconds), int(interval_s), **enable_kw)
     if fleet_bin:
         sim.enable_battery_fleet(int(seconds))
     sim.run(int(seconds), trace=())
     out = getattr(sim, kind)()
     fleet = {k: v[0] for k, v in sim.battery_fleet(bin_s=int(fleet_bin), mean=True).items()} if fleet_bin else None
-    bad = int((sim.status() != 0).sum())
-    if bad:
-        logger.warning(f"{bad} of {n} chains faulted (reference exceptions); their "
-                       f"{'intervals' if kind == 'intervals' else 'registers'} hold the seconds before the fault")
+    _warn_faulted(sim, n, f"their {'intervals' if kind == 'intervals' else 'registers'} hold the seconds before the fault")
     return raw.cpu().numpy(), out, fleet
 
 
@@ -172,7 +174,9 @@ def _times(start, seconds):
     return [t0 + dt.timedelta(seconds=s) for s in range(int(seconds))]
 
 
-def _need_batch(realtime, batch, name):
+def _batch_mode(verbose, realtime, batch, name):
+    """What every command begins with: the logging level, then the refusal of anything but the offline mode."""
+    logging.basicConfig(level=logging.WARN - 10 * verbose)
     if batch is None:
         try:
             import aio_pika  # noqa: F401
@@ -185,7 +189,16 @@ def _need_batch(realtime, batch, name):
         raise click.ClickException("--batch is an offline mode: combine it with --no-realtime")
 
 
-_common = [
+def _options(*opts):
+    """The options as one decorator; --help lists them in the order given."""
+    def decorate(f):
+        for opt in reversed(opts):
+            f = opt(f)
+        return f
+    return decorate
+
+
+common = _options(
     click.option("--amqp-url", default=os.environ.get("AMQP_URL"), help="AMQP URL (defaults to 'amqp://localhost:5672/')"),
     click.option("--exchange", default=os.environ.get("TMHPVSIM_EXCHANGE", "meter"),
                  help="The name of the exchange (defaults to 'meter')"),
@@ -194,14 +207,7 @@ _common = [
     click.option("--batch", type=int, default=None, help="offline engine mode: number of chains (site x scenario)"),
     click.option("--start", default="2019-09-06T12:00:00", help="batch mode: local wall-clock start time"),
     click.option("--seconds", type=int, default=86400, help="batch mode: seconds to simulate"),
-    click.option("--seed", type=int, default=0x5EED, help="batch mode: keyed Philox seed"),
-]
-
-
-def common(f):
-    for opt in reversed(_common):
-        f = opt(f)
-    return f
+    click.option("--seed", type=int, default=0x5EED, help="batch mode: keyed Philox seed"))
 
 
 @click.group()
@@ -216,8 +222,7 @@ def main():
 @click.option("--all-chains", default=None, help="batch mode: also write every chain's traces to this .npz")
 def pvsim(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, all_chains):
     """Simulated PV + meter + residual load to FILE (CSV, pvsim.py:72-84)."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "pvsim")
+    _batch_mode(verbose, realtime, batch, "pvsim")
     out = _batch_run(batch, start, seconds, seed, precision, ("meter", "pv", "residual"))
     with open(file, mode="w", newline="") as fh:
         w = csv.writer(fh)
@@ -236,8 +241,7 @@ def pvsim(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, se
 @click.option("--out", "out_file", default="-", help="batch mode: JSON-lines message file ('-' = stdout)")
 def metersim(amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, out_file):
     """Meter values as the AMQP messages of metersim.py:38-42, one JSON object per line."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "metersim")
+    _batch_mode(verbose, realtime, batch, "metersim")
     out = _batch_run(batch, start, seconds, seed, "fp64", ("meter",))
     m = out["meter"]
     with click.open_file(out_file, "w") as fh:
@@ -256,8 +260,7 @@ def metersim(amqp_url, exchange, verbose, realtime, batch, start, seconds, seed,
 @click.option("--bin", "bin_s", type=click.IntRange(min=1), default=1, help="seconds per output row (a last partial bin is kept)")
 def fleet(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, bin_s):
     """Fleet means per bin over --batch chains to FILE (CSV; series-only engine run)."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "fleet")
+    _batch_mode(verbose, realtime, batch, "fleet")
     out = _fleet_run(batch, start, seconds, seed, precision, bin_s)
     t0 = dt.datetime.fromisoformat(str(start))
     with open(file, mode="w", newline="") as fh:
@@ -280,13 +283,12 @@ TABLE_CSV = {
     "storage": (("import_wh", "energy_wh_import"), ("export_wh", "energy_wh_export"), ("pv_wh", "energy_wh_pv"),
                 ("meter_wh", "energy_wh_meter"), ("charge_wh", "energy_wh_charge"), ("discharge_wh", "energy_wh_discharge"),
                 ("soc_wh", "soc_wh"), ("n_ok", "n_ok")),
-    "battery": (("import_wh", "energy_wh_import"), ("export_wh", "energy_wh_export"), ("pv_wh", "energy_wh_pv"),
-                ("meter_wh", "energy_wh_meter"), ("charge_wh", "energy_wh_charge"), ("discharge_wh", "energy_wh_discharge"),
-                ("soc_wh", "soc_wh"), ("loss_wh", "energy_wh_loss"), ("n_ok", "n_ok")),
 }
+# (each later kind of the battery family holds the earlier one's columns: battery's loss goes before n_ok)
+TABLE_CSV["battery"] = TABLE_CSV["storage"][:-1] + (("loss_wh", "energy_wh_loss"),) + TABLE_CSV["storage"][-1:]
 TABLE_CSV["dispatch"] = TABLE_CSV["battery"] + (("curtailed_wh", "energy_wh_curtailed"), ("peak_import_w", "peak_w_import"),
                                                 ("peak_export_w", "peak_w_export"))
-
+TABLE_CSV["schedule"] = TABLE_CSV["dispatch"]   # (and the command's own last column, `rule`)
 
 # the battery fleet series' CSV columns: (header, key of battery.fleet_to_watts)
 FLEET_CSV = (("n_ok", "n_ok"), ("meter", "meter"), ("pv", "pv"), ("import_w", "import_w"), ("export_w", "export_w"),
@@ -322,54 +324,51 @@ def _table_command(kind, file, batch, start, seconds, seed, precision, interval_
                + (f" and {len(fl['n_ok'])} fleet rows to {fleet}" if fleet else ""))
 
 
-def table_options(f):
-    for opt in (click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz"),
-                click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
-                             help="seconds per metering interval (a last partial interval is kept)"),
-                click.option("--precision", type=click.Choice(["fp64", "fp32"]), default="fp32", help="batch mode arithmetic")):
-        f = opt(f)
-    return f
+def table_options(precision=True, every="chain's raw table and watt arrays"):
+    """--interval and --all-chains (`every`: what the .npz holds), after --precision unless the command is fp64 only."""
+    all_chains = click.option("--all-chains", default=None, help=f"also write every {every} to this .npz")
+    interval = click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
+                            help="seconds per metering interval (a last partial interval is kept)")
+    if not precision:
+        return _options(all_chains, interval)
+    return _options(click.option("--precision", type=click.Choice(["fp64", "fp32"]), default="fp32", help="batch mode arithmetic"),
+                    interval, all_chains)
 
 
 @main.command()
 @click.argument("file")
 @common
-@table_options
+@table_options()
 def intervals(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, interval_s, all_chains):
     """Interval means of chain 0 over --batch chains to FILE (CSV; interval-metering engine run)."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "intervals")
+    _batch_mode(verbose, realtime, batch, "intervals")
     _table_command("intervals", file, batch, start, seconds, seed, precision, interval_s, all_chains)
 
 
 @main.command()
 @click.argument("file")
 @common
-@table_options
+@table_options()
 def registers(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, interval_s, all_chains):
     """Import / export registers of chain 0 over --batch chains to FILE (CSV; registers-only engine run)."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "registers")
+    _batch_mode(verbose, realtime, batch, "registers")
     _table_command("registers", file, batch, start, seconds, seed, precision, interval_s, all_chains)
 
 
 @main.command()
 @click.argument("file")
 @common
-@table_options
+@table_options()
 def demand(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, precision, interval_s, all_chains):
     """Demand registers of chain 0 over --batch chains to FILE (CSV; demand-only engine run)."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "demand")
+    _batch_mode(verbose, realtime, batch, "demand")
     _table_command("demand", file, batch, start, seconds, seed, precision, interval_s, all_chains)
 
 
 @main.command()
 @click.argument("file")
 @common
-@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
-@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
-              help="seconds per metering interval (a last partial interval is kept)")
+@table_options(precision=False)
 @click.option("--capacity-wh", type=float, required=True, help="battery capacity (Wh)")
 @click.option("--charge-w", type=float, required=True, help="charge power limit (W)")
 @click.option("--discharge-w", type=float, required=True, help="discharge power limit (W)")
@@ -377,8 +376,7 @@ def demand(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, s
 def storage(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
             charge_w, discharge_w, soc0_wh):
     """Battery storage of chain 0 over --batch chains to FILE (CSV; storage-only fp64 engine run)."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "storage")
+    _batch_mode(verbose, realtime, batch, "storage")
     _table_command("storage", file, batch, start, seconds, seed, "fp64", interval_s, all_chains, capacity_wh=capacity_wh,
                    charge_w=charge_w, discharge_w=discharge_w, soc0_wh=soc0_wh)
 
@@ -392,40 +390,6 @@ def _dealt(ctx, param, value):
     return vals
 
 
-def _deal(vals, n):
-    """vals dealt to n chains round-robin."""
-    return [vals[i % len(vals)] for i in range(int(n))]
-
-
-@main.command()
-@click.argument("file")
-@common
-@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
-@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
-              help="seconds per metering interval (a last partial interval is kept)")
-@click.option("--capacity-wh", callback=_dealt, required=True, help="battery capacity (Wh); a list is dealt to the chains")
-@click.option("--charge-w", callback=_dealt, required=True, help="charge power limit at the meter side (W)")
-@click.option("--discharge-w", callback=_dealt, required=True, help="discharge power limit at the meter side (W)")
-@click.option("--charge-eff", callback=_dealt, default="1.0", help="charge efficiency in [0.5, 1]")
-@click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]")
-@click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)")
-@click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)")
-@click.option("--fleet", default=None, help="also write the battery fleet series' means per bin to this CSV")
-@click.option("--bin", "bin_s", type=click.IntRange(min=1), default=1, help="--fleet: seconds per row (a last partial bin is kept)")
-def battery(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
-            charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh, fleet, bin_s):
-    """Battery storage with losses of chain 0 over --batch chains to FILE (CSV; battery-only fp64 engine run)."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "battery")
-    try:
-        _table_command("battery", file, batch, start, seconds, seed, "fp64", interval_s, all_chains, fleet=fleet, bin_s=bin_s,
-                       **{k: _deal(v, batch) for k, v in dict(
-                           capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
-                           discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh).items()})
-    except ValueError as e:   # (a quantity outside its range: battery.quantize_params)
-        raise click.ClickException(str(e))
-
-
 def _dealt_limit(ctx, param, value):
     """--feed-in-limit-w: one value or a comma-separated list, each a number of watts or `none` (no limit)."""
     if value is None:
@@ -436,36 +400,60 @@ def _dealt_limit(ctx, param, value):
         raise click.BadParameter("a number, `none`, or a comma-separated list of them")
 
 
+def battery_options(a_list_is):
+    """The battery's seven options; a_list_is: what a command does with a comma-separated list."""
+    return _options(
+        click.option("--capacity-wh", callback=_dealt, required=True, help=f"battery capacity (Wh); a list is {a_list_is}"),
+        click.option("--charge-w", callback=_dealt, required=True, help="charge power limit at the meter side (W)"),
+        click.option("--discharge-w", callback=_dealt, required=True, help="discharge power limit at the meter side (W)"),
+        click.option("--charge-eff", callback=_dealt, default="1.0", help="charge efficiency in [0.5, 1]"),
+        click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]"),
+        click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)"),
+        click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)"))
+
+
+dispatch_options = _options(
+    click.option("--charge-above-w", callback=_dealt, default="0.0", help="charge only from the surplus above this (W)"),
+    click.option("--discharge-above-w", callback=_dealt, default="0.0", help="discharge only into the deficit above this (W)"),
+    click.option("--feed-in-limit-w", callback=_dealt_limit, default=None, help="feed-in limit (W); `none`: no limit (the default)"))
+
+
+def _deal(vals, n):
+    """vals dealt to n chains round-robin."""
+    return [vals[i % len(vals)] for i in range(int(n))]
+
+
+def _dealt_table_command(kind, file, batch, start, seconds, seed, interval_s, all_chains, lists, **kw):
+    """_table_command for the fp64 kinds whose option `lists` (a list per battery or dispatch option) are dealt to the
+    chains; a quantity outside its range (the kind's quantize_params) is the command's refusal."""
+    with _refusals():
+        _table_command(kind, file, batch, start, seconds, seed, "fp64", interval_s, all_chains,
+                       **{k: _deal(v, batch) for k, v in lists.items()}, **kw)
+
+
 @main.command()
 @click.argument("file")
 @common
-@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
-@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
-              help="seconds per metering interval (a last partial interval is kept)")
-@click.option("--capacity-wh", callback=_dealt, required=True, help="battery capacity (Wh); a list is dealt to the chains")
-@click.option("--charge-w", callback=_dealt, required=True, help="charge power limit at the meter side (W)")
-@click.option("--discharge-w", callback=_dealt, required=True, help="discharge power limit at the meter side (W)")
-@click.option("--charge-eff", callback=_dealt, default="1.0", help="charge efficiency in [0.5, 1]")
-@click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]")
-@click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)")
-@click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)")
-@click.option("--charge-above-w", callback=_dealt, default="0.0", help="charge only from the surplus above this (W)")
-@click.option("--discharge-above-w", callback=_dealt, default="0.0", help="discharge only into the deficit above this (W)")
-@click.option("--feed-in-limit-w", callback=_dealt_limit, default=None, help="feed-in limit (W); `none`: no limit (the default)")
-def dispatch(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
-             charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh, charge_above_w, discharge_above_w,
-             feed_in_limit_w):
+@table_options(precision=False)
+@battery_options("dealt to the chains")
+@click.option("--fleet", default=None, help="also write the battery fleet series' means per bin to this CSV")
+@click.option("--bin", "bin_s", type=click.IntRange(min=1), default=1, help="--fleet: seconds per row (a last partial bin is kept)")
+def battery(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, fleet, bin_s, **lists):
+    """Battery storage with losses of chain 0 over --batch chains to FILE (CSV; battery-only fp64 engine run)."""
+    _batch_mode(verbose, realtime, batch, "battery")
+    _dealt_table_command("battery", file, batch, start, seconds, seed, interval_s, all_chains, lists, fleet=fleet, bin_s=bin_s)
+
+
+@main.command()
+@click.argument("file")
+@common
+@table_options(precision=False)
+@battery_options("dealt to the chains")
+@dispatch_options
+def dispatch(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, **lists):
     """Battery dispatch (thresholds, a feed-in limit) of chain 0 over --batch chains to FILE (CSV; fp64 engine run)."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "dispatch")
-    try:
-        _table_command("dispatch", file, batch, start, seconds, seed, "fp64", interval_s, all_chains,
-                       **{k: _deal(v, batch) for k, v in dict(
-                           capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
-                           discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh, charge_above_w=charge_above_w,
-                           discharge_above_w=discharge_above_w, feed_in_limit_w=feed_in_limit_w).items()})
-    except ValueError as e:   # (a quantity outside its range: dispatch.quantize_params)
-        raise click.ClickException(str(e))
+    _batch_mode(verbose, realtime, batch, "dispatch")
+    _dealt_table_command("dispatch", file, batch, start, seconds, seed, interval_s, all_chains, lists)
 
 
 def parse_period(text):
@@ -494,45 +482,28 @@ def _period(ctx, param, value):
         raise click.BadParameter(str(e))
 
 
-TABLE_CSV["schedule"] = TABLE_CSV["dispatch"]
-
-
 @main.command()
 @click.argument("file")
 @common
-@click.option("--all-chains", default=None, help="also write every chain's raw table and watt arrays to this .npz")
-@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
-              help="seconds per metering interval (a last partial interval is kept)")
-@click.option("--capacity-wh", callback=_dealt, required=True, help="battery capacity (Wh); a list is dealt to the chains")
-@click.option("--charge-w", callback=_dealt, required=True, help="charge power limit at the meter side (W)")
-@click.option("--discharge-w", callback=_dealt, required=True, help="discharge power limit at the meter side (W)")
-@click.option("--charge-eff", callback=_dealt, default="1.0", help="charge efficiency in [0.5, 1]")
-@click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]")
-@click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)")
-@click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)")
+@table_options(precision=False)
+@battery_options("dealt to the chains")
 @click.option("--period", multiple=True, required=True, callback=_period,
               help="HH:MM,CHARGE_ABOVE,DISCHARGE_ABOVE,LIMIT|none,GRID_CHARGE: a rule (watts) that starts daily at that local "
                    "time; 1 to 8 of them")
-def schedule(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
-             charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh, period):
+def schedule(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, period, **lists):
     """Scheduled dispatch (a daily tariff of rules, grid charging) of chain 0 over --batch chains to FILE (CSV with the
     rule of each interval; fp64 engine run)."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "schedule")
+    _batch_mode(verbose, realtime, batch, "schedule")
     from . import schedule as S
     from .params import ModelParams
     if not 1 <= len(period) <= S.RULES_MAX:
         raise click.ClickException(f"schedule: {len(period)} --period options outside [1, {S.RULES_MAX}]")
-    try:
+    with _refusals():   # (two periods at one time: schedule.daily)
         rule_of_interval = S.daily(start, ModelParams(seed=int(seed)).site.tz, int(seconds), int(interval_s),
                                    [(s, r) for r, (s, _) in enumerate(period)])
-        _table_command("schedule", file, batch, start, seconds, seed, "fp64", interval_s, all_chains,
-                       csv_extra={"rule": rule_of_interval}, rules=[rule for _, rule in period], rule_of_interval=rule_of_interval,
-                       **{k: _deal(v, batch) for k, v in dict(
-                           capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
-                           discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh).items()})
-    except ValueError as e:   # (a quantity outside its range, two periods at one time: schedule.quantize_params, daily)
-        raise click.ClickException(str(e))
+    _dealt_table_command("schedule", file, batch, start, seconds, seed, interval_s, all_chains, lists,
+                         csv_extra={"rule": rule_of_interval}, rules=[rule for _, rule in period],
+                         rule_of_interval=rule_of_interval)
 
 
 SWEEP_OPTIONS = ("capacity_wh", "charge_w", "discharge_w", "charge_eff", "discharge_eff", "standby_w", "soc0_wh")
@@ -541,6 +512,22 @@ SWEEP_OPTIONS = ("capacity_wh", "charge_w", "discharge_w", "charge_eff", "discha
 SWEEP_TOTALS = (("import_wh", "energy_wh_import"), ("export_wh", "energy_wh_export"), ("charge_wh", "energy_wh_charge"),
                 ("discharge_wh", "energy_wh_discharge"), ("loss_wh", "energy_wh_loss"))
 SWEEP_RATIOS = ("self_consumption", "self_sufficiency", "full_cycles")
+
+DISPATCH_SWEEP_OPTIONS = SWEEP_OPTIONS + ("charge_above_w", "discharge_above_w", "feed_in_limit_w")
+# the dispatch-sweep CSV: a row per variant -- its parameters (feed_in_limit_w `none` without a limit), then (header,
+# key of dispatch.sweep_summary) fleet totals, the largest peaks of any chain (W) and ratios
+DISPATCH_SWEEP_TOTALS = SWEEP_TOTALS + (("curtailed_wh", "energy_wh_curtailed"), ("peak_import_w", "peak_w_import"),
+                                        ("peak_export_w", "peak_w_export"))
+DISPATCH_SWEEP_RATIOS = SWEEP_RATIOS + ("curtailed_share",)
+
+# per sweep command: the BatchedSim method that enables its table and the attribute with the quantized parameters, the
+# module whose sweep_summary(fleet=True) gives the CSV's rows, and the CSV's columns
+SWEEPS = {
+    "battery-sweep": dict(enable="enable_battery_sweep", params="battery_params", module="battery",
+                          options=SWEEP_OPTIONS, totals=SWEEP_TOTALS, ratios=SWEEP_RATIOS),
+    "dispatch-sweep": dict(enable="enable_dispatch_sweep", params="dispatch_params", module="dispatch",
+                           options=DISPATCH_SWEEP_OPTIONS, totals=DISPATCH_SWEEP_TOTALS, ratios=DISPATCH_SWEEP_RATIOS),
+}
 
 
 def _variant_lists(command, lists):
@@ -563,137 +550,75 @@ def dispatch_sweep_lists(**lists):
     return _variant_lists("dispatch-sweep", lists)
 
 
-def sweep_fleet_rows(raw, interval_s, params):
-    """A dict per variant of the fleet's totals (SWEEP_TOTALS, Wh over all the chains) and ratios (SWEEP_RATIOS, of
-    the fleet's integer sums) from a raw sweep table [K, n_iv, 10, n]: battery.sweep_summary(fleet=True)."""
-    from . import battery as B
-    fleet = B.sweep_summary(raw, interval_s, params, fleet=True)
+def _fleet_rows(command, raw, interval_s, params):
+    from importlib import import_module
+    fleet = import_module("." + SWEEPS[command]["module"], __package__).sweep_summary(raw, interval_s, params, fleet=True)
     return [{k: float(v[i]) for k, v in fleet.items()} for i in range(len(raw))]
 
 
-@main.command("battery-sweep")
-@click.argument("file")
-@common
-@click.option("--all-chains", default=None, help="also write every variant's raw table of every chain to this .npz")
-@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
-              help="seconds per metering interval (a last partial interval is kept)")
-@click.option("--capacity-wh", callback=_dealt, required=True, help="battery capacity (Wh); a list is one value per variant")
-@click.option("--charge-w", callback=_dealt, required=True, help="charge power limit at the meter side (W)")
-@click.option("--discharge-w", callback=_dealt, required=True, help="discharge power limit at the meter side (W)")
-@click.option("--charge-eff", callback=_dealt, default="1.0", help="charge efficiency in [0.5, 1]")
-@click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]")
-@click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)")
-@click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)")
-def battery_sweep(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
-                  charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh):
-    """Every chain behind each of K candidate batteries in one fp64 engine run: a CSV row per variant to FILE."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "battery-sweep")
-    k, opts = sweep_lists(capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
-                          discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh)
-    from .engine import BatchedSim
-    from .params import ModelParams
-    import torch
-    if not torch.cuda.is_available():
-        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
-    mp = ModelParams(seed=int(seed))
-    sim = BatchedSim(int(batch), start, tz=mp.site.tz, params=mp, precision="fp64", device="cuda:0", horizon=int(seconds))
-    try:
-        raw = sim.enable_battery_sweep(int(seconds), int(interval_s), n_variants=k, **opts)
-    except ValueError as e:   # (a quantity outside its range, too many variants: battery.quantize_sweep_params)
-        raise click.ClickException(str(e))
-    sim.run(int(seconds), trace=())
-    torch.cuda.synchronize()
-    raw, params = raw.cpu().numpy(), sim.battery_params.cpu().numpy()
-    bad = int((sim.status() != 0).sum())
-    if bad:
-        logger.warning(f"{bad} of {batch} chains faulted (reference exceptions); their tables hold the seconds before the fault")
-    rows = sweep_fleet_rows(raw, interval_s, params)
-    with open(file, "w") as f:
-        f.write(",".join(("variant",) + SWEEP_OPTIONS + tuple(h for h, _ in SWEEP_TOTALS) + SWEEP_RATIOS) + "\n")
-        for v, row in enumerate(rows):
-            f.write(",".join([str(v)] + [repr(float(opts[o][v])) for o in SWEEP_OPTIONS] + [repr(row[key]) for _, key in SWEEP_TOTALS]
-                             + [repr(row[key]) for key in SWEEP_RATIOS]) + "\n")
-    if all_chains:
-        import numpy as np
-        np.savez(all_chains, raw=raw, params=params, soc=sim.soc.cpu().numpy(), interval_s=interval_s)
-    click.echo(f"wrote {k} rows to {file}" + (f" and {k} x {batch} chains to {all_chains}" if all_chains else ""))
-
-
-DISPATCH_SWEEP_OPTIONS = SWEEP_OPTIONS + ("charge_above_w", "discharge_above_w", "feed_in_limit_w")
-# the dispatch-sweep CSV: a row per variant -- its parameters (feed_in_limit_w `none` without a limit), then (header,
-# key of dispatch.sweep_summary) fleet totals, the largest peaks of any chain (W) and ratios
-DISPATCH_SWEEP_TOTALS = SWEEP_TOTALS + (("curtailed_wh", "energy_wh_curtailed"), ("peak_import_w", "peak_w_import"),
-                                        ("peak_export_w", "peak_w_export"))
-DISPATCH_SWEEP_RATIOS = SWEEP_RATIOS + ("curtailed_share",)
+def sweep_fleet_rows(raw, interval_s, params):
+    """A dict per variant of the fleet's totals (SWEEP_TOTALS, Wh over all the chains) and ratios (SWEEP_RATIOS, of
+    the fleet's integer sums) from a raw sweep table [K, n_iv, 10, n]: battery.sweep_summary(fleet=True)."""
+    return _fleet_rows("battery-sweep", raw, interval_s, params)
 
 
 def dispatch_sweep_fleet_rows(raw, interval_s, params):
     """A dict per variant of the fleet's totals and ratios (DISPATCH_SWEEP_TOTALS, DISPATCH_SWEEP_RATIOS) from a raw
     dispatch sweep table [K, n_iv, 13, n]: dispatch.sweep_summary(fleet=True)."""
-    from . import dispatch as D
-    fleet = D.sweep_summary(raw, interval_s, params, fleet=True)
-    return [{k: float(v[i]) for k, v in fleet.items()} for i in range(len(raw))]
+    return _fleet_rows("dispatch-sweep", raw, interval_s, params)
 
 
-@main.command("dispatch-sweep")
-@click.argument("file")
-@common
-@click.option("--all-chains", default=None, help="also write every variant's raw table of every chain to this .npz")
-@click.option("--interval", "interval_s", type=click.IntRange(min=1), default=900,
-              help="seconds per metering interval (a last partial interval is kept)")
-@click.option("--capacity-wh", callback=_dealt, required=True, help="battery capacity (Wh); a list is one value per variant")
-@click.option("--charge-w", callback=_dealt, required=True, help="charge power limit at the meter side (W)")
-@click.option("--discharge-w", callback=_dealt, required=True, help="discharge power limit at the meter side (W)")
-@click.option("--charge-eff", callback=_dealt, default="1.0", help="charge efficiency in [0.5, 1]")
-@click.option("--discharge-eff", callback=_dealt, default="1.0", help="discharge efficiency in [0.5, 1]")
-@click.option("--standby-w", callback=_dealt, default="0.0", help="standby drain (W)")
-@click.option("--soc0-wh", callback=_dealt, default="0.0", help="state of charge at the start (Wh)")
-@click.option("--charge-above-w", callback=_dealt, default="0.0", help="charge only from the surplus above this (W)")
-@click.option("--discharge-above-w", callback=_dealt, default="0.0", help="discharge only into the deficit above this (W)")
-@click.option("--feed-in-limit-w", callback=_dealt_limit, default=None, help="feed-in limit (W); `none`: no limit (the default)")
-def dispatch_sweep(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, capacity_wh,
-                   charge_w, discharge_w, charge_eff, discharge_eff, standby_w, soc0_wh, charge_above_w, discharge_above_w,
-                   feed_in_limit_w):
-    """Every chain under each of K dispatch rules (battery, thresholds, feed-in limit) in one fp64 engine run: a CSV
-    row per variant to FILE."""
-    logging.basicConfig(level=logging.WARN - 10 * verbose)
-    _need_batch(realtime, batch, "dispatch-sweep")
-    k, opts = dispatch_sweep_lists(capacity_wh=capacity_wh, charge_w=charge_w, discharge_w=discharge_w, charge_eff=charge_eff,
-                                   discharge_eff=discharge_eff, standby_w=standby_w, soc0_wh=soc0_wh,
-                                   charge_above_w=charge_above_w, discharge_above_w=discharge_above_w,
-                                   feed_in_limit_w=feed_in_limit_w)
-    from .engine import BatchedSim
-    from .params import ModelParams
+def _sweep_command(command, file, batch, start, seconds, seed, interval_s, all_chains, lists):
+    """The `battery-sweep` and `dispatch-sweep` commands (SWEEPS): a row per variant to FILE, every variant's raw table
+    to the .npz.  lists: a list per option of the command, in any order."""
+    sweep = SWEEPS[command]
+    k, opts = _variant_lists(command, {o: lists[o] for o in sweep["options"]})
+    sim = _open_sim(batch, start, seconds, seed, "fp64")
     import torch
-    if not torch.cuda.is_available():
-        raise click.ClickException("--batch runs on the MI355X engine and no GPU is visible (there is no CPU path)")
-    mp = ModelParams(seed=int(seed))
-    sim = BatchedSim(int(batch), start, tz=mp.site.tz, params=mp, precision="fp64", device="cuda:0", horizon=int(seconds))
-    try:
-        raw = sim.enable_dispatch_sweep(int(seconds), int(interval_s), n_variants=k, **opts)
-    except ValueError as e:   # (a quantity outside its range, too many variants: dispatch.quantize_sweep_params)
-        raise click.ClickException(str(e))
+    with _refusals():   # (also too many variants: the module's quantize_sweep_params)
+        raw = getattr(sim, sweep["enable"])(int(seconds), int(interval_s), n_variants=k, **opts)
     sim.run(int(seconds), trace=())
     torch.cuda.synchronize()
-    raw, params = raw.cpu().numpy(), sim.dispatch_params.cpu().numpy()
-    bad = int((sim.status() != 0).sum())
-    if bad:
-        logger.warning(f"{bad} of {batch} chains faulted (reference exceptions); their tables hold the seconds before the fault")
-    rows = dispatch_sweep_fleet_rows(raw, interval_s, params)
-    cell = lambda x: "none" if x is None else repr(float(x))
+    raw, params = raw.cpu().numpy(), getattr(sim, sweep["params"]).cpu().numpy()
+    _warn_faulted(sim, batch, "their tables hold the seconds before the fault")
+    rows = _fleet_rows(command, raw, interval_s, params)
+    cell = lambda x: "none" if x is None else repr(float(x))   # (a feed-in limit)
     with open(file, "w") as f:
-        f.write(",".join(("variant",) + DISPATCH_SWEEP_OPTIONS + tuple(h for h, _ in DISPATCH_SWEEP_TOTALS)
-                         + DISPATCH_SWEEP_RATIOS) + "\n")
+        f.write(",".join(("variant",) + sweep["options"] + tuple(h for h, _ in sweep["totals"]) + sweep["ratios"]) + "\n")
         for v, row in enumerate(rows):
-            f.write(",".join([str(v)] + [cell(opts[o][v]) for o in DISPATCH_SWEEP_OPTIONS]
-                             + [repr(row[key]) for _, key in DISPATCH_SWEEP_TOTALS]
-                             + [repr(row[key]) for key in DISPATCH_SWEEP_RATIOS]) + "\n")
+            f.write(",".join([str(v)] + [cell(opts[o][v]) for o in sweep["options"]]
+                             + [repr(row[key]) for _, key in sweep["totals"]]
+                             + [repr(row[key]) for key in sweep["ratios"]]) + "\n")
     if all_chains:
         import numpy as np
         np.savez(all_chains, raw=raw, params=params, soc=sim.soc.cpu().numpy(), interval_s=interval_s)
     click.echo(f"wrote {k} rows to {file}" + (f" and {k} x {batch} chains to {all_chains}" if all_chains else ""))
 
 
+@main.command("battery-sweep")
+@click.argument("file")
+@common
+@table_options(precision=False, every="variant's raw table of every chain")
+@battery_options("one value per variant")
+def battery_sweep(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, **lists):
+    """Every chain behind each of K candidate batteries in one fp64 engine run: a CSV row per variant to FILE."""
+    _batch_mode(verbose, realtime, batch, "battery-sweep")
+    _sweep_command("battery-sweep", file, batch, start, seconds, seed, interval_s, all_chains, lists)
+
+
+@main.command("dispatch-sweep")
+@click.argument("file")
+@common
+@table_options(precision=False, every="variant's raw table of every chain")
+@battery_options("one value per variant")
+@dispatch_options
+def dispatch_sweep(file, amqp_url, exchange, verbose, realtime, batch, start, seconds, seed, interval_s, all_chains, **lists):
+    """Every chain under each of K dispatch rules (battery, thresholds, feed-in limit) in one fp64 engine run: a CSV
+    row per variant to FILE."""
+    _batch_mode(verbose, realtime, batch, "dispatch-sweep")
+    _sweep_command("dispatch-sweep", file, batch, start, seconds, seed, interval_s, all_chains, lists)
+
+
 if __name__ == "__main__":
     main()
+
