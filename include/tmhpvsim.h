@@ -514,6 +514,37 @@ typedef struct tmh_schedule {
     uint32_t n_rules;         /* 1 .. TMH_SCHEDULE_RULES_MAX */
 } tmh_schedule;
 
+/* The dispatch fleet series: the battery fleet series (TMH_BATTERY_FLEET_COLS above) behind battery dispatch or
+ * scheduled dispatch -- what the whole batch draws, feeds in, curtails and stores second by second under a feed-in
+ * limit, thresholds, a tariff or grid charging.  The coincidence across chains within an interval is what no
+ * table holds: the sum of the chains' peaks (columns 11 and 12) is not the fleet's peak.  An output of the kind
+ * beside its interval table (never instead of it), filled by the replay pass of tmh_set_dispatch or of
+ * tmh_set_schedule, whichever is set.  The descriptor is tmh_series with TMH_DISPATCH_FLEET_COLS columns per row:
+ * sum is device int64 [n_groups][n_steps][9], accumulated over calls (the caller zero-initialises); the ok rule
+ * and the groups are the fleet series' (chain i of a call in group i / group_chains, 0: one group, else a
+ * multiple of 512).  Row s of a group holds, for step step0 + s, over the group's chains that are ok at that step:
+ *   [0..3] tmh_series' columns (sum of q(pv), sum of q(meter), n_ok, covered), bit for bit
+ *   [4] sum of import_b     what the fleet draws from the grid (grid charging included)
+ *   [5] sum of export_b     what it feeds in, after the limit
+ *   [6] sum of x'           the state of charge after the second, in 2^-12 W s
+ *   [7] sum of max(b, 0)    what the batteries take at the meter side
+ *   [8] sum of curtailed    what the inverters throw away above the limit
+ * with import_b, export_b, b, x' and curtailed exactly tmh_dispatch's per-second quantities; under a schedule
+ * they are tmh_schedule's, with the rule of the second's own interval.  For every row [4] - [5] - [8] == [1] - [0]
+ * + sum of b, so the fleet's net battery power follows from the row and its discharging power is [7] - sum of b
+ * >= 0; columns 4-8 are >= 0; [6] <= the sum of C over the group; where every chain of the group has the same
+ * limit L, [5] <= n_ok * L.  A chain that is not ok at a second adds nothing to that row, its stored energy
+ * included.  With Tc = Td = 0 and L = 2^27 columns 0-7 are the battery fleet series' and column 8 is 0.
+ * Bounds of the kernels' 32-lane, 32-bit partial sums: under plain dispatch b lies between 0 and d, so the battery
+ * fleet series' bounds hold (max(b, 0) <= q(pv) < 2^26, import_b < 2^27), and export_b + curtailed = the surplus
+ * <= max(d, 0) < 2^26.  A grid-charging rule of a schedule breaks two of them: b goes up to Pc = 2^27 -- 32 lanes
+ * of exactly 2^27 are 2^32 -- and import_b up to 2^26 + 2^27.  Under a schedule these two are therefore summed
+ * over 16 lanes in 32 bits (16 x 3 * 2^26 < 2^32) and the two 16-lane sums added in 33 bits; export_b and
+ * curtailed stay below 2^26 (the surplus r = d - b <= d), x' < 2^40 goes as two 20-bit halves as before.  Plain
+ * dispatch's replay keeps the 32-lane sums.  Integer sums: the bits do not depend on block, wave, window, batch
+ * or pipelining order and equal a sequential loop over the traces; several engines may add into one buffer. */
+#define TMH_DISPATCH_FLEET_COLS 9
+
 int tmh_abi_version(void);
 const char* tmh_last_error(void);
 /* TMH_SERIES_FRAC_BITS and TMH_SERIES_MAX_W as the library was built with them */
@@ -769,6 +800,19 @@ int tmh_set_dispatch_sweep(struct tmh_engine* eng, const tmh_dispatch_sweep* sw)
  * kind set too, in either order; tmh_set_series or tmh_set_battery_fleet set; per-chain sites (tmh_set_sites).
  * The parameters' and the array's values are not read on the host: the kernels clamp them. */
 int tmh_set_schedule(struct tmh_engine* eng, const tmh_schedule* sc);
+/* The dispatch fleet series (TMH_DISPATCH_FLEET_COLS above): every later expansion of this engine with battery
+ * dispatch or the schedule set adds its window's rows to fleet->sum, in the kind's replay pass, beside the kind's
+ * table; NULL switches it off.  The kind's table and soc are exactly what they are without the series.  A setter
+ * like tmh_set_battery_fleet: the struct is copied, the buffer must outlive the launches, the rows are final after
+ * the TMH_EXPAND_KERNEL half.  Refused here (TMH_E_INVAL, the messages name "dispatch fleet series"):
+ * tmh_set_battery_fleet's bad-struct cases; an fp32 engine.  Refused at a step / expansion call or a walk of that
+ * window, before any launch and naming "dispatch fleet series": neither tmh_set_dispatch nor tmh_set_schedule set;
+ * any other table kind set; tmh_set_series or tmh_set_battery_fleet set too; chain ids set (compaction); per-chain
+ * sites (tmh_set_sites: one feeder is one site); a window not inside [step0, step0 + n_steps); n_groups *
+ * group_chains < n_chains.  Everything the kind's step refuses without the series stays refused in its words
+ * (tmh_set_battery_fleet beside dispatch or the schedule included).  Statistics and the histogram are accumulated
+ * beside both when tmh_stats gives them. */
+int tmh_set_dispatch_fleet(struct tmh_engine* eng, const tmh_series* fleet);
 /* Tests only: the fp32 guard-band records (chain, block) the last expansion on
  * `scratch` (laid out for n_chains x n_steps) appended; a synchronous copy from the
  * device (the caller has synchronised the expansion's stream).  Negative: TMH_E_*. */
@@ -883,7 +927,9 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * TMH_OUT_BATTERY (the battery kind, likewise), TMH_OUT_BATTERY_FLEET (the battery kind with its fleet
  * series: the replay pass that fills both), TMH_OUT_BATTERY_SWEEP (the battery sweep),
  * TMH_OUT_DISPATCH (battery dispatch: its replay pass, with or without statistics),
- * TMH_OUT_DISPATCH_SWEEP (the dispatch sweep), TMH_OUT_SCHEDULE (scheduled dispatch: its replay pass), plus
+ * TMH_OUT_DISPATCH_SWEEP (the dispatch sweep), TMH_OUT_SCHEDULE (scheduled dispatch: its replay pass),
+ * TMH_OUT_DISPATCH_FLEET and TMH_OUT_SCHEDULE_FLEET (battery dispatch / the schedule with the dispatch fleet
+ * series: the replay pass that fills both), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
@@ -900,6 +946,8 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
 #define TMH_OUT_DISPATCH 11
 #define TMH_OUT_DISPATCH_SWEEP 12
 #define TMH_OUT_SCHEDULE 13
+#define TMH_OUT_DISPATCH_FLEET 14
+#define TMH_OUT_SCHEDULE_FLEET 15
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
 int tmh_engine_last_expand(const struct tmh_engine* eng);

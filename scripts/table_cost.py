@@ -4,6 +4,7 @@ kernel) of the statistics-only expansion and of the expansions with a table, sam
 same window, same process, the runs alternating.
 
     python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet|battery_sweep|dispatch|dispatch_sweep|schedule
+                                        |dispatch_fleet|schedule_fleet
                                  [--variants 5] [--rules 1] [--chains 65536] [--steps 86400]
                                  [--interval 900] [--rounds 5] [--precision fp32]
                                  [--start "2019-09-05 00:00:00"] [--out FILE.json]
@@ -48,6 +49,12 @@ The runs of a kind:
              thresholds and the limit halved; the script checks the schedule table's identities, that the grid rule's
              intervals never discharge, the hold's neither charge nor discharge, and that the table differs from the
              dispatch kind's.
+  dispatch_fleet: OUT_DISPATCH and OUT_DISPATCH_FLEET, dispatch's setting -- battery dispatch alone and with the
+             dispatch fleet series (BatchedSim.enable_dispatch_fleet, one group); the two tables and soc are equal, the
+             rows summed over each interval are the table summed over the chains (columns 0-5, 7 and 8 against 0-5, 6
+             and 10), and the fleet curtails.
+  schedule_fleet: OUT_SCHEDULE and OUT_SCHEDULE_FLEET, schedule's setting (--rules 1|4) -- the schedule alone and with
+             the dispatch fleet series; dispatch_fleet's checks.
 Every run but the sweeps' has the same statistics beside its table.  The three launches of a battery-family table (map
 pass, scan, replay pass) are timed separately as well (TMH_K_STORAGE_*), inside the TMH_K_EXPAND span.  The script
 checks each run's variant and launch counts, the kind's identities (on the warm-up round's tables), that the
@@ -79,11 +86,14 @@ RUNS = {
     "dispatch": (("battery", "battery"), ("dispatch", "dispatch")),
     "dispatch_sweep": (("dispatch", "dispatch"), ("dispatch_sweep", "dispatch_sweep")),
     "schedule": (("dispatch", "dispatch"), ("schedule", "schedule")),
+    "dispatch_fleet": (("dispatch", "dispatch"), ("dispatch_fleet", "dispatch_fleet")),
+    "schedule_fleet": (("schedule", "schedule"), ("schedule_fleet", "schedule_fleet")),
 }
 # the tables of the battery family (fp64 engines) and their three launches: _lib.K_STORAGE_<PART>
-FAMILY = ("storage", "battery", "battery_fleet", "battery_sweep", "dispatch", "dispatch_sweep", "schedule")
+FAMILY = ("storage", "battery", "battery_fleet", "battery_sweep", "dispatch", "dispatch_sweep", "schedule", "dispatch_fleet",
+          "schedule_fleet")
 PARTS = ("map", "scan", "replay")
-SHORT = {"stats_only": "stats", "battery_fleet": "fleet"}   # labels as the ratios' keys name them
+SHORT = {"stats_only": "stats", "battery_fleet": "fleet", "dispatch_fleet": "fleet", "schedule_fleet": "fleet"}   # labels as the ratios' keys name them
 
 
 def run_once(a, mp, stats, table, kw):
@@ -93,12 +103,13 @@ def run_once(a, mp, stats, table, kw):
     import torch
     from tmhpvsim_amd import _lib
     from tmhpvsim_amd.engine import BatchedSim
-    fleet = table == "battery_fleet"
+    fleet = table is not None and table.endswith("_fleet")   # the kind's table with its fleet series beside it
+    base = table[:-len("_fleet")] if fleet else table
     sim = BatchedSim(a.chains, a.start, tz="Europe/Berlin", params=mp, precision=a.precision, device="cuda:0", horizon=a.steps)
     if stats:
         sim.enable_stats()
-    raw = getattr(sim, "enable_" + ("battery" if fleet else table))(a.steps, a.interval, **kw) if table else None
-    fleet_rows = sim.enable_battery_fleet(a.steps) if fleet else None
+    raw = getattr(sim, "enable_" + base)(a.steps, a.interval, **kw) if table else None
+    fleet_rows = getattr(sim, "enable_battery_fleet" if base == "battery" else "enable_dispatch_fleet")(a.steps) if fleet else None
     _lib.check(sim.L.tmh_profile_enable(sim._eng, 1))
     sim.run(a.steps, trace=(), window=a.steps)
     torch.cuda.synchronize()
@@ -277,8 +288,8 @@ def dispatch_sweep_kind(a, battery, lossy):
                 derived=sweep_yardstick(K, "dispatch", "dispatch_sweep"))
 
 
-def schedule_kind(a, battery, lossy):
-    """The dispatch kind and scheduled dispatch (a.rules rule sets) over the same batteries."""
+def schedule_rules(a):
+    """(dispatch's rule, the schedule's a.rules rule sets, the rule of each interval) of --rules 1 or 4."""
     import numpy as np
     rule = dict(charge_above_w=a.charge_above_w, discharge_above_w=a.discharge_above_w, feed_in_limit_w=a.feed_in_limit_w)
     n_iv = -(-a.steps // a.interval)
@@ -292,7 +303,14 @@ def schedule_kind(a, battery, lossy):
                       feed_in_limit_w=a.feed_in_limit_w / 2, grid_charge_w=0.0)]
         roi = ((np.arange(n_iv) * a.interval // 3600) % 4).astype(np.uint8)
     else:
-        sys.exit("--kind schedule: --rules 1 or 4")
+        sys.exit("--kind schedule, schedule_fleet: --rules 1 or 4")
+    return rule, rules, roi
+
+
+def schedule_kind(a, battery, lossy):
+    """The dispatch kind and scheduled dispatch (a.rules rule sets) over the same batteries."""
+    import numpy as np
+    rule, rules, roi = schedule_rules(a)
 
     def check(dp, sc):   # the warm-up round's tables
         import torch
@@ -321,8 +339,43 @@ def schedule_kind(a, battery, lossy):
                 keys=dict(modules=a.modules, battery=lossy, n_rules=a.rules, rules=rules, rule_of_interval=roi.tolist()))
 
 
+def fleet_check(interval_s):
+    """The dispatch fleet series' check on the warm-up round (the kind alone, the kind with the series): the same table
+    and soc, the rows summed over each interval the table summed over the chains, and a fleet that curtails."""
+    def check(alone, both):
+        import torch
+        t, fl = both.raw, both.fleet_rows
+        assert torch.equal(alone.raw, t) and torch.equal(alone.soc, both.soc) and bool((fl[..., 4:] >= 0).all())
+        if fl.shape[1] % interval_s == 0:
+            per = fl[0].reshape(-1, interval_s, 9).sum(dim=1)
+            for col, tcol in ((0, 0), (1, 1), (2, 2), (3, 3), (4, 4), (5, 5), (7, 6), (8, 10)):
+                assert torch.equal(per[:, col], t[:, tcol].sum(dim=1)), (col, tcol)
+        assert int(fl[..., 6].max()) > 0 and int(fl[..., 5].max()) > 0 and int(fl[..., 8].max()) > 0   # (a day's sum of [6] passes 2^63)
+        return dict(export_cells=int((t[:, 5] > 0).sum()), curtail_seconds=int((fl[0, :, 8] > 0).sum()),
+                    peak_fleet_import_w=int(fl[0, :, 4].max()) / 4096.0, peak_fleet_export_w=int(fl[0, :, 5].max()) / 4096.0)
+    return check
+
+
+def dispatch_fleet_kind(a, battery, lossy):
+    """Battery dispatch alone and with the dispatch fleet series."""
+    rule = dict(charge_above_w=a.charge_above_w, discharge_above_w=a.discharge_above_w, feed_in_limit_w=a.feed_in_limit_w)
+    kw = {**lossy, **rule}
+    return dict(runs=(("dispatch", "dispatch", kw), ("dispatch_fleet", "dispatch_fleet", kw)), stats=True,
+                check=fleet_check(a.interval), keys=dict(modules=a.modules, battery=lossy, rule=rule), derived=lambda med, pmed: {})
+
+
+def schedule_fleet_kind(a, battery, lossy):
+    """The schedule (a.rules rule sets) alone and with the dispatch fleet series."""
+    _, rules, roi = schedule_rules(a)
+    kw = dict(lossy, rules=rules, rule_of_interval=roi)
+    return dict(runs=(("schedule", "schedule", kw), ("schedule_fleet", "schedule_fleet", kw)), stats=True,
+                check=fleet_check(a.interval), derived=lambda med, pmed: {},
+                keys=dict(modules=a.modules, battery=lossy, n_rules=a.rules, rules=rules, rule_of_interval=roi.tolist()))
+
+
 KINDS = {**{kind: table_kind for kind in RUNS}, "battery_sweep": battery_sweep_kind, "dispatch": dispatch_kind,
-         "dispatch_sweep": dispatch_sweep_kind, "schedule": schedule_kind}
+         "dispatch_sweep": dispatch_sweep_kind, "schedule": schedule_kind, "dispatch_fleet": dispatch_fleet_kind,
+         "schedule_fleet": schedule_fleet_kind}
 
 
 def assemble(a, row, t, pt, found, device, build_stamp):
@@ -365,7 +418,7 @@ def parse_args(argv=None):
     ap.add_argument("--discharge-eff", type=float, default=0.95)
     ap.add_argument("--standby-w", type=float, default=2.0)
     ap.add_argument("--variants", type=int, default=5, help="--kind battery_sweep, dispatch_sweep: the variants per chain")
-    ap.add_argument("--rules", type=int, default=1, help="--kind schedule: 1 (the dispatch kind's rule) or 4 hourly rules")
+    ap.add_argument("--rules", type=int, default=1, help="--kind schedule, schedule_fleet: 1 (the dispatch kind's rule) or 4 hourly rules")
     ap.add_argument("--charge-above-w", type=float, default=500.0, help="--kind dispatch: the charge threshold")
     ap.add_argument("--discharge-above-w", type=float, default=200.0, help="--kind dispatch: the discharge threshold")
     ap.add_argument("--feed-in-limit-w", type=float, default=1000.0, help="--kind dispatch: the feed-in limit")

@@ -132,7 +132,7 @@ EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_by
            "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals",
            "tmh_set_registers", "tmh_set_demand", "tmh_set_storage", "tmh_storage_work_bytes", "tmh_set_battery", "tmh_set_battery_fleet",
            "tmh_set_battery_sweep", "tmh_battery_sweep_work_bytes", "tmh_set_dispatch", "tmh_probe_pv",
-           "tmh_set_dispatch_sweep", "tmh_set_schedule"]
+           "tmh_set_dispatch_sweep", "tmh_set_schedule", "tmh_set_dispatch_fleet"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
 K_STORAGE_MAP, K_STORAGE_SCAN, K_STORAGE_REPLAY = 4, 5, 6   # battery storage's three launches (inside K_EXPAND)
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
@@ -152,6 +152,8 @@ BATTERY_SWEEP_MAX = 16  # TMH_BATTERY_SWEEP_MAX
 DISPATCH_SWEEP_MAX = 16  # TMH_DISPATCH_SWEEP_MAX
 OUT_SCHEDULE = 13       # scheduled dispatch (tmh_set_schedule)
 SCHEDULE_RULES_MAX = 8  # TMH_SCHEDULE_RULES_MAX
+OUT_DISPATCH_FLEET = 14  # battery dispatch with the dispatch fleet series (tmh_set_dispatch_fleet)
+OUT_SCHEDULE_FLEET = 15  # the schedule with it
 
 _lib = None
 
@@ -263,6 +265,8 @@ def load():
     L.tmh_set_dispatch_sweep.restype = C.c_int
     L.tmh_set_schedule.argtypes = [p, C.POINTER(Schedule)]
     L.tmh_set_schedule.restype = C.c_int
+    L.tmh_set_dispatch_fleet.argtypes = [p, C.POINTER(Series)]   # (tmh_series with nine columns per row)
+    L.tmh_set_dispatch_fleet.restype = C.c_int
     L.tmh_battery_sweep_work_bytes.argtypes = [u32, u32, u32]
     L.tmh_battery_sweep_work_bytes.restype = sz
     L.tmh_storage_work_bytes.argtypes = [u32, u32]

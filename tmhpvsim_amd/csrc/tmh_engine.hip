@@ -109,6 +109,12 @@ constexpr bool out_lossy_replay(int out) { return out_base(out) == OUT_STORAGE &
 //    pass's 39.9 ms; in the replay passes' shape, 256-chain workgroups at EXP_WAVES_LOSSY (168 VGPRs, 9 spilled, 32 B),
 //    it runs 39.8 ms (Scheduled dispatch).  Its replay pass runs at that shape as every lossy replay does.
 constexpr bool out_sched_map(int out) { return (out & OUT_SCHED) != 0 && (out & OUT_MAP) != 0; }
+//  the dispatch fleet series' two replay instantiations (OUT_FLEET on battery dispatch's and on the schedule's replay,
+//    fp64 single-site, 256-chain workgroups): 3 each.  At 3 waves (168 VGPRs) they spill 47 and 52 VGPRs -- fewer than
+//    the replays they derive from (105, 144) -- and their replay passes run 70.8 and 71.2 ms; at 2 waves (199 and 201
+//    VGPRs, no spill) 79.3 and 80.6 ms (Dispatch fleet series)
+constexpr int EXP_WAVES_DFLEET = 3, EXP_WAVES_SFLEET = 3;
+constexpr bool out_dfleet(int out) { return (out & OUT_FLEET) != 0 && (out & OUT_DISPATCH) != 0; }
 constexpr int FIX_WAVES_SITES = 1;   // min waves per SIMD of the per-site fixup (its fp64 redo recomputes the site's geometry)
 
 struct BlockDesc {                 // as of the step before the block start; -1 = none in the window
@@ -2054,6 +2060,7 @@ constexpr int exp_waves()
     return SITES                             ? EXP_WAVES_SITES
            : out_dsweep(OUT)                  ? ((OUT & OUT_MAP) ? EXP_WAVES_DSWEEP_MAP : EXP_WAVES_DSWEEP_REPLAY)
            : out_sweep(OUT)                   ? ((OUT & OUT_MAP) ? EXP_WAVES_SWEEP_MAP : EXP_WAVES_SWEEP_REPLAY)
+           : out_dfleet(OUT)                  ? ((OUT & OUT_SCHED) ? EXP_WAVES_SFLEET : EXP_WAVES_DFLEET)
            : out_lossy_replay(OUT)            ? EXP_WAVES_LOSSY
            : out_sched_map(OUT)               ? EXP_WAVES_LOSSY
            : sizeof(R) == 8                   ? EXP_WAVES_F64
@@ -2132,16 +2139,22 @@ __device__ __forceinline__ void series_flush(SeriesLds* sl, const SeriesView& se
 // replay workgroup, so that three workgroups per CU (EXP_WAVES_LOSSY) keep their LDS with a histogram of up to
 // about 10,000 bins beside them (the launch's dynamic LDS, two bytes per bin; the default has 4,096).
 constexpr int FLEET_PARTS = 8;   // q(pv), q(meter), import_b, export_b, x' low, x' high, max(b, 0), counts
+// The dispatch fleet series (OUT_FLEET on battery dispatch's and the schedule's replay): a third 16-byte store per
+// slot -- curtailed, then the carries of import_b and of max(b, 0) (the schedule's 33-bit sums; 0 in plain
+// dispatch) and a word of padding.  HALVES x 3,264 B: 25.5 KB for a replay workgroup, 41.5 KB with the static 15.4 KB,
+// so three workgroups per CU keep their LDS (160 KB) with a histogram of up to about 6,500 bins beside them.
+constexpr int DFLEET_PARTS = 12;
+constexpr int fleet_parts(int out) { return out_dfleet(out) ? DFLEET_PARTS : FLEET_PARTS; }
 constexpr int FLEET_HALF = BLOCK_STEPS / 2, FLEET_SLOTS = FLEET_HALF + 4;
-template <int HALVES>
+template <int HALVES, int PARTS = FLEET_PARTS>
 struct FleetLds {
-    __attribute__((aligned(16))) uint32_t part[HALVES][FLEET_SLOTS][FLEET_PARTS];
+    __attribute__((aligned(16))) uint32_t part[HALVES][FLEET_SLOTS][PARTS];
 };
-template <bool ON, int HALVES>
-__device__ __forceinline__ FleetLds<HALVES>* fleet_lds()
+template <bool ON, int HALVES, int PARTS>
+__device__ __forceinline__ FleetLds<HALVES, PARTS>* fleet_lds()
 {
     if constexpr (ON) {
-        __shared__ FleetLds<HALVES> s;
+        __shared__ FleetLds<HALVES, PARTS> s;
         return &s;
     } else {
         return nullptr;
@@ -2174,32 +2187,85 @@ __device__ __forceinline__ void fleet_add(FleetLds<HALVES>* fl, uint32_t slot, i
         p[1] = make_uint4(xl, xh, sc, (threadIdx.x & 32u) ? (nok | ncov << 16) : 0u);
     }
 }
+// The dispatch fleet series' second (DFLEET_PARTS words per slot), as fleet_add: cu is the curtailed power (< 2^26,
+// as export_b: both are parts of the surplus).  WIDE (the schedule): a grid-charging rule takes max(b, 0) up to
+// Pc = 2^27 and import_b up to 2^26 + 2^27, so 32 lanes of either may reach 2^32: the two are summed in 33 bits
+// (half_wave_sum_w) and their carries stored beside the curtailed sum.  PV = false: a night second -- no surplus, so
+// export_b and curtailed are 0; max(b, 0) is 0 too unless a grid rule charges (WIDE), which is then reduced.
+template <bool PV, bool WIDE, int HALVES>
+__device__ __forceinline__ void dfleet_add(FleetLds<HALVES, DFLEET_PARTS>* fl, uint32_t slot, int qpv, int qm, uint32_t im,
+                                           uint32_t ex, uint32_t ch, uint32_t cu, long long x, uint32_t nok, uint32_t ncov)
+{
+    const int sm = half_wave_sum(qm);
+    const uint32_t xl = half_wave_sum_u((uint32_t)x & ((1u << FLEET_SOC_HALF) - 1u));
+    const uint32_t xh = half_wave_sum_u((uint32_t)((unsigned long long)x >> FLEET_SOC_HALF));
+    uint32_t si, sic = 0, sc = 0, scc = 0;
+    if constexpr (WIDE) {
+        half_wave_sum_w(im, si, sic);
+        half_wave_sum_w(ch, sc, scc);
+    } else {
+        si = half_wave_sum_u(im);
+        if constexpr (PV) sc = half_wave_sum_u(ch);
+    }
+    int sp = 0;
+    uint32_t se = 0, su = 0;
+    if constexpr (PV) {
+        sp = half_wave_sum(qpv);
+        se = half_wave_sum_u(ex);
+        su = half_wave_sum_u(cu);
+    }
+    if ((threadIdx.x & 31u) == 31u) {   // (threadIdx.x >> 5 < HALVES: the workgroup's size)
+        uint4* p = reinterpret_cast<uint4*>(fl->part[threadIdx.x >> 5][slot]);
+        p[0] = make_uint4((uint32_t)sp, (uint32_t)sm, si, se);
+        p[1] = make_uint4(xl, xh, sc, (threadIdx.x & 32u) ? (nok | ncov << 16) : 0u);
+        p[2] = make_uint4(su, sic, scc, 0u);
+    }
+}
 // Slots [0, j1 - j0) as the window's rows [j0, j1) of group g into the device table, as series_flush: rows of
-// TMH_BATTERY_FLEET_COLS int64, consecutive steps contiguous, zeros skipped; each value is the sum of the halves'
-// partials (q(pv) and q(meter) sign-extended, the state of charge put together from its two halves).  Every thread
-// of the workgroup calls it, at the same seconds (the tile's sequence of seconds is the workgroup's).
-template <int WGT>
-__device__ __forceinline__ void fleet_flush(const FleetLds<WGT / 32>* fl, const SeriesView& se, uint32_t g, uint32_t j0,
+// TMH_BATTERY_FLEET_COLS int64 (PARTS = FLEET_PARTS) or of TMH_DISPATCH_FLEET_COLS (DFLEET_PARTS), consecutive steps
+// contiguous, zeros skipped; each value is the sum of the halves' partials (q(pv) and q(meter) sign-extended, the
+// state of charge put together from its two halves, the dispatch series' import_b and max(b, 0) from the low word
+// and the carry).  Every thread of the workgroup calls it, at the same seconds (the tile's sequence of seconds is
+// the workgroup's).
+template <int WGT, int PARTS>
+__device__ __forceinline__ void fleet_flush(const FleetLds<WGT / 32, PARTS>* fl, const SeriesView& se, uint32_t g, uint32_t j0,
                                             uint32_t j1)
 {
-    constexpr uint32_t FC = TMH_BATTERY_FLEET_COLS;
-    static_assert(FC == 8, "rows of eight: the series' four columns and the battery's four");
+    constexpr uint32_t FC = PARTS == FLEET_PARTS ? TMH_BATTERY_FLEET_COLS : TMH_DISPATCH_FLEET_COLS;
+    static_assert(TMH_BATTERY_FLEET_COLS == 8, "rows of eight: the series' four columns and the battery's four");
+    static_assert(TMH_DISPATCH_FLEET_COLS == 9, "rows of nine: the battery fleet's eight and the curtailed sum");
     __syncthreads();   // the waves' last stores
     unsigned long long* dst = se.sum + (size_t)g * se.gstride + (size_t)j0 * FC;
     const uint32_t nv = (j1 - j0) * FC;
     for (uint32_t i = threadIdx.x; i < nv; i += WGT) {
-        const uint32_t row = i >> 3, col = i & 7u;
         unsigned long long v = 0;
-        for (int h = 0; h < WGT / 32; ++h) {
-            const uint32_t* p = fl->part[h][row];
-            v += col == 0   ? (unsigned long long)(long long)(int)p[0]
-                 : col == 1 ? (unsigned long long)(long long)(int)p[1]
-                 : col == 2 ? (unsigned long long)(p[7] & 0xFFFFu)
-                 : col == 3 ? (unsigned long long)(p[7] >> 16)
-                 : col == 4 ? (unsigned long long)p[2]
-                 : col == 5 ? (unsigned long long)p[3]
-                 : col == 6 ? (unsigned long long)p[4] + ((unsigned long long)p[5] << FLEET_SOC_HALF)
-                            : (unsigned long long)p[6];
+        if constexpr (PARTS == FLEET_PARTS) {
+            const uint32_t row = i >> 3, col = i & 7u;
+            for (int h = 0; h < WGT / 32; ++h) {
+                const uint32_t* p = fl->part[h][row];
+                v += col == 0   ? (unsigned long long)(long long)(int)p[0]
+                     : col == 1 ? (unsigned long long)(long long)(int)p[1]
+                     : col == 2 ? (unsigned long long)(p[7] & 0xFFFFu)
+                     : col == 3 ? (unsigned long long)(p[7] >> 16)
+                     : col == 4 ? (unsigned long long)p[2]
+                     : col == 5 ? (unsigned long long)p[3]
+                     : col == 6 ? (unsigned long long)p[4] + ((unsigned long long)p[5] << FLEET_SOC_HALF)
+                                : (unsigned long long)p[6];
+            }
+        } else {
+            const uint32_t row = i / FC, col = i - row * FC;   // (row < FLEET_SLOTS: j1 - j0 is at most that)
+            for (int h = 0; h < WGT / 32; ++h) {
+                const uint32_t* p = fl->part[h][row];
+                v += col == 0   ? (unsigned long long)(long long)(int)p[0]
+                     : col == 1 ? (unsigned long long)(long long)(int)p[1]
+                     : col == 2 ? (unsigned long long)(p[7] & 0xFFFFu)
+                     : col == 3 ? (unsigned long long)(p[7] >> 16)
+                     : col == 4 ? (unsigned long long)p[2] + ((unsigned long long)p[9] << 32)
+                     : col == 5 ? (unsigned long long)p[3]
+                     : col == 6 ? (unsigned long long)p[4] + ((unsigned long long)p[5] << FLEET_SOC_HALF)
+                     : col == 7 ? (unsigned long long)p[6] + ((unsigned long long)p[10] << 32)
+                                : (unsigned long long)p[8];
+            }
         }
         if (v) atomicAdd(dst + i, v);
     }
@@ -2225,7 +2291,8 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                                             const PV64* pv_lds, const double* pv_lds_tab,
                                             const float4* nd_lds, const SeriesView& se, SeriesLds* ser_lds,
                                             const IntervalsView& ivv, const StorageView& sto, const long long* batp,
-                                            FleetLds<WGT / 32>* flt_lds, const SweepView& swv, const ScheduleView& scv)
+                                            FleetLds<WGT / 32, fleet_parts(OUT)>* flt_lds, const SweepView& swv,
+                                            const ScheduleView& scv)
 {
     constexpr bool SER = out_base(OUT) == OUT_SERIES;
     // Battery storage (fp64 only), two passes over the same per-second body:
@@ -2257,7 +2324,11 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // dispatch_ask in place of soc_ask, and in the replay the feed-in limit: one more 64-bit sum (the curtailed
     // energy), the demand kind's running peaks fed with import_b and export_b, and IVC = 13
     constexpr bool DSP = (OUT & OUT_DISPATCH) != 0;
-    static_assert(!DSP || (BAT && !FLT), "battery dispatch: a flag of the battery kind's passes, no fleet series");
+    static_assert(!DSP || BAT, "battery dispatch: a flag of the battery kind's passes");
+    // DSP && FLT: the dispatch fleet series beside battery dispatch's or the schedule's table -- the battery fleet
+    // series' second with export_b after the limit and the curtailed power beside it (dfleet_add, rows of
+    // TMH_DISPATCH_FLEET_COLS); single site, no sweep
+    static_assert(!(DSP && FLT) || (!SWP && !SITES), "the dispatch fleet series: single site, not beside a sweep");
     // DSW: the dispatch sweep, both flags -- the sweep's shared second, then dispatch's second of each of KV variants:
     // per variant three more parameters (sw_dsp), and in the replay the curtailed sum (sw_cu) and the four peak
     // registers (sw_im, sw_imj, sw_xm, sw_xmj) beside the sweep's; a variant's parameters are 9 rows, its cells 13 columns
@@ -2546,7 +2617,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     auto flt_mid = [&](uint32_t j) __attribute__((always_inline)) {
         if constexpr (FLT) {
             if (flt_base == 0 && j - j0 >= (uint32_t)FLEET_HALF) {
-                fleet_flush<WGT>(flt_lds, se, flt_g, j0, j);
+                fleet_flush<WGT, fleet_parts(OUT)>(flt_lds, se, flt_g, j0, j);
                 flt_base = j - j0;
             }
         }
@@ -2825,7 +2896,24 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                     }
                     st_ch += (long long)(ok ? max(bm, 0) : 0);
                     st_dis += (long long)(ok ? max(-bm, 0) : 0);
-                    if constexpr (FLT) {
+                    if constexpr (FLT && DSP) {
+                        // the second's row of the dispatch fleet series, as the battery fleet series' below: r, vi, su
+                        // and ve are the second's above (the same expressions), each 0 on lanes that are not ok and
+                        // live.  A night second has no surplus; under a grid rule (SCH) it may charge all the same.
+                        const bool okl = ok && live;
+                        const uint32_t nok = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(okl));
+                        const uint32_t ncov = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(okl && covered));
+                        const int r = d - bm;
+                        const uint32_t im = (uint32_t)(okl ? max(-r, 0) : 0), ch = (uint32_t)(okl ? max(bm, 0) : 0);
+                        const long long xs = okl ? sx : 0ll;
+                        if (__builtin_constant_p(pv) && pv == R(0)) {
+                            dfleet_add<false, SCH, WGT / 32>(flt_lds, jb - flt_base, 0, okl ? qm : 0, im, 0u, ch, 0u, xs, nok, ncov);
+                        } else {
+                            const int su = okl ? max(r, 0) : 0, ve = min(su, dsp.lim);
+                            dfleet_add<true, SCH, WGT / 32>(flt_lds, jb - flt_base, okl ? qp : 0, okl ? qm : 0, im, (uint32_t)ve, ch,
+                                                            (uint32_t)(su - ve), xs, nok, ncov);
+                        }
+                    } else if constexpr (FLT) {
                         // the second's row of the battery fleet series, as the series' (SER above): sums by wave
                         // reduction, counts by ballot; sx after the update, 0 on lanes that are not ok
                         const bool okl = ok && live;
@@ -3141,7 +3229,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     }
     if constexpr (SER)   // (group_chains is a multiple of the workgroup's chains: one group per tile)
         series_flush<WGT>(ser_lds, se, se.group_chains ? cblk * (uint32_t)WGT / se.group_chains : 0u, j0, j1);
-    if constexpr (FLT) fleet_flush<WGT>(flt_lds, se, flt_g, j0 + flt_base, j1);   // the seconds since the mid-tile flush
+    if constexpr (FLT) fleet_flush<WGT, fleet_parts(OUT)>(flt_lds, se, flt_g, j0 + flt_base, j1);   // the seconds since the mid-tile flush
 }
 
 
@@ -3156,10 +3244,11 @@ using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView,
                                                           out_base(OUT) == OUT_DEMAND,
                                                       IntervalsView,
                                                       std::conditional_t<out_base(OUT) == OUT_STORAGE,
+                                                                         std::conditional_t<(OUT & OUT_SCHED) != 0 && (OUT & OUT_FLEET) != 0, ScheduleFleetView,
                                                                          std::conditional_t<(OUT & OUT_SCHED) != 0, ScheduleView,
                                                                          std::conditional_t<(OUT & OUT_SWEEP) != 0, SweepView,
                                                                          std::conditional_t<(OUT & OUT_FLEET) != 0, BatteryFleetView,
-                                                                                            std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>>>>,
+                                                                                            std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>>>>>,
                                                                          TraceView>>>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
@@ -3181,6 +3270,13 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     const long long* batp = nullptr;
     SweepView swv{};
     ScheduleView scv{};
+    if constexpr ((OUT & OUT_SCHED) != 0 && (OUT & OUT_FLEET) != 0) {   // the schedule with the dispatch fleet series: its view + the series'
+        scv = ov.sc;
+        sto = ov.sc.bt.st;
+        ivv = ov.sc.bt.st.iv;
+        batp = ov.sc.bt.params;
+        se = ov.se;
+    } else
     if constexpr ((OUT & OUT_SCHED) != 0) {   // scheduled dispatch: battery dispatch's view + the rule array
         scv = ov;
         sto = ov.bt.st;
@@ -3196,7 +3292,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     if constexpr (out_base(OUT) == OUT_SERIES) se = ov;
     else if constexpr (out_base(OUT) == OUT_INTERVALS || out_base(OUT) == OUT_REGISTERS || out_base(OUT) == OUT_DEMAND)
         ivv = ov;
-    else if constexpr ((OUT & OUT_FLEET) != 0) {   // the battery kind with its fleet series: the kind's view + the series'
+    else if constexpr ((OUT & OUT_FLEET) != 0) {   // the battery kind (or battery dispatch) with its fleet series: the kind's view + the series'
         sto = ov.bt.st;
         ivv = ov.bt.st.iv;
         batp = ov.bt.params;
@@ -3219,7 +3315,7 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     }
     extern __shared__ uint32_t lds_hist[];
     constexpr int WGT = exp_wg<R, OUT, SITES>();   // threads per workgroup
-    FleetLds<WGT / 32>* const flt_lds = fleet_lds<(OUT & OUT_FLEET) != 0, WGT / 32>();   // (written before it is read: no zeroing)
+    FleetLds<WGT / 32, fleet_parts(OUT)>* const flt_lds = fleet_lds<(OUT & OUT_FLEET) != 0, WGT / 32, fleet_parts(OUT)>();   // (written before it is read: no zeroing)
     __shared__ uint32_t cov_lds[4][WGT];
     __shared__ R min_lds[4][WGT];   // minute boundaries mA, mA + 1 of the block: cloudy, clear noise
     __shared__ uint4 held_lds[WGT];
@@ -3974,6 +4070,8 @@ static_assert(TMH_OUT_BATTERY_SWEEP > TMH_OUT_BATTERY_FLEET && TMH_OUT_BATTERY_S
 static_assert(TMH_OUT_DISPATCH > TMH_OUT_BATTERY_SWEEP && TMH_OUT_DISPATCH < TMH_OUT_SITES, "TMH_OUT_DISPATCH: likewise");
 static_assert(TMH_OUT_DISPATCH_SWEEP > TMH_OUT_DISPATCH && TMH_OUT_DISPATCH_SWEEP < TMH_OUT_SITES, "TMH_OUT_DISPATCH_SWEEP: likewise");
 static_assert(TMH_OUT_SCHEDULE > TMH_OUT_DISPATCH_SWEEP && TMH_OUT_SCHEDULE < TMH_OUT_SITES, "TMH_OUT_SCHEDULE: likewise");
+static_assert(TMH_OUT_DISPATCH_FLEET > TMH_OUT_SCHEDULE && TMH_OUT_SCHEDULE_FLEET == TMH_OUT_DISPATCH_FLEET + 1 &&
+                  TMH_OUT_SCHEDULE_FLEET == TMH_OUT_SITES - 1, "the dispatch fleet series' codes: the last two below the flags");
 static_assert(DSWEEP_KV >= 2 && DSWEEP_KV <= TMH_DISPATCH_SWEEP_MAX, "a group of one variant runs battery dispatch's own kernels");
 constexpr bool table_cols_ok()
 {
@@ -4026,6 +4124,8 @@ struct tmh_engine {
     } tables[TBL_KINDS];
     bool has_fleet = false;  // tmh_set_battery_fleet: the battery kind's replay pass adds its window to `fleet` too
     tmh_series fleet{};
+    bool has_dfleet = false;  // tmh_set_dispatch_fleet: battery dispatch's or the schedule's replay pass adds its window to `dfleet` too
+    tmh_series dfleet{};
     // the first set kind (TBL_KINDS: none); a step is refused unless it is the only one (check_interval_tables)
     int table_kind() const
     {
@@ -4627,6 +4727,61 @@ static int check_battery_fleet(const tmh_engine* eng, uint32_t n_chains, int64_t
     return TMH_OK;
 }
 
+// the dispatch fleet series: tmh_set_battery_fleet's cases in its own words
+int tmh_set_dispatch_fleet(struct tmh_engine* eng, const tmh_series* fleet)
+{
+    if (fleet) {
+        if (!fleet->sum || fleet->n_steps == 0 || fleet->n_groups == 0)
+            return fail(TMH_E_INVAL, "dispatch fleet series needs a buffer, n_steps > 0 and n_groups > 0");
+        if ((uintptr_t)fleet->sum & 7) return fail(TMH_E_INVAL, "dispatch fleet series buffer must be 8-byte aligned");
+        if (fleet->group_chains % 512 != 0 || (fleet->group_chains == 0 && fleet->n_groups != 1))
+            return fail(TMH_E_INVAL, "dispatch fleet series group_chains %u (x %u groups): 0 with one group, or a multiple of 512",
+                        fleet->group_chains, fleet->n_groups);
+    }
+    if (!eng) return fail(TMH_E_INVAL, "NULL engine");
+    if (fleet && eng->kp.precision != TMH_FP64)
+        return fail(TMH_E_INVAL, "a dispatch fleet series needs an fp64 engine, as the dispatch kinds whose replay pass fills it");
+    eng->has_dfleet = fleet != nullptr;
+    eng->dfleet = fleet ? *fleet : tmh_series{};
+    return TMH_OK;
+}
+
+// A step / expansion with a dispatch fleet series set, before the other checks (a state no earlier library knows:
+// without the series this returns at once and every refusal keeps its words): what the replay pass's rows assume,
+// before any launch.
+static int check_dispatch_fleet(const tmh_engine* eng, uint32_t n_chains, int64_t step0, uint32_t n_steps)
+{
+    if (!eng->has_dfleet) return TMH_OK;
+    const tmh_series& fl = eng->dfleet;
+    const int kind = eng->table_kind();
+    if (kind != TBL_DISPATCH && kind != TBL_SCHEDULE) {
+        if (kind == TBL_KINDS)
+            return fail(TMH_E_INVAL, "a dispatch fleet series needs battery dispatch or the schedule set (tmh_set_dispatch, "
+                                     "tmh_set_schedule): the kind's replay pass fills it");
+        return fail(TMH_E_INVAL, "a dispatch fleet series cannot run beside %s: battery dispatch's or the schedule's replay pass fills it",
+                    TABLE_KINDS[kind].name);
+    }
+    for (int k = kind + 1; k < TBL_KINDS; ++k)
+        if (eng->tables[k].set)
+            return fail(TMH_E_INVAL, "a dispatch fleet series cannot run beside two table kinds (%s and %s)", TABLE_KINDS[kind].name,
+                        TABLE_KINDS[k].name);
+    if (eng->has_series)
+        return fail(TMH_E_INVAL, "a dispatch fleet series and a fleet series (tmh_set_series) are both set: one of the two per engine");
+    if (eng->has_fleet)
+        return fail(TMH_E_INVAL, "a dispatch fleet series and a battery fleet series (tmh_set_battery_fleet) are both set: the "
+                                 "battery fleet series is the battery kind's");
+    if (eng->kp.ids) return fail(TMH_E_INVAL, "a dispatch fleet series cannot run on compacted chains (tmh_set_chain_ids)");
+    if (eng->kp.sites)
+        return fail(TMH_E_INVAL, "a dispatch fleet series cannot run with per-chain sites (tmh_set_sites): one feeder is one site");
+    if (step0 < fl.step0 || step0 + (int64_t)n_steps > fl.step0 + (int64_t)fl.n_steps)
+        return fail(TMH_E_INVAL, "window [%lld, +%u) outside the dispatch fleet series [%lld, +%u)", (long long)step0, n_steps,
+                    (long long)fl.step0, fl.n_steps);
+    if (fl.group_chains && (uint64_t)fl.n_groups * fl.group_chains < n_chains)
+        return fail(TMH_E_INVAL, "dispatch fleet series of %u groups x %u chains < n_chains %u", fl.n_groups, fl.group_chains,
+                    n_chains);
+    return TMH_OK;
+}
+
 // A step / expansion with an interval table set (nothing to check without one): everything the
 // kernels assume, checked on the host before any launch (tmhpvsim.h, tmh_set_intervals,
 // tmh_set_registers, tmh_set_demand).  The messages name the first set kind; with two kinds set
@@ -5040,6 +5195,15 @@ static int phase_expand(const StepCtx& c)
                     } else {
                         launch(r, okind, st, view, rsv);
                     }
+                } else if constexpr ((O == OUT_DSP || O == (OUT_DSP | OUT_SCHED)) && !S) {
+                    // the dispatch fleet series beside the table, likewise (single site: check_dispatch_fleet)
+                    if (eng->has_dfleet) {
+                        if constexpr (O == OUT_DSP) launch(r, out_c<O | OUT_FLEET>, st, BatteryFleetView{view, c.sev}, rsv);
+                        else launch(r, out_c<O | OUT_FLEET>, st, ScheduleFleetView{view, c.sev}, rsv);
+                        out = O == OUT_DSP ? TMH_OUT_DISPATCH_FLEET : TMH_OUT_SCHEDULE_FLEET;
+                    } else {
+                        launch(r, okind, st, view, rsv);
+                    }
                 } else {
                     launch(r, okind, st, view, rsv);
                 }
@@ -5162,6 +5326,7 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
     if (stats && stats->hist && (stats->n_bins == 0 || stats->n_bins > 16384 || !(stats->hi > stats->lo)))
         return fail(TMH_E_INVAL, "bad histogram spec (n_bins %u in [1,16384], hi > lo)", stats->n_bins);
     if (int rc = check_tables(eng, n_chains)) return rc;
+    if (int rc = check_dispatch_fleet(eng, n_chains, step0, n_steps)) return rc;
     const bool series = eng->has_series;   // (checked for a walk too: nothing of a refused window is launched)
     if (series)
         if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
@@ -5198,6 +5363,10 @@ static int step_phases(struct tmh_engine* eng, void* state, uint64_t chain0, uin
         c.sev = SeriesView{reinterpret_cast<unsigned long long*>(eng->fleet.sum) +
                                (size_t)(step0 - eng->fleet.step0) * TMH_BATTERY_FLEET_COLS,
                            (uint64_t)eng->fleet.n_steps * TMH_BATTERY_FLEET_COLS, eng->fleet.group_chains, 0u};
+    else if (eng->has_dfleet)   // (never beside either: check_dispatch_fleet) the dispatch fleet series' rows of nine
+        c.sev = SeriesView{reinterpret_cast<unsigned long long*>(eng->dfleet.sum) +
+                               (size_t)(step0 - eng->dfleet.step0) * TMH_DISPATCH_FLEET_COLS,
+                           (uint64_t)eng->dfleet.n_steps * TMH_DISPATCH_FLEET_COLS, eng->dfleet.group_chains, 0u};
     if (c.table() != TBL_KINDS) {   // the whole table; the window's first step from its origin (the cells' columns:
         const tmh_intervals& t = eng->tables[c.table()].t;   // the kernels' compile-time constant)
         c.ivv = IntervalsView{reinterpret_cast<unsigned long long*>(t.sum), t.ld, (uint32_t)(step0 - t.step0), t.interval_s};
@@ -5294,7 +5463,8 @@ int tmh_run(struct tmh_engine* eng, void* state, uint64_t chain0, uint32_t n_cha
     const size_t need = eng->path == TMH_PATH_TIME_PARALLEL ? pb + tmh_engine_scratch_bytes(eng, n_chains, n_steps) : pb;
     if (!workspace || workspace_bytes < need)
         return fail(TMH_E_INVAL, "workspace too small: %zu < %zu", workspace_bytes, need);
-    if (eng->has_series)   // before the plan's launches
+    if (int rc = check_dispatch_fleet(eng, n_chains, step0, n_steps)) return rc;   // before the plan's launches
+    if (eng->has_series)
         if (int rc = check_series(eng, n_chains, step0, n_steps, trace)) return rc;
     if (int rc = check_interval_tables(eng, n_chains, step0, n_steps, trace)) return rc;
     if (int rc = check_battery_fleet(eng, n_chains, step0, n_steps)) return rc;

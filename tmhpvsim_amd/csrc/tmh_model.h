@@ -1576,7 +1576,9 @@ enum OutKind : int {
     // discharge efficiency, standby drain and the loss column; the engine reports it as TMH_OUT_BATTERY
     OUT_LOSSY = 64,
     // flag on OUT_STORAGE | OUT_LOSSY, replay pass only: the battery fleet series beside the table -- the second's
-    // quantities reduced across the chains into rows of TMH_BATTERY_FLEET_COLS sums; TMH_OUT_BATTERY_FLEET
+    // quantities reduced across the chains into rows of TMH_BATTERY_FLEET_COLS sums; TMH_OUT_BATTERY_FLEET.  Also on
+    // battery dispatch's and scheduled dispatch's replay pass (| OUT_DISPATCH, | OUT_DISPATCH | OUT_SCHED, single
+    // site): the dispatch fleet series, rows of TMH_DISPATCH_FLEET_COLS; TMH_OUT_DISPATCH_FLEET, TMH_OUT_SCHEDULE_FLEET
     OUT_FLEET = 128,
     // flag on OUT_STORAGE | OUT_LOSSY, both passes: the battery sweep (tmh_battery_sweep) -- a lane carries up to
     // SWEEP_KV batteries of its chain through one pass over the seconds; TMH_OUT_BATTERY_SWEEP
@@ -1792,6 +1794,13 @@ struct BatteryFleetView {
     BatteryView bt;
     SeriesView se;
 };
+// The dispatch fleet series beside scheduled dispatch's table (OUT_SCHED | OUT_FLEET): the schedule's view and the
+// series' rows, as BatteryFleetView's (which battery dispatch's OUT_FLEET instantiation takes as it is: its view
+// is the battery kind's); rows of TMH_DISPATCH_FLEET_COLS int64 per step.
+struct ScheduleFleetView {
+    ScheduleView sc;
+    SeriesView se;
+};
 // The battery sweep (OUT_SWEEP): one launch's group of nv <= SWEEP_KV variants of every chain.  `bt` is the battery
 // kind's view of the group's first variant; variant v's table lies tstride elements, its work buffer wstride
 // elements and its parameters 6 * ld elements after variant v - 1's.  Variants nv .. SWEEP_KV - 1 of a short last
@@ -1836,6 +1845,20 @@ __device__ __forceinline__ uint32_t half_wave_sum_u(uint32_t v)
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);    // row_shr:8
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1, 3
     return v;
+}
+// The half-wave sums of values whose 32-lane sum may reach 2^32 but whose 16-lane sum does not (scheduled dispatch
+// under a grid-charging rule: max(b, 0) <= 2^27 and import_b < 3 * 2^26, 16 x 3 * 2^26 < 2^32): the rows of 16 lanes
+// are summed as above, and lanes 31 and 63 add the row before theirs in 33 bits -- the low word in lo, the carry
+// (0 or 1) in hi.  One move and one compare more than half_wave_sum_u.
+__device__ __forceinline__ void half_wave_sum_w(uint32_t v, uint32_t& lo, uint32_t& hi)
+{
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);    // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);    // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);    // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);    // row_shr:8
+    const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1, 3
+    lo = v + t;
+    hi = lo < v ? 1u : 0u;
 }
 // The sums of v over lanes 0-31 in lane 31 and over lanes 32-63 in lane 63 (other lanes:
 // partial sums).  Four shifted adds scan each row of 16 lanes (zeros shifted in), then

@@ -332,3 +332,101 @@ def sweep_summary(raw, interval_s, params, fleet=False):
     out.update({"energy_wh_curtailed": cur / e, "curtailed_share": cur / qpv, "self_consumption": (pv - exp - cur) / qpv,
                 "peak_w_import": pk_im / scale, "peak_w_export": pk_ex / scale})
     return out
+
+
+# The dispatch fleet series (tmh_set_dispatch_fleet, BatchedSim.enable_dispatch_fleet): battery.FLEET_COLUMNS behind
+# this kind's rule -- the export after the limit -- and the curtailed power beside them.
+FLEET_COLUMNS = battery.FLEET_COLUMNS + ("curtailed",)
+
+
+def _fleet_rows(base, ok, d_all, x, second, n_groups, gc):
+    """The loop the two kinds' fleet_from_traces share: second(t, x, d) -> (b, x', lim) of second t; base is
+    series.from_traces' [n_groups, n_steps, 4].  Returns ([n_groups, n_steps, 9], the SoC after the seconds)."""
+    n_steps = ok.shape[0]
+    out = np.zeros((n_groups, n_steps, len(FLEET_COLUMNS)), dtype=np.int64)
+    out[..., :4] = base
+    for t in range(n_steps):
+        oks, d = ok[t], d_all[t]
+        b, xn, lim = second(t, x, d)
+        x = np.where(oks, xn, x)
+        r = d - b
+        sur = np.maximum(r, 0)
+        exp = np.minimum(sur, lim)
+        cols = np.where(oks, np.stack([np.maximum(-r, 0), exp, x, np.maximum(b, 0), sur - exp]), 0)
+        for g in range(n_groups):
+            out[g, t, 4:] = cols[:, g * gc:(g + 1) * gc].sum(axis=1)
+    return out, x
+
+
+def fleet_from_traces(pv, meter, covered, *, params, soc0, group_chains=0):
+    """The dispatch fleet series of time-major traces [n_steps, n_chains] and the SoC after them: (int64
+    [n_groups, n_steps, 9], int64 [n_chains]).  from_traces' loop over the seconds (on _second), summed over the
+    chains of a group instead of the seconds of an interval: row t of a group holds, over its chains that are ok at
+    second t, FLEET_COLUMNS -- series.from_traces' four columns, the sums of import_b, of export_b after the limit,
+    of the SoC x' after the second, of max(b, 0) and of the curtailed power.  params [9, n_chains], soc0: as
+    from_traces; groups as series.from_traces (chain i in group i // group_chains, 0: one group, else a multiple of
+    512; the last may be partial)."""
+    from . import series
+    pv, meter, covered = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (pv, meter, covered))
+    base = series.from_traces(pv, meter, covered, group_chains)                   # (checks the arguments)
+    n = pv.shape[1]
+    params = check_params(params)
+    if params.shape[1] != n:
+        raise ValueError(f"dispatch params for {params.shape[1]} chains, traces of {n}")
+    x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (n,)), 0, params[0])
+    ok, d_all = battery._ok_d(pv, meter, covered)
+    return _fleet_rows(base, ok, d_all, x, lambda t, x, d: _second(x, d, params) + (params[8],), base.shape[0],
+                       int(group_chains) or max(n, 1))
+
+
+def fleet_to_watts(raw, bin_s=1, mean=False):
+    """float64 series of a raw dispatch fleet table [..., n_steps, 9]: battery.fleet_to_watts' keys (pv, meter,
+    import_w, export_w -- after the limit --, charge_w, discharge_w, soc_wh, n_ok, covered) plus curtailed_w, each
+    [..., n_bins]; fleet sums, or with mean=True the means per ok chain-second.  Bins of bin_s seconds are summed
+    as integers first; a last partial bin is kept; a bin without an ok chain-second gives NaN.  The discharging
+    power is [7] - sum of b with sum of b = [4] - [5] - [8] - ([1] - [0]), the row's identity."""
+    raw = np.asarray(raw.cpu() if hasattr(raw, "cpu") else raw).astype(np.int64, copy=False)
+    if raw.ndim < 2 or raw.shape[-1] != len(FLEET_COLUMNS):
+        raise ValueError("raw dispatch fleet series must end in the 9 columns")
+    bin_s = int(bin_s)
+    if bin_s < 1:
+        raise ValueError("bin_s must be >= 1")
+    n_steps = raw.shape[-2]
+    secs = np.ones(n_steps, dtype=np.int64)
+    if bin_s > 1 and n_steps:
+        edges = np.arange(0, n_steps, bin_s)
+        raw, secs = np.add.reduceat(raw, edges, axis=-2), np.add.reduceat(secs, edges)
+    n_ok = raw[..., 2]
+    den = np.where(n_ok > 0, n_ok, np.nan).astype(np.float64)
+    scale = float(1 << FRAC_BITS)
+    div = den * scale if mean else np.where(n_ok > 0, scale, np.nan)
+    dis = raw[..., 7] - (raw[..., 4] - raw[..., 5] - raw[..., 8] - (raw[..., 1] - raw[..., 0]))
+    return {"pv": raw[..., 0] / div, "meter": raw[..., 1] / div, "import_w": raw[..., 4] / div,
+            "export_w": raw[..., 5] / div, "charge_w": raw[..., 7] / div, "discharge_w": dis / div,
+            "curtailed_w": raw[..., 8] / div,
+            "soc_wh": raw[..., 6] / ((div if mean else div * secs) * 3600.0),
+            "n_ok": n_ok.astype(np.float64), "covered": raw[..., 3] / den}
+
+
+def fleet_peaks(raw, bin_s):
+    """Per bin of bin_s seconds of a raw dispatch fleet table [..., n_steps, 9] (a last partial bin is kept): the
+    fleet's highest import and highest feed-in of any one second in W and the second of each -- dict of
+    peak_w_import, peak_w_export (float64 [..., n_bins]) and t_peak_import, t_peak_export (int64, seconds into the
+    bin of the earliest second at the peak).  The coincident peak: what the feeder sees, not the sum of the chains'
+    own peaks (table columns 11 and 12)."""
+    raw = np.asarray(raw.cpu() if hasattr(raw, "cpu") else raw).astype(np.int64, copy=False)
+    if raw.ndim < 2 or raw.shape[-1] != len(FLEET_COLUMNS):
+        raise ValueError("raw dispatch fleet series must end in the 9 columns")
+    bin_s = int(bin_s)
+    if bin_s < 1:
+        raise ValueError("bin_s must be >= 1")
+    n_steps = raw.shape[-2]
+    n_bins = -(-n_steps // bin_s)
+    out = {}
+    for name, col in (("import", 4), ("export", 5)):
+        v = raw[..., col]
+        pad = np.full(v.shape[:-1] + (n_bins * bin_s - n_steps,), -1, dtype=np.int64)   # (below every sum: never the peak)
+        v = np.concatenate([v, pad], axis=-1).reshape(v.shape[:-1] + (n_bins, bin_s))
+        out["peak_w_" + name] = v.max(axis=-1) / float(1 << FRAC_BITS)
+        out["t_peak_" + name] = v.argmax(axis=-1).astype(np.int64)                       # (the first maximum)
+    return out

@@ -266,6 +266,8 @@ class BatchedSim:
             setattr(self, t["desc"], None)
         self.battery_fleet_raw = None   # int64 [n_groups, n_steps, 8]: the battery fleet series (enable_battery_fleet)
         self._battery_fleet = None
+        self.dispatch_fleet_raw = None   # int64 [n_groups, n_steps, 9]: the dispatch fleet series (enable_dispatch_fleet)
+        self._dispatch_fleet = None
         self.compact_slots = []      # slots each window of the last compact=True run ran on (run())
         self._last_scratch = None
         with torch.cuda.device(self.device):
@@ -465,6 +467,8 @@ class BatchedSim:
         torch = _torch()
         t, name, label = _BATTERIES[kind], _TABLES[kind]["name"], kind.replace("_", " ")
         if n_steps is None:
+            if kind in ("dispatch", "schedule") and getattr(self, "_" + kind) is not None and self._dispatch_fleet is not None:
+                self.enable_dispatch_fleet(None)   # (the kind's own output: off with it)
             if getattr(self, "_" + kind) is not None:   # (else soc and the work buffer may be another kind's)
                 self.soc = self._battery_work = self._battery_args = None
                 setattr(self, t["desc"], None)
@@ -855,6 +859,53 @@ class BatchedSim:
         _torch().cuda.synchronize(self.device)
         return fleet_to_watts(self.battery_fleet_raw, bin_s=bin_s, mean=mean)
 
+    # ------------------------------------------------------------------ the dispatch fleet series
+    def enable_dispatch_fleet(self, n_steps, step0=None, group_chains=0, buffer=None):
+        """Beside battery dispatch's or the schedule's table (enable_dispatch or enable_schedule first), accumulate
+        the dispatch fleet series (tmhpvsim_amd.dispatch.FLEET_COLUMNS: per second and group of chains, the battery
+        fleet series' eight columns under the kind's rule -- the export after the feed-in limit, the import with
+        what a grid-charging rule buys -- and the curtailed power) of steps [step0, step0 + n_steps) in every later
+        run: the feeder's coincident peaks, which no table holds.  step0, group_chains and buffer as
+        enable_battery_fleet, with rows of nine: `sim.dispatch_fleet_raw` is the int64 tensor [n_groups, n_steps, 9]
+        (several sims may add into one buffer).  The kind's table and `sim.soc` are what they are without the
+        series.  run() and its window pipeline carry it; compact=True and per-chain sites are refused.
+        n_steps=None switches it off; so does switching the kind off."""
+        torch = _torch()
+        if n_steps is None:
+            _lib.check(self.L.tmh_set_dispatch_fleet(self._eng, None))
+            self.dispatch_fleet_raw, self._dispatch_fleet = None, None
+            return None
+        if self._dispatch is None and self._schedule is None:
+            raise ValueError("enable_dispatch_fleet: call enable_dispatch or enable_schedule first (the kind's replay pass "
+                             "fills the dispatch fleet series)")
+        if self.sites is not None:
+            raise ValueError("a dispatch fleet series cannot run with per-chain sites (one feeder is one site)")
+        from .dispatch import FLEET_COLUMNS
+        n_steps, gc, nc = int(n_steps), int(group_chains), len(FLEET_COLUMNS)
+        if n_steps < 1 or gc < 0 or gc % 512:
+            raise ValueError("enable_dispatch_fleet: n_steps >= 1, group_chains 0 or a multiple of 512")
+        n_groups = 1 if gc == 0 else -(-self.n // gc)
+        if buffer is None:
+            buffer = torch.zeros(n_groups, n_steps, nc, dtype=torch.int64, device=self.device)
+        elif (buffer.dtype != torch.int64 or buffer.device != self.device or not buffer.is_contiguous()
+              or buffer.dim() != 3 or buffer.shape[0] < n_groups or tuple(buffer.shape[1:]) != (n_steps, nc)):
+            raise ValueError(f"dispatch fleet buffer must be a contiguous int64 [>= {n_groups}, {n_steps}, {nc}] tensor "
+                             f"on {self.device}")
+        st = _lib.Series(buffer.data_ptr(), self.step if step0 is None else int(step0), n_steps, gc,
+                         int(buffer.shape[0]), 0)
+        _lib.check(self.L.tmh_set_dispatch_fleet(self._eng, C.byref(st)))
+        self.dispatch_fleet_raw, self._dispatch_fleet = buffer, st
+        return buffer
+
+    def dispatch_fleet(self, bin_s=1, mean=False):
+        """The dispatch fleet series in watts and watt-hours (dispatch.fleet_to_watts of dispatch_fleet_raw),
+        [n_groups, n_bins] each; dispatch.fleet_peaks gives the bins' coincident peaks."""
+        from .dispatch import fleet_to_watts
+        if self.dispatch_fleet_raw is None:
+            raise ValueError("no dispatch fleet series: call enable_dispatch_fleet first")
+        _torch().cuda.synchronize(self.device)
+        return fleet_to_watts(self.dispatch_fleet_raw, bin_s=bin_s, mean=mean)
+
     def guard_records(self):
         """Tests: the fp32 guard-band records (chain, 128-s block) of the last window that run()
         issued as a single tmh_run (tmh_test_guard_records; synchronises the device)."""
@@ -917,6 +968,15 @@ class BatchedSim:
             s0, sn = self._battery_fleet.step0, self._battery_fleet.n_steps
             if self.step < s0 or self.step + n_steps > s0 + sn:
                 raise ValueError(f"steps [{self.step}, +{n_steps}) outside the battery fleet series [{s0}, +{sn})")
+        if self._dispatch_fleet is not None:   # (likewise)
+            if compact:
+                raise ValueError("a dispatch fleet series cannot run compacted (a compacted tile would mix groups)")
+            if trace:
+                raise ValueError("a dispatch fleet series run takes no traces (trace=()): run the rule over the traces "
+                                 "instead (dispatch.fleet_from_traces)")
+            s0, sn = self._dispatch_fleet.step0, self._dispatch_fleet.n_steps
+            if self.step < s0 or self.step + n_steps > s0 + sn:
+                raise ValueError(f"steps [{self.step}, +{n_steps}) outside the dispatch fleet series [{s0}, +{sn})")
         if n_steps > ROLL_MAX:   # one rolling clock covers at most ROLL_MAX steps: run in pieces (same bits)
             res = out if out is not None else self._alloc(n_steps, trace)
             done = 0

@@ -242,3 +242,38 @@ def daily(start, tz, n_steps, interval_s, starts, step0=0):
     n_iv = n_intervals(n_steps, interval_s)
     tod = np.array([ck.local_at(step0 + k * interval_s) % 86400 for k in range(n_iv)], dtype=np.int64)
     return rule[np.searchsorted(edges, tod, side="right") - 1]   # (index -1: the last period, over midnight)
+
+
+def fleet_from_traces(pv, meter, covered, interval_s, *, params, rule_of_interval, soc0, origin=0, group_chains=0):
+    """The dispatch fleet series behind the schedule: dispatch.fleet_from_traces with each second under the rule of
+    its interval (origin + t) // interval_s -- (int64 [n_groups, n_steps, 9], int64 [n_chains]).  params [6 + 4 R,
+    n_chains], rule_of_interval, soc0, interval_s and origin as from_traces; groups as series.from_traces.  Under a
+    grid-charging rule the import holds what the batteries buy and the charge may exceed the PV."""
+    from . import series
+    pv, meter, covered = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (pv, meter, covered))
+    base = series.from_traces(pv, meter, covered, group_chains)                  # (checks the arguments)
+    interval_s, origin = int(interval_s), int(origin)
+    if not 1 <= interval_s <= MAX_INTERVAL_S:
+        raise ValueError("1 <= interval_s <= 2^23 - 1")
+    n_steps, n = pv.shape
+    params = check_params(params)
+    if params.shape[1] != n:
+        raise ValueError(f"schedule params for {params.shape[1]} chains, traces of {n}")
+    rules = check_rules(rule_of_interval, n_rules_of(params), n_intervals(origin + n_steps, interval_s))
+    cap, pc, pd, ec, ed, sb = params[:6]
+    kc, kd = battery._recip(ec), battery._recip(ed)
+
+    def second(t, x, d):
+        tc, td, lim, g = params[6 + 4 * int(rules[(origin + t) // interval_s]):][:4]
+        a = _ask(d, pc, pd, tc, td, g)
+        s = battery._stored(a, ec, kd)
+        x1 = np.clip(x + s, 0, cap)
+        mv = x1 - x
+        fill = np.minimum(a, (mv * kc + 65535) >> 16)
+        drain = -np.minimum(-a, (-mv * ed) >> 16)
+        b = np.where(mv == s, a, np.where(mv > 0, fill, np.where(mv < 0, drain, 0)))
+        return b, np.maximum(x1 - sb, 0), lim
+
+    x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (n,)), 0, cap)
+    ok, d_all = battery._ok_d(pv, meter, covered)
+    return dispatch._fleet_rows(base, ok, d_all, x, second, base.shape[0], int(group_chains) or max(n, 1))
