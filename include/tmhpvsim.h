@@ -44,7 +44,9 @@
  *    dispatch sweep (tmh_dispatch_sweep: battery dispatch's table and state of charge for each
  *    of up to TMH_DISPATCH_SWEEP_MAX rule sets per chain, in one run), or scheduled dispatch
  *    (tmh_schedule: battery dispatch with up to TMH_SCHEDULE_RULES_MAX rule sets per chain, one
- *    of them in force per metering interval, and charging from the grid).
+ *    of them in force per metering interval, and charging from the grid), or the schedule sweep
+ *    (tmh_schedule_sweep: scheduled dispatch's table and state of charge for each of up to
+ *    TMH_SCHEDULE_SWEEP_MAX variants -- battery, rule sets and rule array -- per chain, in one run).
  *  - `stream` is a hipStream_t (NULL = default stream); all work is enqueued
  *    asynchronously on it.  One engine per device; not re-entrant per engine.
  */
@@ -514,6 +516,39 @@ typedef struct tmh_schedule {
     uint32_t n_rules;         /* 1 .. TMH_SCHEDULE_RULES_MAX */
 } tmh_schedule;
 
+/* The schedule sweep: tmh_schedule's second, unchanged to the bit, on n_variants (battery, rule sets, rule array)
+ * variants of the same chain in one run -- the same household (the same pv and meter second for second) under each
+ * of K tariffs and batteries: which tariff to take, whether grid charging at night pays under tariff A or B, which
+ * battery to buy under it.  It relates to tmh_schedule as tmh_dispatch_sweep relates to tmh_dispatch.  Variant v's
+ * slice of table, soc, params and rule_of_interval is exactly what tmh_set_schedule would be given and would
+ * produce for it, all thirteen columns and soc bit for bit, so columns 0-3 are the same in every variant:
+ *   table.sum         device int64 [n_variants][n_intervals][TMH_DISPATCH_COLS][ld], zero-initialised by the
+ *                     caller; variant v's table starts n_intervals * TMH_DISPATCH_COLS * ld elements after v - 1's
+ *   soc               device int64 [n_variants][ld]
+ *   params            device int64 [n_variants][6 + 4 * n_rules][ld]; n_rules is the same for every variant (a
+ *                     variant with fewer rules repeats one)
+ *   rule_of_interval  device uint8 [n_variants][n_intervals], variant v's array n_intervals bytes after v - 1's:
+ *                     two tariffs have different periods (a shared array is the special case of equal rows)
+ * The table, soc and params strides are in units of ld, so column slices of wider tensors stay valid; indexing
+ * within a variant is per chain index (ids[slot] under tmh_set_chain_ids).  Entries at or above n_rules and
+ * interval indices past the array are clamped per variant as a lane loads them, as tmh_schedule's: no address
+ * depends on an unchecked value.  work: the battery sweep's, >= tmh_battery_sweep_work_bytes(n_chains, n_steps,
+ * n_variants) bytes of the largest window.  The engine runs the variants in groups of a compile-time count per
+ * launch (a group of one variant is tmh_schedule's own launches on that variant's array row); the bits do not
+ * depend on the grouping, windows, pipelining, batches or compaction.  fp64 engines and the engine's one site
+ * only.  n_variants takes tmh_schedule's tail padding: sizeof(tmh_schedule_sweep) == sizeof(tmh_schedule). */
+#define TMH_SCHEDULE_SWEEP_MAX 16
+typedef struct tmh_schedule_sweep {
+    tmh_intervals table;      /* sum is [n_variants][n_intervals][TMH_DISPATCH_COLS][ld] */
+    int64_t* soc;             /* device [n_variants][ld] */
+    void* work;               /* device scratch */
+    size_t work_bytes;        /* >= tmh_battery_sweep_work_bytes(n_chains, n_steps, n_variants) of the largest window */
+    const int64_t* params;    /* device [n_variants][6 + 4 * n_rules][ld] */
+    const uint8_t* rule_of_interval;   /* device [n_variants][n_intervals] */
+    uint32_t n_rules;         /* 1 .. TMH_SCHEDULE_RULES_MAX, the same for every variant */
+    uint32_t n_variants;      /* 1 .. TMH_SCHEDULE_SWEEP_MAX */
+} tmh_schedule_sweep;
+
 /* The dispatch fleet series: the battery fleet series (TMH_BATTERY_FLEET_COLS above) behind battery dispatch or
  * scheduled dispatch -- what the whole batch draws, feeds in, curtails and stores second by second under a feed-in
  * limit, thresholds, a tariff or grid charging.  The coincidence across chains within an interval is what no
@@ -800,6 +835,20 @@ int tmh_set_dispatch_sweep(struct tmh_engine* eng, const tmh_dispatch_sweep* sw)
  * kind set too, in either order; tmh_set_series or tmh_set_battery_fleet set; per-chain sites (tmh_set_sites).
  * The parameters' and the array's values are not read on the host: the kernels clamp them. */
 int tmh_set_schedule(struct tmh_engine* eng, const tmh_schedule* sc);
+/* The schedule sweep (tmh_schedule_sweep above): every later expansion of this engine advances sw->soc and adds
+ * its window to sw->table.sum for each of the n_variants (battery, rules, array) variants of every chain; NULL
+ * switches it off.  The variants run in groups, each group in the kind's three launches; the TMH_K_STORAGE_* slots
+ * sum this kind's launches of a window and TMH_K_EXPAND spans all of them.  Statistics and the histogram, when
+ * tmh_stats gives them, are accumulated by exactly one replay launch per window.  tmh_engine_last_expand reports
+ * TMH_OUT_SCHEDULE_SWEEP | TMH_OUT_FP64.  Refused here (TMH_E_INVAL, the messages name "schedule sweep"):
+ * tmh_set_schedule's bad-struct cases; n_variants 0 or above TMH_SCHEDULE_SWEEP_MAX; n_rules 0 or above
+ * TMH_SCHEDULE_RULES_MAX; a NULL or misaligned (8 bytes) params, soc or work; a NULL rule_of_interval; work_bytes
+ * below tmh_battery_sweep_work_bytes(1, 1, n_variants); an fp32 engine.  Refused at a step / expansion call or a
+ * walk of that window, before any launch: everything tmh_set_schedule's step refuses (traces; the work buffer
+ * against tmh_battery_sweep_work_bytes of the window); any other table kind set too, in either order;
+ * tmh_set_series, tmh_set_battery_fleet or tmh_set_dispatch_fleet set; per-chain sites (tmh_set_sites).  The
+ * parameters' and the arrays' values are not read on the host: the kernels clamp them. */
+int tmh_set_schedule_sweep(struct tmh_engine* eng, const tmh_schedule_sweep* sw);
 /* The dispatch fleet series (TMH_DISPATCH_FLEET_COLS above): every later expansion of this engine with battery
  * dispatch or the schedule set adds its window's rows to fleet->sum, in the kind's replay pass, beside the kind's
  * table; NULL switches it off.  The kind's table and soc are exactly what they are without the series.  A setter
@@ -929,7 +978,8 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
  * TMH_OUT_DISPATCH (battery dispatch: its replay pass, with or without statistics),
  * TMH_OUT_DISPATCH_SWEEP (the dispatch sweep), TMH_OUT_SCHEDULE (scheduled dispatch: its replay pass),
  * TMH_OUT_DISPATCH_FLEET and TMH_OUT_SCHEDULE_FLEET (battery dispatch / the schedule with the dispatch fleet
- * series: the replay pass that fills both), plus
+ * series: the replay pass that fills both), TMH_OUT_SCHEDULE_SWEEP (the schedule sweep: codes 0-15 are used
+ * up, so it is the first value above the two flags and never a combination of them), plus
  * TMH_OUT_SITES with per-chain sites and TMH_OUT_FP64 in fp64; -1 before the first expansion (and on the sequential path, whose one
  * kernel serves every output). */
 #define TMH_OUT_ANY 0
@@ -950,6 +1000,7 @@ int tmh_profile_read(struct tmh_engine* eng, int kernel, double* total_ms, int* 
 #define TMH_OUT_SCHEDULE_FLEET 15
 #define TMH_OUT_SITES 16
 #define TMH_OUT_FP64 32
+#define TMH_OUT_SCHEDULE_SWEEP 64
 int tmh_engine_last_expand(const struct tmh_engine* eng);
 
 /* Device math probes for parity tests: out[i] = f(a, x[i]) with

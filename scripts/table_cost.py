@@ -4,7 +4,7 @@ kernel) of the statistics-only expansion and of the expansions with a table, sam
 same window, same process, the runs alternating.
 
     python scripts/table_cost.py --kind intervals|registers|demand|storage|battery|battery_fleet|battery_sweep|dispatch|dispatch_sweep|schedule
-                                        |dispatch_fleet|schedule_fleet
+                                        |dispatch_fleet|schedule_fleet|schedule_sweep
                                  [--variants 5] [--rules 1] [--chains 65536] [--steps 86400]
                                  [--interval 900] [--rounds 5] [--precision fp32]
                                  [--start "2019-09-05 00:00:00"] [--out FILE.json]
@@ -55,6 +55,13 @@ The runs of a kind:
              and 10), and the fleet curtails.
   schedule_fleet: OUT_SCHEDULE and OUT_SCHEDULE_FLEET, schedule's setting (--rules 1|4) -- the schedule alone and with
              the dispatch fleet series; dispatch_fleet's checks.
+  schedule_sweep: OUT_SCHEDULE and OUT_SCHEDULE_SWEEP, schedule's setting with --rules 4, no statistics -- the unchanged
+             schedule kind and the schedule sweep over --variants K variants: the four hourly rules with the thresholds,
+             the limit and the grid-charge power scaled by factors spread over [0.6, 1.4] (the hold rule's thresholds stay
+             at the range's end), variant v's array the hourly array rotated by v hours against the middle variant's.
+             The middle variant is the schedule run itself: its table and soc are the schedule kind's bit for bit;
+             columns 0-3 agree in every variant and every variant keeps the table's identities.  The yardstick is K x
+             the schedule kind's median: ratio_sweep_k_schedule likewise.
 Every run but the sweeps' has the same statistics beside its table.  The three launches of a battery-family table (map
 pass, scan, replay pass) are timed separately as well (TMH_K_STORAGE_*), inside the TMH_K_EXPAND span.  The script
 checks each run's variant and launch counts, the kind's identities (on the warm-up round's tables), that the
@@ -88,10 +95,11 @@ RUNS = {
     "schedule": (("dispatch", "dispatch"), ("schedule", "schedule")),
     "dispatch_fleet": (("dispatch", "dispatch"), ("dispatch_fleet", "dispatch_fleet")),
     "schedule_fleet": (("schedule", "schedule"), ("schedule_fleet", "schedule_fleet")),
+    "schedule_sweep": (("schedule", "schedule"), ("schedule_sweep", "schedule_sweep")),
 }
 # the tables of the battery family (fp64 engines) and their three launches: _lib.K_STORAGE_<PART>
 FAMILY = ("storage", "battery", "battery_fleet", "battery_sweep", "dispatch", "dispatch_sweep", "schedule", "dispatch_fleet",
-          "schedule_fleet")
+          "schedule_fleet", "schedule_sweep")
 PARTS = ("map", "scan", "replay")
 SHORT = {"stats_only": "stats", "battery_fleet": "fleet", "dispatch_fleet": "fleet", "schedule_fleet": "fleet"}   # labels as the ratios' keys name them
 
@@ -373,9 +381,49 @@ def schedule_fleet_kind(a, battery, lossy):
                 keys=dict(modules=a.modules, battery=lossy, n_rules=a.rules, rules=rules, rule_of_interval=roi.tolist()))
 
 
+def schedule_sweep_kind(a, battery, lossy):
+    """The schedule kind (four hourly rules) and the schedule sweep over a.variants scaled rule sets and rotated arrays."""
+    import numpy as np
+    K = a.variants
+    mid = (K - 1) // 2
+    fac = [0.6 + 0.8 * v / (K - 1) for v in range(K)] if K > 1 else [1.0]
+    fac[mid] = 1.0
+    if a.rules != 4:
+        sys.exit("--kind schedule_sweep: --rules 4")
+    _, rules, roi = schedule_rules(a)
+    top = 32768.0   # the range's end (2^27 in the series' units): a hold rule's thresholds
+    srules = [{k: [min(w * f, top) for f in fac] for k, w in rule.items()} for rule in rules]
+    hours = np.arange(len(roi)) * a.interval // 3600
+    arrays = np.stack([((hours + v - mid) % 4).astype(np.uint8) for v in range(K)])
+    assert np.array_equal(arrays[mid], roi)
+
+    def check(sc, sw):   # the warm-up round's tables: the middle variant is the kind's, columns 0-3 every variant's
+        import torch
+        assert torch.equal(sw.raw[mid], sc.raw) and torch.equal(sw.soc[mid], sc.soc)
+        for v in range(K):
+            t = sw.raw[v]
+            assert torch.equal(t[:, :4], sc.raw[:, :4]) and bool((t[:, 4:8] >= 0).all()) and bool((t[:, 9:11] >= 0).all())
+            assert torch.equal(t[:, 4] - t[:, 5], t[:, 1] - t[:, 0] + t[:, 6] - t[:, 7] + t[:, 10])
+            assert torch.equal(t[:, 11] != 0, t[:, 2] > 0) and torch.equal(t[:, 12] != 0, t[:, 2] > 0)
+            r = torch.from_numpy(arrays[v].astype(np.int64)).to(t.device)
+            assert not bool(t[r == 1, 7].any()) and int(t[r == 1, 6].sum()) > 0      # the grid rule never discharges
+            assert not bool(t[r == 2, 6].any()) and not bool(t[r == 2, 7].any())     # hold
+            assert v == mid or not torch.equal(t[:, 4:], sc.raw[:, 4:])
+        s = sc.raw
+        assert int(s[:, 6].sum()) > 0 and int(s[:, 7].sum()) > 0 and int(s[:, 10].sum()) > 0
+        return dict(import_over_schedule=[int(sw.raw[v][:, 4].sum()) / int(s[:, 4].sum()) for v in range(K)],
+                    launch_groups=sw.groups)
+
+    return dict(runs=(("schedule", "schedule", dict(lossy, rules=rules, rule_of_interval=roi)),
+                      ("schedule_sweep", "schedule_sweep", dict(lossy, n_variants=K, rules=srules, rule_of_interval=arrays))),
+                stats=False, check=check, derived=sweep_yardstick(K, "schedule", "schedule_sweep"),
+                keys=dict(modules=a.modules, battery=lossy, variants=K, n_rules=a.rules, factors=fac, rules=rules,
+                          rule_of_interval=roi.tolist()))
+
+
 KINDS = {**{kind: table_kind for kind in RUNS}, "battery_sweep": battery_sweep_kind, "dispatch": dispatch_kind,
          "dispatch_sweep": dispatch_sweep_kind, "schedule": schedule_kind, "dispatch_fleet": dispatch_fleet_kind,
-         "schedule_fleet": schedule_fleet_kind}
+         "schedule_fleet": schedule_fleet_kind, "schedule_sweep": schedule_sweep_kind}
 
 
 def assemble(a, row, t, pt, found, device, build_stamp):
@@ -417,8 +465,8 @@ def parse_args(argv=None):
     ap.add_argument("--charge-eff", type=float, default=0.95)
     ap.add_argument("--discharge-eff", type=float, default=0.95)
     ap.add_argument("--standby-w", type=float, default=2.0)
-    ap.add_argument("--variants", type=int, default=5, help="--kind battery_sweep, dispatch_sweep: the variants per chain")
-    ap.add_argument("--rules", type=int, default=1, help="--kind schedule, schedule_fleet: 1 (the dispatch kind's rule) or 4 hourly rules")
+    ap.add_argument("--variants", type=int, default=5, help="--kind battery_sweep, dispatch_sweep, schedule_sweep: the variants per chain")
+    ap.add_argument("--rules", type=int, default=1, help="--kind schedule, schedule_fleet: 1 (the dispatch kind's rule) or 4 hourly rules; schedule_sweep: 4")
     ap.add_argument("--charge-above-w", type=float, default=500.0, help="--kind dispatch: the charge threshold")
     ap.add_argument("--discharge-above-w", type=float, default=200.0, help="--kind dispatch: the discharge threshold")
     ap.add_argument("--feed-in-limit-w", type=float, default=1000.0, help="--kind dispatch: the feed-in limit")

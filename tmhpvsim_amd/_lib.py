@@ -122,6 +122,16 @@ class Schedule(C.Structure):
                 ("params", C.c_void_p), ("rule_of_interval", C.c_void_p), ("n_rules", C.c_uint32)]
 
 
+class ScheduleSweep(C.Structure):
+    """tmh_schedule_sweep: the schedule sweep's tables [n_variants][n_intervals][13][ld] (tmh_intervals of variant
+    0), the variants' state of charge [n_variants][ld], the work buffer, the parameters [n_variants][6 + 4 *
+    n_rules][ld] and the variants' rule arrays, uint8 [n_variants][n_intervals] (tmh_set_schedule_sweep).  n_variants
+    takes tmh_schedule's tail padding: the two structs have one size."""
+    _fields_ = [("table", Intervals), ("soc", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t),
+                ("params", C.c_void_p), ("rule_of_interval", C.c_void_p), ("n_rules", C.c_uint32),
+                ("n_variants", C.c_uint32)]
+
+
 EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_bytes", "tmh_state_offsets", "tmh_plan_bytes",
            "tmh_scratch_bytes", "tmh_engine_scratch_bytes", "tmh_workspace_bytes", "tmh_engine_create", "tmh_engine_destroy", "tmh_engine_path",
            "tmh_init", "tmh_run", "tmh_plan", "tmh_step", "tmh_probe", "tmh_profile_enable", "tmh_profile_read",
@@ -132,7 +142,8 @@ EXPORTS = ["tmh_abi_version", "tmh_last_error", "tmh_build_stamp", "tmh_state_by
            "tmh_set_series", "tmh_series_frac_bits", "tmh_series_max_w", "tmh_test_guard_records", "tmh_set_intervals",
            "tmh_set_registers", "tmh_set_demand", "tmh_set_storage", "tmh_storage_work_bytes", "tmh_set_battery", "tmh_set_battery_fleet",
            "tmh_set_battery_sweep", "tmh_battery_sweep_work_bytes", "tmh_set_dispatch", "tmh_probe_pv",
-           "tmh_set_dispatch_sweep", "tmh_set_schedule", "tmh_set_dispatch_fleet"]
+           "tmh_set_dispatch_sweep", "tmh_set_schedule", "tmh_set_dispatch_fleet",
+           "tmh_set_schedule_sweep"]
 K_EXPAND, K_SEGMENTS, K_CANDIDATES, K_STEP = 0, 1, 2, 3
 K_STORAGE_MAP, K_STORAGE_SCAN, K_STORAGE_REPLAY = 4, 5, 6   # battery storage's three launches (inside K_EXPAND)
 WALK_DRAWS, WALK_SEGMENTS = 1, 2
@@ -154,6 +165,8 @@ OUT_SCHEDULE = 13       # scheduled dispatch (tmh_set_schedule)
 SCHEDULE_RULES_MAX = 8  # TMH_SCHEDULE_RULES_MAX
 OUT_DISPATCH_FLEET = 14  # battery dispatch with the dispatch fleet series (tmh_set_dispatch_fleet)
 OUT_SCHEDULE_FLEET = 15  # the schedule with it
+OUT_SCHEDULE_SWEEP = 64  # the schedule sweep (tmh_set_schedule_sweep): the first value above OUT_FP64
+SCHEDULE_SWEEP_MAX = 16  # TMH_SCHEDULE_SWEEP_MAX
 
 _lib = None
 
@@ -265,6 +278,8 @@ def load():
     L.tmh_set_dispatch_sweep.restype = C.c_int
     L.tmh_set_schedule.argtypes = [p, C.POINTER(Schedule)]
     L.tmh_set_schedule.restype = C.c_int
+    L.tmh_set_schedule_sweep.argtypes = [p, C.POINTER(ScheduleSweep)]
+    L.tmh_set_schedule_sweep.restype = C.c_int
     L.tmh_set_dispatch_fleet.argtypes = [p, C.POINTER(Series)]   # (tmh_series with nine columns per row)
     L.tmh_set_dispatch_fleet.restype = C.c_int
     L.tmh_battery_sweep_work_bytes.argtypes = [u32, u32, u32]

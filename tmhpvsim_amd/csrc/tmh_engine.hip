@@ -98,6 +98,13 @@ constexpr int EXP_WAVES_SWEEP_MAP = 2, EXP_WAVES_SWEEP_REPLAY = 2;
 constexpr int EXP_WAVES_DSWEEP_MAP = 2, EXP_WAVES_DSWEEP_REPLAY = 2;
 constexpr bool out_sweep(int out) { return (out & OUT_SWEEP) != 0; }
 constexpr bool out_dsweep(int out) { return (out & OUT_SWEEP) != 0 && (out & OUT_DISPATCH) != 0; }
+//  the schedule sweep's two passes (fp64 single-site, SSWEEP_KV = 4 variants per lane), in 256-chain workgroups: 2 = at
+//    most 256 VGPRs; the map pass takes 242 and does not spill, the replay takes all 256 and spills 33 (96 B of scratch):
+//    the grid-charge power per variant and the reload's live values on top of the dispatch sweep's.  Three variants per
+//    lane fit (249 VGPRs, no spill) and ran slower, 277.7 ms against 259.6 ms at K = 5 and 424.7 ms against 345.0 ms at
+//    K = 8; two take 218 VGPRs, do not spill either and run one more pass than three: not timed (Schedule sweep)
+constexpr int EXP_WAVES_SSWEEP_MAP = 2, EXP_WAVES_SSWEEP_REPLAY = 2;
+constexpr bool out_ssweep(int out) { return (out & OUT_SWEEP) != 0 && (out & OUT_SCHED) != 0; }
 constexpr bool out_lossy_replay(int out) { return out_base(out) == OUT_STORAGE && (out & OUT_LOSSY) && !(out & OUT_MAP); }
 //  battery dispatch's replay pass (fp64 single-site) runs at the battery kind's shape, EXP_WAVES_LOSSY: one more
 //    64-bit sum, the two running peaks with their seconds and three more parameters live across the per-second
@@ -2058,7 +2065,8 @@ template <typename R, int OUT, bool SITES>
 constexpr int exp_waves()
 {
     return SITES                             ? EXP_WAVES_SITES
-           : out_dsweep(OUT)                  ? ((OUT & OUT_MAP) ? EXP_WAVES_DSWEEP_MAP : EXP_WAVES_DSWEEP_REPLAY)
+           : out_ssweep(OUT)                  ? ((OUT & OUT_MAP) ? EXP_WAVES_SSWEEP_MAP : EXP_WAVES_SSWEEP_REPLAY)
+           : out_dsweep(OUT)                 ? ((OUT & OUT_MAP) ? EXP_WAVES_DSWEEP_MAP : EXP_WAVES_DSWEEP_REPLAY)
            : out_sweep(OUT)                   ? ((OUT & OUT_MAP) ? EXP_WAVES_SWEEP_MAP : EXP_WAVES_SWEEP_REPLAY)
            : out_dfleet(OUT)                  ? ((OUT & OUT_SCHED) ? EXP_WAVES_SFLEET : EXP_WAVES_DFLEET)
            : out_lossy_replay(OUT)            ? EXP_WAVES_LOSSY
@@ -2339,10 +2347,16 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // intervals' pieces already; the map pass (PCS below) walks them too, so that a second's rule is its own
     // interval's also inside a four-second group that straddles a boundary, and flushes nothing.
     constexpr bool SCH = (OUT & OUT_SCHED) != 0;
-    static_assert(!SCH || (DSP && !SWP && !SITES), "scheduled dispatch: a flag of battery dispatch's two passes, single site");
-    constexpr int KV = DSW ? DSWEEP_KV : SWP ? SWEEP_KV : 1;
+    // SSW: the schedule sweep, SCH beside the dispatch sweep's two flags and nothing else -- the sweep's shared second,
+    // then the schedule's second of each of KV variants: schedule_ask with the variant's own rule (sw_dsp, sw_g), every
+    // variant's rule reloaded where a piece ends (ssw_rule) from the rule the variant's own array names; a variant's
+    // parameters are swv.rows = 6 + 4 R rows, a run-time count
+    static_assert(!SCH || (DSP && !SITES && (!SWP || (OUT & ~OUT_MAP) == (OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH | OUT_SCHED | OUT_SWEEP))),
+                  "scheduled dispatch: a flag of battery dispatch's two passes or of the dispatch sweep's, single site");
+    constexpr bool SSW = SCH && SWP;
+    constexpr int KV = SSW ? SSWEEP_KV : DSW ? DSWEEP_KV : SWP ? SWEEP_KV : 1;
     constexpr int KD = DSW ? KV : 1;          // the per-variant dispatch state: one unused set elsewhere
-    constexpr int PROWS = DSP ? TMH_DISPATCH_PARAMS : 6;   // a variant's parameter rows
+    constexpr int PROWS = DSP ? TMH_DISPATCH_PARAMS : 6;   // a variant's parameter rows (the schedule sweep: swv.rows)
     static_assert(!STO || sizeof(R) == 8, "battery storage: fp64 engines only (no guard-band seconds)");
     // REG: the import / export registers -- the intervals' pieces, accumulators and flush, with
     // one more accumulator and IVC = 6 columns per cell instead of 4
@@ -2561,7 +2575,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     // inside the array whatever k.)
     int sc_g = 0;
     auto sch_rule = [&](uint32_t k) __attribute__((always_inline)) {
-        if constexpr (SCH) {
+        if constexpr (SCH && !SWP) {
             const uint32_t e = scv.rules[min(k, scv.n_iv - 1u)];
             const uint32_t rule = __builtin_amdgcn_readfirstlane(min(e, scv.n_rules - 1u));
             if (live) {
@@ -2584,11 +2598,37 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
     long long sw_cu[KD];
     int sw_im[KD], sw_xm[KD];
     uint32_t sw_imj[KD], sw_xmj[KD];
+    int sw_g[KD];   // the schedule sweep's: the grid-charge power of the variant's rule in force, as sc_g above
+    // the schedule sweep: a variant's parameters lie this many elements after the one before (PROWS * ld elsewhere)
+    size_t pstride = 0;
+    if constexpr (SSW) pstride = (size_t)swv.rows * ivv.ld;
+    // the schedule sweep: sch_rule for the group -- per variant one byte of its own array at a wave-uniform address
+    // (variant v's array n_iv bytes after v - 1's; the interval index clamped into the array, the entry below the rule
+    // count), then the rule's four rows of the variant's parameters; variants nv .. KV - 1 are not loaded
+    auto ssw_rule = [&](uint32_t k) __attribute__((always_inline)) {
+        if constexpr (SSW) {
+            const uint32_t kk = min(k, scv.n_iv - 1u);
+#pragma unroll
+            for (int v = 0; v < KV; ++v) {
+                if ((uint32_t)v < swv.nv) {
+                    const uint32_t e = scv.rules[(size_t)v * scv.n_iv + kk];
+                    const uint32_t rule = __builtin_amdgcn_readfirstlane(min(e, scv.n_rules - 1u));
+                    if (live) {
+                        const ScheduleRule sr = schedule_load(batp + (size_t)v * pstride, ivv.ld, gid(kp.ids, c), rule);
+                        sw_dsp[v] = sr.dp;
+                        sw_g[v] = sr.g;
+                    }
+                }
+            }
+        }
+    };
     if constexpr (DSW) {
 #pragma unroll
         for (int v = 0; v < KV; ++v) {
             sw_dsp[v] = dispatch_none();
-            if (live && (uint32_t)v < swv.nv) sw_dsp[v] = dispatch_load(batp + (size_t)v * PROWS * ivv.ld, ivv.ld, gid(kp.ids, c));
+            sw_g[v] = 0;
+            if constexpr (!SSW)
+                if (live && (uint32_t)v < swv.nv) sw_dsp[v] = dispatch_load(batp + (size_t)v * PROWS * ivv.ld, ivv.ld, gid(kp.ids, c));
             sw_cu[v] = 0;
             sw_im[v] = sw_xm[v] = 0;
             sw_imj[v] = sw_xmj[v] = 0;
@@ -2600,7 +2640,11 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             const bool on = live && (uint32_t)v < swv.nv;
             sw_map[v] = soc_identity();
             sw_bp[v] = battery_none();
-            if (on) sw_bp[v] = battery_load(batp + (size_t)v * PROWS * ivv.ld, ivv.ld, gid(kp.ids, c));
+            if constexpr (SSW) {
+                if (on) sw_bp[v] = battery_load(batp + (size_t)v * pstride, ivv.ld, gid(kp.ids, c));
+            } else {
+                if (on) sw_bp[v] = battery_load(batp + (size_t)v * PROWS * ivv.ld, ivv.ld, gid(kp.ids, c));
+            }
             sw_hi[v] = max(sw_bp[v].cap - (long long)sw_bp[v].sigma, 0ll);
             sw_x[v] = 0;
             if constexpr (REP)
@@ -2629,6 +2673,7 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
         iv_next = __builtin_amdgcn_readfirstlane((uint32_t)min(nb, (uint64_t)j1));
     }
     sch_rule(iv_k);
+    ssw_rule(iv_k);
     auto iv_flush = [&](uint32_t pa, uint32_t pb) __attribute__((always_inline)) {
         if constexpr (SWP && REP) {
             // the sweep: the piece's ten columns into every variant's table -- columns 0-3 the same in each,
@@ -2819,7 +2864,9 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                     if (v > 0 && (uint32_t)v >= swv.nv) continue;   // a short group's missing variants: a scalar branch
                     const BatteryParams& p = sw_bp[v];
                     int ab;
-                    if constexpr (DSW) ab = dispatch_ask(d, sw_dsp[v].tc, sw_dsp[v].td, p.pc, p.pd);
+                    // (the schedule sweep: the variant's rule of the interval, its grid-charge power on top of the ask)
+                    if constexpr (SSW) ab = schedule_ask(d, sw_dsp[v].tc, sw_dsp[v].td, sw_g[v], p.pc, p.pd);
+                    else if constexpr (DSW) ab = dispatch_ask(d, sw_dsp[v].tc, sw_dsp[v].td, p.pc, p.pd);
                     else ab = soc_ask(d, p.pc, p.pd);
                     const int s = bat_stored(ab, p);
                     if constexpr (MAP) {
@@ -2835,6 +2882,8 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
                             // battery dispatch's second (below) of the variant: the deficit left at the meter is the
                             // import, the surplus fed in up to the variant's limit and curtailed above it; a night
                             // second's literal pv = 0 has no surplus, so that code stays out of it
+                            // (the schedule sweep under a grid-charging rule: b >= 0 >= d there, beyond [d, 0], and r = d - b
+                            // <= 0 all the same -- no surplus either, the night second charges and the import holds what it buys)
                             const int r = d - bm, vi = ok ? max(-r, 0) : 0;
                             sw_imj[v] = vi > sw_im[v] ? jb : sw_imj[v];
                             sw_im[v] = max(vi, sw_im[v]);
@@ -3179,7 +3228,10 @@ __device__ __forceinline__ void expand_tile(uint32_t b, uint32_t cblk, const KPa
             }
             // scheduled dispatch: the next piece lies in interval iv_k, under its rule
             if constexpr (SCH)
-                if (j < j1) sch_rule(iv_k);
+                if (j < j1) {
+                    sch_rule(iv_k);
+                    ssw_rule(iv_k);
+                }
         } while (PCS && j < j1);
     };
     // (fp32 single-site only: in the fp64 and per-site kernels, which sit at their
@@ -3244,11 +3296,12 @@ using OutView = std::conditional_t<out_base(OUT) == OUT_SERIES, SeriesView,
                                                           out_base(OUT) == OUT_DEMAND,
                                                       IntervalsView,
                                                       std::conditional_t<out_base(OUT) == OUT_STORAGE,
+                                                                         std::conditional_t<(OUT & OUT_SCHED) != 0 && (OUT & OUT_SWEEP) != 0, ScheduleSweepView,
                                                                          std::conditional_t<(OUT & OUT_SCHED) != 0 && (OUT & OUT_FLEET) != 0, ScheduleFleetView,
                                                                          std::conditional_t<(OUT & OUT_SCHED) != 0, ScheduleView,
                                                                          std::conditional_t<(OUT & OUT_SWEEP) != 0, SweepView,
                                                                          std::conditional_t<(OUT & OUT_FLEET) != 0, BatteryFleetView,
-                                                                                            std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>>>>>,
+                                                                                            std::conditional_t<(OUT & OUT_LOSSY) != 0, BatteryView, StorageView>>>>>>,
                                                                          TraceView>>>;
 template <typename R, int OUT, bool SITES>
 __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES>())) void expand_kernel(KParams kp, DrawParams dp, StateView st, uint64_t chain0,
@@ -3270,6 +3323,13 @@ __global__ __launch_bounds__((exp_wg<R, OUT, SITES>()), (exp_waves<R, OUT, SITES
     const long long* batp = nullptr;
     SweepView swv{};
     ScheduleView scv{};
+    if constexpr ((OUT & OUT_SCHED) != 0 && (OUT & OUT_SWEEP) != 0) {   // the schedule sweep: the dispatch sweep's view + the group's arrays
+        swv = ov.sw;
+        scv = ScheduleView{ov.sw.bt, ov.rules, ov.n_iv, ov.n_rules};
+        sto = ov.sw.bt.st;
+        ivv = ov.sw.bt.st.iv;
+        batp = ov.sw.bt.params;
+    } else
     if constexpr ((OUT & OUT_SCHED) != 0 && (OUT & OUT_FLEET) != 0) {   // the schedule with the dispatch fleet series: its view + the series'
         scv = ov.sc;
         sto = ov.sc.bt.st;
@@ -4020,7 +4080,7 @@ void with_real(bool f64, F&& f)
 // Its rows also say what its one setter (set_battery_table), its one refusal (check_interval_tables) and its one
 // launch sequence (phase_expand) differ in from kind to kind; a new kind of the family is a row, its public struct
 // and the few lines of its exported setter that copy the struct into a BatteryDesc.
-enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_DISPATCH_SWEEP, TBL_SCHEDULE, TBL_KINDS };
+enum TableKind { TBL_INTERVALS, TBL_REGISTERS, TBL_DEMAND, TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_DISPATCH_SWEEP, TBL_SCHEDULE, TBL_SCHEDULE_SWEEP, TBL_KINDS };
 struct TableKindInfo {
     int cols, out;      // out: TMH_OUT_* as tmh_engine_last_expand reports it (the expansion's OutKind but for the battery family)
     const char* what;   // in the setter's and the checks' messages
@@ -4037,6 +4097,7 @@ struct TableKindInfo {
     const char* no_fleet = nullptr;
     const char* soc_shape = "";      // after "soc buffer" in the setter's refusal
     const char* params_shape = "";   // the params tensor's shape in the setter's refusal
+    int variants_max = 0;            // a kind with rules and variants: the most variants (count_max is then the rules')
 };
 constexpr int OUT_BAT = OUT_STORAGE | OUT_LOSSY, OUT_DSP = OUT_BAT | OUT_DISPATCH;
 constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
@@ -4062,6 +4123,11 @@ constexpr TableKindInfo TABLE_KINDS[TBL_KINDS] = {
     // and grid charging
     {TMH_DISPATCH_COLS, TMH_OUT_SCHEDULE, "schedule tables", "the schedule", OUT_DSP | OUT_SCHED, 6, TMH_SCHEDULE_RULE_PARAMS, 1,
      TMH_SCHEDULE_RULES_MAX, "n_rules", true, true, "", "", "[6 + 4 * n_rules][ld]"},
+    // the schedule sweep (tmh_schedule_sweep): n_variants (battery, rule sets, rule array) variants per chain,
+    // SSWEEP_KV of them per launch
+    {TMH_DISPATCH_COLS, TMH_OUT_SCHEDULE_SWEEP, "schedule sweep tables", "the schedule sweep", OUT_DSP | OUT_SCHED | OUT_SWEEP, 6,
+     TMH_SCHEDULE_RULE_PARAMS, SSWEEP_KV, TMH_SCHEDULE_RULES_MAX, "n_rules", true, true, "", " [n_variants][ld]",
+     "[n_variants][6 + 4 * n_rules][ld]", TMH_SCHEDULE_SWEEP_MAX},
 };
 static_assert(TMH_DISPATCH_PARAMS == 9 && TMH_SCHEDULE_RULE_PARAMS == 4, "the params shapes in TABLE_KINDS' words");
 static_assert(TMH_OUT_BATTERY > out_base(~0) && TMH_OUT_BATTERY < TMH_OUT_SITES, "TMH_OUT_BATTERY: a code of its own below the flags");
@@ -4072,7 +4138,11 @@ static_assert(TMH_OUT_DISPATCH_SWEEP > TMH_OUT_DISPATCH && TMH_OUT_DISPATCH_SWEE
 static_assert(TMH_OUT_SCHEDULE > TMH_OUT_DISPATCH_SWEEP && TMH_OUT_SCHEDULE < TMH_OUT_SITES, "TMH_OUT_SCHEDULE: likewise");
 static_assert(TMH_OUT_DISPATCH_FLEET > TMH_OUT_SCHEDULE && TMH_OUT_SCHEDULE_FLEET == TMH_OUT_DISPATCH_FLEET + 1 &&
                   TMH_OUT_SCHEDULE_FLEET == TMH_OUT_SITES - 1, "the dispatch fleet series' codes: the last two below the flags");
+static_assert(TMH_OUT_SCHEDULE_SWEEP > (TMH_OUT_SITES | TMH_OUT_FP64) && (TMH_OUT_SCHEDULE_SWEEP & (TMH_OUT_SITES | TMH_OUT_FP64)) == 0,
+              "TMH_OUT_SCHEDULE_SWEEP: codes 0-15 are used up; above both flags and not a combination of them");
 static_assert(DSWEEP_KV >= 2 && DSWEEP_KV <= TMH_DISPATCH_SWEEP_MAX, "a group of one variant runs battery dispatch's own kernels");
+static_assert(SSWEEP_KV >= 2 && SSWEEP_KV <= TMH_SCHEDULE_SWEEP_MAX, "a group of one variant runs scheduled dispatch's own kernels");
+static_assert(sizeof(tmh_schedule_sweep) == sizeof(tmh_schedule), "n_variants takes tmh_schedule's tail padding");
 constexpr bool table_cols_ok()
 {
     for (int k = 0; k < TBL_KINDS; ++k)
@@ -4619,6 +4689,8 @@ static int set_battery_table(tmh_engine* eng, TableKind kind, const tmh_interval
         return fail(TMH_E_INVAL, "%s: interval_s %u > 2^23 - 1 (the SoC key holds the second's offset above 40 bits)", what,
                     table->interval_s);
     const uint32_t count = ki.rule_rows ? d.n_rules : d.n_variants;
+    if (ki.variants_max && (d.n_variants == 0 || d.n_variants > (uint32_t)ki.variants_max))
+        return fail(TMH_E_INVAL, "%s: n_variants %u outside [1, %d]", what, d.n_variants, ki.variants_max);
     if (ki.count_max && (count == 0 || count > (uint32_t)ki.count_max))
         return fail(TMH_E_INVAL, "%s: %s %u outside [1, %d]", what, ki.count, count, ki.count_max);
     if (!d.soc || ((uintptr_t)d.soc & 7)) return fail(TMH_E_INVAL, "%s need an 8-byte aligned soc buffer%s", what, ki.soc_shape);
@@ -4633,7 +4705,8 @@ static int set_battery_table(tmh_engine* eng, TableKind kind, const tmh_interval
         return fail(TMH_E_INVAL, "%s need an 8-byte aligned params tensor %s", what, ki.params_shape);
     }
     if (ki.rule_rows && !d.rule_of_interval)
-        return fail(TMH_E_INVAL, "%s need a rule_of_interval array [n_intervals] (the schedule: each interval's rule)", what);
+        return fail(TMH_E_INVAL, "%s need a rule_of_interval array %s[n_intervals] (the schedule: each interval's rule)", what,
+                    ki.variants_max ? "[n_variants]" : "");
     if (ki.floor && d.work_bytes < tmh_battery_sweep_work_bytes(1, 1, d.n_variants))
         return fail(TMH_E_INVAL, "%s work buffer too small: %zu < %zu", what, d.work_bytes,
                     tmh_battery_sweep_work_bytes(1, 1, d.n_variants));
@@ -4684,6 +4757,13 @@ int tmh_set_schedule(struct tmh_engine* eng, const tmh_schedule* sc)
     BatteryDesc d(sc->soc, sc->work, sc->work_bytes, sc->params);
     d.rule_of_interval = sc->rule_of_interval, d.n_rules = sc->n_rules;
     return set_battery_table(eng, TBL_SCHEDULE, &sc->table, d);
+}
+int tmh_set_schedule_sweep(struct tmh_engine* eng, const tmh_schedule_sweep* sw)
+{
+    if (!sw) return set_battery_table(eng, TBL_SCHEDULE_SWEEP, nullptr, {});
+    BatteryDesc d(sw->soc, sw->work, sw->work_bytes, sw->params);
+    d.rule_of_interval = sw->rule_of_interval, d.n_rules = sw->n_rules, d.n_variants = sw->n_variants;
+    return set_battery_table(eng, TBL_SCHEDULE_SWEEP, &sw->table, d);
 }
 
 // the battery fleet series: tmh_set_series' struct cases in its own words (the struct first, as the tables'
@@ -4814,7 +4894,7 @@ static int check_interval_tables(const tmh_engine* eng, uint32_t n_chains, int64
             return fail(TMH_E_INVAL, "%s work buffer too small for this window: %zu < %zu", what, d.work_bytes, need);
         return TMH_OK;
     };
-    for (int k = TBL_SCHEDULE; k >= TBL_DISPATCH; --k)
+    for (int k = TBL_SCHEDULE_SWEEP; k >= TBL_DISPATCH; --k)
         if (int rc = runs_alone(k)) return rc;
     if (eng->has_series) return fail(TMH_E_INVAL, "%s and a fleet series are both set: one of the two per engine", what);
     for (int k = TBL_SWEEP; k >= TBL_STORAGE; --k)
@@ -5210,7 +5290,7 @@ static int phase_expand(const StepCtx& c)
                 eng->close(TMH_K_STORAGE_REPLAY, t, c.s);
             };
             if (table != TBL_KINDS && TABLE_KINDS[table].replay) {
-                with_value<TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_DISPATCH_SWEEP, TBL_SCHEDULE>(table, [&](auto k) {
+                with_value<TBL_STORAGE, TBL_BATTERY, TBL_SWEEP, TBL_DISPATCH, TBL_DISPATCH_SWEEP, TBL_SCHEDULE, TBL_SCHEDULE_SWEEP>(table, [&](auto k) {
                     constexpr int K = decltype(k)::value;
                     constexpr TableKindInfo ki = TABLE_KINDS[K];
                     constexpr int O = ki.replay;
@@ -5236,6 +5316,16 @@ static int phase_expand(const StepCtx& c)
                             const StatsView gsv = v0 == 0 ? sv : StatsView{};
                             if constexpr (O == OUT_STORAGE) {
                                 passes(out_c<O>, stv, btv, soc, nv, wstride, rows, gsv);
+                            } else if constexpr ((O & OUT_SCHED) != 0 && (O & OUT_SWEEP) != 0) {
+                                // the schedule sweep: the group's first variant's array row; a group of one variant is
+                                // the schedule itself on that row, at its own instantiations' occupancy
+                                const uint8_t* const arr = d.rule_of_interval + (size_t)v0 * n_iv;
+                                if (nv == 1)
+                                    passes(out_c<O & ~OUT_SWEEP>, ScheduleView{btv, arr, (uint32_t)n_iv, d.n_rules}, btv, soc, nv, wstride,
+                                           rows, gsv);
+                                else
+                                    passes(out_c<O>, ScheduleSweepView{SweepView{btv, tstride, wstride, nv, rows}, arr, (uint32_t)n_iv, d.n_rules},
+                                           btv, soc, nv, wstride, rows, gsv);
                             } else if constexpr ((O & OUT_SCHED) != 0) {
                                 passes(out_c<O>, ScheduleView{btv, d.rule_of_interval, (uint32_t)n_iv, d.n_rules}, btv, soc, nv, wstride,
                                        rows, gsv);

@@ -1589,7 +1589,9 @@ enum OutKind : int {
     OUT_DISPATCH = 512,
     // flag on OUT_STORAGE | OUT_LOSSY | OUT_DISPATCH, both passes, single site: scheduled dispatch (tmh_schedule) --
     // the rule (Tc, Td, L and the grid-charge power G) reloaded at every metering-interval boundary from the
-    // rule the shared array names for the interval; the map pass walks the intervals' pieces too; TMH_OUT_SCHEDULE
+    // rule the shared array names for the interval; the map pass walks the intervals' pieces too; TMH_OUT_SCHEDULE.
+    // With OUT_SWEEP: the schedule sweep (tmh_schedule_sweep) -- the dispatch sweep's variants, each under the rule
+    // its own array names for the interval; TMH_OUT_SCHEDULE_SWEEP
     OUT_SCHED = 1024
 };
 constexpr int out_base(int out) { return out & 7; }
@@ -1813,10 +1815,25 @@ constexpr int SWEEP_KV = 4;
 // peak registers per variant: DESIGN.md, Dispatch sweep).  A group of one variant runs battery dispatch's own
 // instantiations.
 constexpr int DSWEEP_KV = 4;
+// (rows: a variant's parameter rows where they are a run-time count, the schedule sweep's 6 + 4 R; 0 in the two
+// sweeps above, whose rows are compile-time constants)
 struct SweepView {
     BatteryView bt;
     uint64_t tstride, wstride;
-    uint32_t nv, pad;
+    uint32_t nv, rows;
+};
+// The schedule sweep (OUT_SWEEP | OUT_DISPATCH | OUT_SCHED, tmh_schedule_sweep): the dispatch sweep's view with
+// sw.rows = 6 + 4 R parameter rows per variant, and the rule array of the group's first variant -- variant v's
+// n_iv bytes after variant v - 1's; entry and interval index clamped per variant as ScheduleView's.  SSWEEP_KV
+// variants per lane and launch, a count of this kind's own: beside the dispatch sweep's state a variant carries
+// its grid-charge power, and the reload at a piece's end keeps the array's and the parameters' addresses live
+// (Schedule sweep).  A group of one variant runs scheduled dispatch's own instantiations on that
+// variant's array row.
+constexpr int SSWEEP_KV = 4;
+struct ScheduleSweepView {
+    SweepView sw;
+    const uint8_t* rules;
+    uint32_t n_iv, n_rules;
 };
 // The state of charge (0 <= x < 2^40) in two halves of FLEET_SOC_HALF bits: 32 lanes of either fit an int32 partial
 constexpr int FLEET_SOC_HALF = 20;

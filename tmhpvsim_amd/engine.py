@@ -127,6 +127,9 @@ for _kind, _t in _TABLES.items():   # no table beside battery storage, whichever
     if _kind != "schedule":
         _t["enable_excludes"] += (("_schedule", "the schedule is enabled: one table output per sim "
                                                 "(the schedule runs alone)"),)
+    # (enable_schedule_sweep: the schedule sweep, as the two sweeps above; the last words of every kind's list)
+    _t["enable_excludes"] += (("_schedule_sweep", "the schedule sweep is enabled: one table output per sim "
+                                                  "(the schedule sweep runs alone)"),)
 # the sweeps: a table per variant; what they refuse beside them at enable_<kind> is _enable_battery's to say
 _TABLES["battery_sweep"] = dict(
     noun="battery sweep tables", name="the battery sweep", enable_excludes=(), run_excludes=(),
@@ -136,6 +139,10 @@ _TABLES["dispatch_sweep"] = dict(
     noun="dispatch sweep tables", name="the dispatch sweep", enable_excludes=(), run_excludes=(),
     no_trace="a dispatch sweep run takes no traces (trace=()): run the rules over the traces instead "
              "(dispatch.sweep_from_traces)")
+_TABLES["schedule_sweep"] = dict(
+    noun="schedule sweep tables", name="the schedule sweep", enable_excludes=(), run_excludes=(),
+    no_trace="a schedule sweep run takes no traces (trace=()): run the variants over the traces instead "
+             "(schedule.sweep_from_traces)")
 
 # The battery family: the kinds of _TABLES that carry a state of charge per chain (`sim.soc`) through a work buffer,
 # one of them per sim, through one enabler (_enable_battery), one setter (_set_battery) and one work buffer
@@ -157,6 +164,8 @@ _BATTERIES = {
                           params="battery_params", desc="_sweep_desc"),
     "dispatch_sweep": dict(mod="dispatch", rows=9, cls=_lib.DispatchSweep, variants=True, one_site=True, window="long",
                            params="dispatch_params", desc="_dsweep_desc"),
+    "schedule_sweep": dict(mod="schedule", rows=None, cls=_lib.ScheduleSweep, variants=True, one_site=True, window="long",
+                           params="schedule_sweep_params", desc="_ssweep_desc"),
 }
 
 
@@ -261,6 +270,8 @@ class BatchedSim:
         # parameters int64 [6, n] (enable_battery), [9, n] (enable_dispatch), [6 + 4 R, n] (enable_schedule) or
         # [K, 6 / 9, n] (the sweeps); schedule_rules uint8 [n_intervals]: the rule of each of the table's intervals
         self.soc = self.battery_params = self.dispatch_params = self.schedule_params = self.schedule_rules = None
+        # the schedule sweep's parameters int64 [K, 6 + 4 R, n] and rule arrays uint8 [K, n_intervals]
+        self.schedule_sweep_params = self.schedule_sweep_rules = None
         self._battery_args = self._battery_work = None   # (soc, params, the struct's last fields), the work buffer
         for t in _BATTERIES.values():
             setattr(self, t["desc"], None)
@@ -460,10 +471,10 @@ class BatchedSim:
     # ------------------------------------------------------------------ the battery family
     def _enable_battery(self, kind, n_steps, interval_s, step0, buffer, soc, params, soc0_wh, quantize, n_variants=None,
                         last=lambda host: ()):
-        """enable_storage, enable_battery, enable_dispatch, enable_schedule and the two sweeps (_BATTERIES[kind]).
+        """enable_storage, enable_battery, enable_dispatch, enable_schedule and the three sweeps (_BATTERIES[kind]).
         quantize(): the kind's quantities as host parameters, called when no params tensor is given (storage: its
         three integers and the starting state of charge); last(host): the fields of the kind's struct after params
-        (the schedule's rule array and rule count).  A refused call leaves what was enabled before as it was."""
+        (the schedule's and the schedule sweep's rule array and rule count; a sweep's variant count follows them).  A refused call leaves what was enabled before as it was."""
         torch = _torch()
         t, name, label = _BATTERIES[kind], _TABLES[kind]["name"], kind.replace("_", " ")
         if n_steps is None:
@@ -472,7 +483,8 @@ class BatchedSim:
             if getattr(self, "_" + kind) is not None:   # (else soc and the work buffer may be another kind's)
                 self.soc = self._battery_work = self._battery_args = None
                 setattr(self, t["desc"], None)
-                for attr in (t["params"],) + (("schedule_rules",) if kind == "schedule" else ()):
+                for attr in (t["params"],) + (("schedule_rules",) if kind == "schedule" else
+                                              ("schedule_sweep_rules",) if kind == "schedule_sweep" else ()):
                     if attr:
                         setattr(self, attr, None)
             return self._enable_table(kind, None, interval_s, step0, buffer)
@@ -511,7 +523,7 @@ class BatchedSim:
             K = int(host.shape[0])
             if n_variants is not None and int(n_variants) != K:
                 raise ValueError(f"enable_{kind}: n_variants {n_variants} but parameters of {K} variants")
-            tail, shape = (K,), (K, self.n)
+            tail, shape = tuple(last(host)) + (K,), (K, self.n)   # (the variant count: the struct's last field)
         else:
             if rows != 0:
                 tail = last(host)
@@ -544,7 +556,7 @@ class BatchedSim:
         """_enable_table for the sweeps: a table per variant, [K, n_intervals, nc, n], and the variants' parameters and
         state of charge (_battery_args) at the table's ld."""
         torch = _torch()
-        label, (soc, params, (K,)) = kind.replace("_", " "), self._battery_args
+        label, (soc, params, (*_, K)) = kind.replace("_", " "), self._battery_args
         npar, nk = int(params.shape[1]), -(-n_steps // interval_s)
         if buffer is None:
             buffer = torch.zeros(K, nk, nc, self.n, dtype=torch.int64, device=self.device)
@@ -573,7 +585,7 @@ class BatchedSim:
             return setter(self._eng, None)
         torch = _torch()
         soc, params, tail = self._battery_args
-        K = tail[0] if t["variants"] else 1
+        K = tail[-1] if t["variants"] else 1
         if params is not None and not t["variants"] and int(params.stride(0)) != int(table.ld):
             raise ValueError(f"{kind} params row stride {int(params.stride(0))} != the table's ld {int(table.ld)}: "
                              "slice both from tensors of the same width")
@@ -596,7 +608,7 @@ class BatchedSim:
             table = getattr(self, "_" + kind)
             if table is None:
                 continue
-            K = self._battery_args[2][0] if t["variants"] else 1
+            K = self._battery_args[2][-1] if t["variants"] else 1
             need = self.L.tmh_battery_sweep_work_bytes(self.n, int(win), K)
             if self._battery_work.numel() < need:
                 _torch().cuda.synchronize(self.device)   # (launches of earlier runs may still read the old one)
@@ -814,6 +826,68 @@ class BatchedSim:
         _torch().cuda.synchronize(self.device)
         t = self._dispatch_sweep
         return [to_watts(raw, t.interval_s, n_steps=t.n_steps) for raw in self.dispatch_sweep_raw]
+
+    # ------------------------------------------------------------------ the schedule sweep
+    def enable_schedule_sweep(self, n_steps, interval_s=900, *, n_variants=None, capacity_wh=None, charge_w=None,
+                              discharge_w=None, charge_eff=1.0, discharge_eff=1.0, standby_w=0.0, rules=None, params=None,
+                              rule_of_interval=None, n_rules=None, soc0_wh=0.0, soc=None, buffer=None, step0=None):
+        """enable_schedule for K variants per chain in one run (tmhpvsim_amd.schedule, tmh_schedule_sweep): every
+        chain -- the same pv and meter second for second -- under each of K sets of battery, R rule sets and rule
+        array, variant v's table and state of charge bit for bit what enable_schedule gives for its parameters and
+        its array: which tariff a household should take, whether grid charging at night pays under it, which battery
+        to buy.  Each battery quantity and each value in `rules` (enable_schedule's list of R dicts) is a scalar, a
+        sequence of K values (one per variant, uniform over the chains) or a [K, n] array; feed-in limits may be None
+        (schedule.quantize_sweep_params); or pass params, a ready int64 device tensor [K, 6 + 4 R, n]
+        (schedule.check_sweep_params).  rule_of_interval is a uint8 sequence, array or device tensor [n_intervals]
+        (every variant's) or [K, n_intervals] (a tariff per variant: schedule.check_sweep_rules); n_rules, when
+        given, is checked against R.  Returns the raw int64 tensor [K, n_intervals, 13, n]; `sim.soc` is the int64
+        [K, n] state of charge, `sim.schedule_sweep_params` the parameters [K, 6 + 4 R, n] and
+        `sim.schedule_sweep_rules` the uint8 arrays [K, n_intervals] on the device.  buffer, soc, params: tensors of
+        those shapes to use, possibly column slices of wider [.., N] tensors of one width.  fp64 only, no traces, no
+        fleet series of any kind, no other table, no per-chain sites; compaction is allowed.  A refused call leaves
+        what was enabled before as it was.  n_steps=None switches the output off."""
+        from . import schedule
+
+        def quantize():
+            if capacity_wh is None or charge_w is None or discharge_w is None or rules is None:
+                raise ValueError("enable_schedule_sweep: capacity_wh, charge_w, discharge_w and rules (or params) are required")
+            return schedule.quantize_sweep_params(capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w,
+                                                  rules=rules, n=self.n, n_variants=n_variants)
+
+        def last(host):   # the variants' rule arrays of the table's intervals on the device, and the rule count
+            torch = _torch()
+            K, R = int(host.shape[0]), schedule.n_rules_of(host[0])
+            if n_rules is not None and int(n_rules) != R:
+                raise ValueError(f"enable_schedule_sweep: n_rules {int(n_rules)} but the schedule sweep params hold {R} rules")
+            if rule_of_interval is None:
+                raise ValueError("enable_schedule_sweep: the schedule sweep needs rule_of_interval (the rule of each metering "
+                                 "interval, [n_intervals] or [K, n_intervals])")
+            a = rule_of_interval.cpu().numpy() if torch.is_tensor(rule_of_interval) else np.asarray(rule_of_interval)
+            if a.dtype != np.uint8:
+                if torch.is_tensor(rule_of_interval):
+                    raise ValueError("schedule sweep rule_of_interval must be a uint8 [n_intervals] or [K, n_intervals] array")
+                if a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) > 255)):
+                    raise ValueError("schedule sweep rule_of_interval must hold integers in [0, 255]")
+                a = a.astype(np.uint8)
+            a = schedule.check_sweep_rules(a, R, schedule.n_intervals(int(n_steps), int(interval_s)), K)
+            return torch.from_numpy(a).to(self.device), R
+        if n_steps is not None and self._dispatch_fleet is not None:
+            raise ValueError("a dispatch fleet series is enabled: it is battery dispatch's or the schedule's "
+                             "(the schedule sweep runs alone)")
+        raw = self._enable_battery("schedule_sweep", n_steps, interval_s, step0, buffer, soc, params, soc0_wh, quantize,
+                                   n_variants=n_variants, last=last)
+        if n_steps is not None:
+            self.schedule_sweep_rules = self._battery_args[2][0]
+        return raw
+
+    def schedule_sweep(self):
+        """Per variant and chain over the run (schedule.sweep_summary of schedule_sweep_raw and the parameters):
+        dispatch.sweep_summary's keys, float64 [K, n] each."""
+        from .schedule import sweep_summary
+        if self.schedule_sweep_raw is None:
+            raise ValueError("no schedule sweep tables: call enable_schedule_sweep first")
+        _torch().cuda.synchronize(self.device)
+        return sweep_summary(self.schedule_sweep_raw, self._schedule_sweep.interval_s, self.schedule_sweep_params)
 
     # ------------------------------------------------------------------ the battery fleet series
     def enable_battery_fleet(self, n_steps, step0=None, group_chains=0, buffer=None):

@@ -25,6 +25,13 @@ rule throughout, the table and the SoC are `dispatch`'s bit for bit.  The ask de
 constants and the time, never on the SoC, so the second is still a clamped addition followed by the drain's:
 `second_maps` gives the triples that storage.compose / storage.apply fold.  `from_traces` is the contract as a
 plain loop; `daily` builds the array of a daily local-time tariff.
+
+The schedule sweep (BatchedSim.enable_schedule_sweep, tmh_set_schedule_sweep) runs the same second for K <=
+SWEEP_MAX variants of every chain in one run -- a battery, R rule sets and a rule array each: one household under
+K tariffs and batteries.  params [K, 6 + 4 R, n], arrays uint8 [K, n_intervals], tables [K, n_intervals, 13, n],
+SoC [K, n]; variant v's slice is the schedule's bit for bit.  `sweep_from_traces` is the reference loop,
+`quantize_sweep_params`, `check_sweep_params` and `check_sweep_rules` mirror the dispatch sweep's, `sweep_summary`
+gives the run's totals per variant and chain and `energy_cost` what a tariff comparison ends in.
 """
 from __future__ import annotations
 
@@ -277,3 +284,195 @@ def fleet_from_traces(pv, meter, covered, interval_s, *, params, rule_of_interva
     x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (n,)), 0, cap)
     ok, d_all = battery._ok_d(pv, meter, covered)
     return dispatch._fleet_rows(base, ok, d_all, x, second, base.shape[0], int(group_chains) or max(n, 1))
+
+
+# The schedule sweep (tmh_set_schedule_sweep, BatchedSim.enable_schedule_sweep): the same second for K <= SWEEP_MAX
+# variants of every chain -- a battery, R rule sets and a rule array each -- in one run; variant v's table and SoC are
+# bit for bit what the schedule gives for params[v], rule_of_interval[v] and soc0[v].
+SWEEP_MAX = 16   # TMH_SCHEDULE_SWEEP_MAX
+
+
+def check_sweep_params(params, n_rules=None):
+    """Sweep parameters as an int64 [K, 6 + 4 R, n] array, 1 <= K <= SWEEP_MAX, every variant inside tmh_schedule's
+    ranges (check_params per variant; ValueError otherwise); n_rules, when given, is checked against the row count."""
+    params = np.asarray(params.cpu() if hasattr(params, "cpu") else params)
+    if params.ndim != 3 or params.dtype != np.int64:
+        raise ValueError("schedule sweep params must be an int64 [K, 6 + 4 R, n] array")
+    if not 1 <= params.shape[0] <= SWEEP_MAX:
+        raise ValueError(f"schedule sweep: {params.shape[0]} variants outside [1, {SWEEP_MAX}]")
+    for p in params:
+        check_params(p, n_rules)
+    return params
+
+
+def check_sweep_rules(rule_of_interval, n_rules, n_intervals, n_variants):
+    """The variants' rule arrays as uint8 [K, n_intervals] with every entry below n_rules; a [n_intervals] array is
+    every variant's (broadcast, a copy).  ValueError otherwise."""
+    a = np.asarray(rule_of_interval.cpu() if hasattr(rule_of_interval, "cpu") else rule_of_interval)
+    if a.dtype != np.uint8 or a.ndim not in (1, 2):
+        raise ValueError("schedule sweep rule_of_interval must be a uint8 [n_intervals] or [K, n_intervals] array")
+    if a.ndim == 1:
+        a = np.broadcast_to(a, (int(n_variants), a.shape[0]))
+    if a.shape != (int(n_variants), int(n_intervals)):
+        raise ValueError(f"schedule sweep rule_of_interval is {tuple(a.shape)} for {int(n_variants)} variants of "
+                         f"{int(n_intervals)} intervals")
+    if a.size and int(a.max()) >= int(n_rules):
+        raise ValueError(f"schedule sweep rule_of_interval names rule {int(a.max())} of {int(n_rules)}")
+    return np.ascontiguousarray(a)
+
+
+def quantize_sweep_params(capacity_wh, charge_w, discharge_w, charge_eff=1.0, discharge_eff=1.0, standby_w=0.0, *,
+                          rules, n, n_variants=None):
+    """The int64 [K, 6 + 4 R, n] parameters of a schedule sweep: each battery quantity and each value of a rule of
+    `rules` (quantize_params' dicts) a scalar (every variant and chain), a sequence of K values (one per variant,
+    uniform over the chains) or a [K, n] array; quantised per variant by quantize_params.  feed_in_limit_w=None, or
+    an entry that is None, means no limit.  Every variant has the len(rules) rules (one with fewer repeats one).  K
+    is n_variants when given, else the longest argument's length; ValueError when an argument's length is neither 1
+    nor K or K is outside [1, SWEEP_MAX]."""
+    rules = list(rules)
+    if not 1 <= len(rules) <= RULES_MAX:
+        raise ValueError(f"schedule sweep: {len(rules)} rules outside [1, {RULES_MAX}]")
+    none_w = NO_LIMIT / float(1 << FRAC_BITS)
+    names = list(battery.PARAMS)
+    vals = [capacity_wh, charge_w, discharge_w, charge_eff, discharge_eff, standby_w]
+    for r, rule in enumerate(rules):
+        unknown = set(rule) - {name + "_w" for name in RULE_PARAMS}
+        if unknown:
+            raise ValueError(f"schedule sweep rule {r}: unknown keys {sorted(unknown)}")
+        lim = rule.get("feed_in_limit_w")
+        if lim is None:
+            lim = none_w
+        elif not np.isscalar(lim):
+            lim = np.asarray(lim, dtype=object)
+            lim = np.where(lim == None, none_w, lim).astype(np.float64)   # noqa: E711 (elementwise)
+        vals += [rule.get("charge_above_w", 0.0), rule.get("discharge_above_w", 0.0), lim, rule.get("grid_charge_w", 0.0)]
+        names += [f"rule {r} {name}" for name in RULE_PARAMS]
+    args = [np.asarray(v, dtype=np.float64) for v in vals]
+    if any(a.ndim > 2 for a in args):
+        raise ValueError("schedule sweep quantities are scalars, [K] sequences or [K, n] arrays")
+    k = int(n_variants) if n_variants is not None else max([a.shape[0] for a in args if a.ndim] or [1])
+    if not 1 <= k <= SWEEP_MAX:
+        raise ValueError(f"schedule sweep: {k} variants outside [1, {SWEEP_MAX}]")
+    for name, a in zip(names, args):
+        if a.ndim and a.shape[0] not in (1, k):
+            raise ValueError(f"schedule sweep {name}: {a.shape[0]} values for {k} variants")
+        if a.ndim == 2 and a.shape[1] not in (1, int(n)):
+            raise ValueError(f"schedule sweep {name}: {a.shape[1]} values for {n} chains")
+    rows = [np.broadcast_to(a if a.ndim == 2 else a.reshape(-1, 1), (k, a.shape[1] if a.ndim == 2 else 1)) for a in args]
+    keys = [name + "_w" for name in RULE_PARAMS]
+    return np.stack([quantize_params(*(row[v] for row in rows[:6]),
+                                     rules=[dict(zip(keys, (row[v] for row in rows[6 + 4 * r:10 + 4 * r])))
+                                            for r in range(len(rules))], n=int(n)) for v in range(k)])
+
+
+def quantize_sweep_soc(soc0_wh, params):
+    """The starting SoC [K, n] of a sweep's batteries from watt-hours (a scalar, [K] or [K, n]); ValueError
+    outside [0, C]."""
+    k, _, n = params.shape
+    a = np.asarray(soc0_wh, dtype=np.float64)
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)
+    a = np.broadcast_to(a, (k, n))
+    return np.stack([quantize_soc(a[v], params[v, :6]) for v in range(k)])
+
+
+def sweep_from_traces(pv, meter, covered, interval_s, *, params, rule_of_interval, soc0, origin=0):
+    """The schedule sweep of time-major traces [n_steps, n_chains]: every chain under each of K variants -- (int64
+    [K, n_intervals, 13, n_chains], int64 [K, n_chains]), variant v what from_traces gives for params[v],
+    rule_of_interval[v] and soc0[v].  One pass over the seconds with the state [K, n]: the second is written out here
+    on [K, n] arrays, apart from from_traces and _ask, so that comparing the two compares two derivations.  params:
+    int64 [K, 6 + 4 R, n_chains]; rule_of_interval: uint8 [n_intervals] (every variant's) or [K, n_intervals]; soc0:
+    a scalar, [K, 1] or [K, n_chains], clamped into [0, C]."""
+    pv, meter, covered = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (pv, meter, covered))
+    base = intervals.from_traces(pv, meter, covered, interval_s, origin=origin)      # (checks the arguments)
+    interval_s, origin = int(interval_s), int(origin)
+    if interval_s > MAX_INTERVAL_S:
+        raise ValueError("interval_s <= 2^23 - 1")
+    n_steps, n = pv.shape
+    params = check_sweep_params(params)
+    if params.shape[2] != n:
+        raise ValueError(f"schedule sweep params for {params.shape[2]} chains, traces of {n}")
+    K, R = params.shape[0], n_rules_of(params[0])
+    arr = check_sweep_rules(rule_of_interval, R, base.shape[0], K).astype(np.int64)
+    cap, pc, pd, ec, ed, sb = (params[:, r] for r in range(6))                           # [K, n] each
+    kc, kd = ((1 << 32) - 1) // ec + 1, ((1 << 32) - 1) // ed + 1
+    rule_rows = params[:, 6:].reshape(K, R, len(RULE_PARAMS), n)
+    vs = np.arange(K)
+    out = np.zeros((K, base.shape[0], len(COLUMNS), n), dtype=np.int64)
+    out[:, :, :4] = base[None]
+    x = np.clip(np.broadcast_to(np.asarray(soc0, dtype=np.int64), (K, n)), 0, cap)
+    nan = np.isnan(pv) | np.isnan(meter) | (covered == 255)
+    qd = np.where(nan, 0, quantize(pv) - quantize(meter)).astype(np.int64)
+    k_at = -1
+    for t in range(n_steps):
+        k, o = divmod(origin + t, interval_s)
+        if k != k_at:                                                       # each variant's rule of the interval
+            tc, td, lim, grid = (rule_rows[vs, arr[:, k], j] for j in range(len(RULE_PARAMS)))
+            k_at = k
+        oks, d = ~nan[t][None], qd[t][None]                                 # [1, n] against the variants' [K, n]
+        charge = np.minimum(np.clip(d - tc, 0, None), pc)                   # from the surplus above Tc
+        drain = np.minimum(np.clip(-d - td, 0, None), pd)                   # into the deficit above Td
+        plain = np.where(d >= 0, charge, -drain)
+        ask = np.where(grid > 0, np.minimum(np.clip(plain, 0, None) + grid, pc), plain)   # grid charging: never discharges
+        up = ask >= 0
+        mag = np.abs(ask)
+        stored = np.where(up, (mag * ec) >> 16, -((mag * kd + 65535) >> 16))
+        x1 = np.minimum(np.maximum(x + stored, 0), cap)
+        moved = x1 - x
+        cost = np.where(moved > 0, (moved * kc + 65535) >> 16, (-moved * ed) >> 16)   # at the meter side, unsigned
+        clipped = np.sign(moved) * np.minimum(mag, cost)
+        b = np.where(moved == stored, ask, clipped)
+        xn = np.maximum(x1 - sb, 0)
+        rest = d - b                                                        # left at the meter
+        imp = np.where(rest < 0, -rest, 0)
+        sur = np.where(rest > 0, rest, 0)
+        fed = np.where(sur > lim, lim, sur)
+        cell = out[:, k]
+        cell[:, 4] += np.where(oks, imp, 0)
+        cell[:, 5] += np.where(oks, fed, 0)
+        cell[:, 6] += np.where(oks, np.maximum(b, 0), 0)
+        cell[:, 7] += np.where(oks, np.maximum(-b, 0), 0)
+        cell[:, 8] = np.where(oks, ((o + 1) << KEY_SHIFT) | xn, cell[:, 8])
+        cell[:, 9] += np.where(oks, b - (xn - x), 0)
+        cell[:, 10] += np.where(oks, sur - fed, 0)
+        cell[:, 11] = np.maximum(cell[:, 11], np.where(oks, demand.pack(imp, o), 0))
+        cell[:, 12] = np.maximum(cell[:, 12], np.where(oks, demand.pack(fed, o), 0))
+        x = np.where(oks, xn, x)
+    return out, x
+
+
+def sweep_summary(raw, interval_s, params, fleet=False):
+    """Per variant and chain, over all the intervals of a raw schedule sweep table [K, n_intervals, 13, n] with the
+    parameters [K, 6 + 4 R, n]: dispatch.sweep_summary's keys, float64 [K, n] each (fleet=True: [K], of the integer
+    totals over the chains).  The rules do not enter the summary: the battery's six rows do."""
+    raw = np.asarray(raw.cpu() if hasattr(raw, "cpu") else raw).astype(np.int64, copy=False)
+    params = check_sweep_params(params)
+    if raw.ndim != 4 or raw.shape[2] != len(COLUMNS) or raw.shape[0] != params.shape[0] or raw.shape[3] != params.shape[2]:
+        raise ValueError("raw schedule sweep table must be [K, n_intervals, 13, n] with params [K, 6 + 4 R, n]")
+    rule0 = np.zeros((params.shape[0], 3, params.shape[2]), dtype=np.int64)   # (a valid dispatch rule: unused by the summary)
+    return dispatch.sweep_summary(raw, interval_s, np.concatenate([params[:, :6], rule0], axis=1), fleet=fleet)
+
+
+def energy_cost(table, import_price, feed_in_price):
+    """What the energy of a raw table costs, per variant and chain: the sum over the intervals of import_price times
+    the interval's import minus feed_in_price times its export, float64 [K, n] from the integer columns 4 and 5 of a
+    raw table [K, n_intervals, 13, n] (or [n] of a single table [n_intervals, 13, n]).  Both prices are in currency
+    per kWh; import_price is a scalar, [n_intervals] (a time-of-use tariff) or [K, n_intervals] (a tariff per
+    variant), feed_in_price a scalar.  The number a tariff comparison ends in."""
+    raw = np.asarray(table.cpu() if hasattr(table, "cpu") else table).astype(np.int64, copy=False)
+    if raw.ndim not in (3, 4) or raw.shape[-2] != len(COLUMNS):
+        raise ValueError("energy_cost: a raw table [K, n_intervals, 13, n] or [n_intervals, 13, n]")
+    single = raw.ndim == 3
+    if single:
+        raw = raw[None]
+    K, nk = raw.shape[:2]
+    price = np.asarray(import_price, dtype=np.float64)
+    if price.ndim > 2 or (price.ndim >= 1 and price.shape[-1] != nk) or (price.ndim == 2 and price.shape[0] != K):
+        raise ValueError(f"energy_cost: import_price is a scalar, [{nk}] or [{K}, {nk}]")
+    if np.ndim(feed_in_price) != 0:
+        raise ValueError("energy_cost: feed_in_price is a scalar")
+    price = np.broadcast_to(price, (K, nk))
+    kwh = float(1 << FRAC_BITS) * 3600.0 * 1000.0                           # a column's units per kWh
+    cost = (price[:, :, None] * raw[:, :, 4].astype(np.float64)).sum(axis=1) / kwh
+    cost -= float(feed_in_price) * raw[:, :, 5].sum(axis=1).astype(np.float64) / kwh
+    return cost[0] if single else cost
